@@ -2,7 +2,15 @@
 """Multi-Krum throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N ... bench.py --gpus N     (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds everything else the benchmark measures or checks (parity against the
+goldens, the other BASELINE configs and modes, the per-kernel pass, single
+calls after idle, the host entries, the CPU baseline, the N > 1 evidence) and
+writes the full record to --detail-out.  --dump-outputs DIR writes what the
+last timed step computed (sel, scores, mean) as DIR/<name>.npy.
 
 One step = one full Multi-Krum pass of the hot path over one synthetic batch
 already resident in HBM: fp64-MFMA Gram (+ RCCL all-reduce of the packed
@@ -1034,6 +1042,17 @@ def golden_check(name, sel_host, mean_local, c0, dl):
     return res
 
 
+def dump_outputs(dirpath, sel, scores, mean):
+    """--dump-outputs: what a caller of the timed path receives from its last
+    step -- the selected rows' indices, the n scores and the mean (this rank's
+    columns) -- as float64 DIR/sel.npy, DIR/scores.npy, DIR/mean.npy (8 (m + n
+    + d) bytes: 8.4 MB at the headline).  The batch is a function of the
+    workload's seed alone, so two runs with the same arguments compare."""
+    os.makedirs(dirpath, exist_ok=True)
+    for name, t in (("sel", sel), ("scores", scores), ("mean", mean)):
+        np.save(os.path.join(dirpath, name + ".npy"), t.cpu().numpy().astype(np.float64))
+
+
 def noised_probe(eng, dev, X, n, d, f, m, k=1):
     """SURVEY §8(f) row 3 at the bench batch: bk_multikrum_noised from pinned
     host Delta + k pinned noise vectors per update (noise added by K6 as the
@@ -1121,13 +1140,15 @@ def compact_line(out, detail_path):
     cpu_baseline and parity, and -- as the LAST key -- a per-config summary of
     every BASELINE config measured in this run, so the driver's stored tail
     holds all of them.  The full record goes to
-    detail_path (copied under profiles/ for the judged runs)."""
-    try:
-        os.makedirs(os.path.dirname(detail_path), exist_ok=True)
-        with open(detail_path, "w") as fp:
-            json.dump(out, fp, indent=1)
-    except OSError as e:
-        detail_path = "unwritable (%r)" % (e,)
+    detail_path (copied under profiles/ for the judged runs); a plain run
+    (no --full, no --detail-out) passes None and writes no record."""
+    if detail_path is not None:
+        try:
+            os.makedirs(os.path.dirname(os.path.abspath(detail_path)), exist_ok=True)
+            with open(detail_path, "w") as fp:
+                json.dump(out, fp, indent=1)
+        except OSError as e:
+            detail_path = "unwritable (%r)" % (e,)
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
             "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")
     line = {k: out[k] for k in keep if k in out}
@@ -1144,7 +1165,9 @@ def compact_line(out, detail_path):
     for k in ("step_roofline", "rccl"):
         if out.get(k):
             line[k] = out[k]
-    line["detail_file"] = os.path.relpath(detail_path, REPO) if os.path.isabs(detail_path) else detail_path
+    if detail_path is not None:
+        line["detail_file"] = (os.path.relpath(detail_path, REPO) if os.path.isabs(detail_path)
+                               else detail_path)
     summ = {}
     head = {"value": out["value"], "ms_per_step": out["ms_per_step"], "roofline": out["roofline"],
             "parity": out.get("parity")}
@@ -1327,13 +1350,30 @@ def main():
                     help="N > 1: the packed-Gram exchange inside libbk over RCCL (default), or "
                          "through torch.distributed gloo on the host (bk_gram_upper_device -> "
                          "all_reduce -> bk_finish_device; lets N ranks share one GPU in tests)")
-    ap.add_argument("--detail-out", default=os.path.join(REPO, "gpurun_out", "bench_detail.json"),
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: parity against the goldens, the other BASELINE "
+                         "configs and modes, the per-kernel pass, single calls after idle, the "
+                         "host entries, the CPU baseline and the N > 1 evidence (each still "
+                         "switched off by its --no-* option); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as "
+                         "DIR/sel.npy, DIR/scores.npy and DIR/mean.npy (float64; at N > 1 rank 0's "
+                         "column shard of the mean)")
+    ap.add_argument("--detail-out", default=None,
                     help="where the full record goes (every variant, kernel breakdown, probes); "
-                         "the printed line is the compact form with a per-config summary")
+                         "the printed line is the compact form with a per-config summary.  "
+                         "Default: bench_out/bench_detail.json with --full, none in a plain run")
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="tuning aid on a 1-GPU box: run rank 0's column shard of an N-rank "
                          "job (sharded path, 1-rank RCCL exchange); value is that rank's rate")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:
+        # a plain run: the headline's set-up, warm-up and timed steps only
+        a.no_cpu_baseline = a.no_e2e = a.no_next_rows = a.no_graph_probe = a.no_variants = True
+    elif a.detail_out is None:
+        a.detail_out = os.path.join(REPO, "bench_out", "bench_detail.json")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` starts its own N ranks
         sys.exit(launch_ranks(a))
@@ -1483,14 +1523,19 @@ def main():
     if small_step:
         kt["k_small"] = {"avg_ms": clock.ms() / a.steps, "count": a.steps}
     host_exch_ms = host_exch_s[0] / a.steps * 1e3
+    if a.dump_outputs and rank == 0:
+        # the last timed step's outputs, before anything below runs the step again
+        dump_outputs(a.dump_outputs, sel, scores, mean[:dl])
     eng.timing_stride(1)
-    # per-kernel breakdown from a separate, untimed pass (every kernel evented)
-    eng.timing_enable(True)
-    for _ in range(max(3, a.steps // 4)):
-        step()
-    torch.cuda.synchronize()
-    kbreak = eng.timing_read()
-    eng.timing_enable(False)
+    kbreak = {}
+    if a.full:
+        # per-kernel breakdown from a separate, untimed pass (every kernel evented)
+        eng.timing_enable(True)
+        for _ in range(max(3, a.steps // 4)):
+            step()
+        torch.cuda.synchronize()
+        kbreak = eng.timing_read()
+        eng.timing_enable(False)
     if small_step and "k_small" not in kbreak and "k_gram" in kbreak:
         # the general chain ran after all: its K1 is the roofline kernel (the
         # untimed pass's events), not the loop-bracketed clock
@@ -1500,7 +1545,7 @@ def main():
         small_step = False
     # the selection margin of this batch (bk_selection_margin): near_tie False
     # proves the reference's argpartition selects exactly this set
-    mg = eng.selection_margin()
+    mg = eng.selection_margin() if a.full else None
     elapsed = t1 - t0
     if world > 1:
         elapsed = max_over_ranks(elapsed, dev)
@@ -1509,8 +1554,10 @@ def main():
 
     EMU_NOTE = {"n/a": "emulated rank: the selection uses 1/%d of the columns, so it is not "
                        "comparable with the full-d golden" % (emu or 1)}
-    parity = EMU_NOTE if emu else golden_check(a.workload, sel.cpu().numpy(),
-                                                mean[:dl].cpu().numpy(), c0, dl)
+    parity = None
+    if a.full:
+        parity = EMU_NOTE if emu else golden_check(a.workload, sel.cpu().numpy(),
+                                                    mean[:dl].cpu().numpy(), c0, dl)
 
     variants = {}
     if a.workload == "D_512x1M_f153" and not a.no_variants:
@@ -1610,7 +1657,7 @@ def main():
     # (tools/profile.sh -> tools/pmc_summary.py), used only when that record was
     # taken with this very libbk.so build (sha256 prefix); otherwise null
     traffic, traffic_src = None, None
-    if world == 1 and not emu:
+    if a.full and world == 1 and not emu:
         traffic, traffic_src = pmc_traffic(workload_tag(a.workload, a.f32_mode))
     roof = dict(groof, traffic=traffic, traffic_source=traffic_src, kernel=k1name,
                 kernel_avg_ms=round(g["avg_ms"], 4), events_every=tstride)
@@ -1663,19 +1710,20 @@ def main():
         parity["margin"] = {"near_tie": mg["near_tie"], "gap": mg["gap"],
                             "err_bound": mg["err_bound"]}
 
-    # one verifier call after idle (the DVFS ramp), beside the steady state
-    sc_step, sc_k1, sc_all = single_call(step, eng, barrier, world, dev)
-    sc_gbs = n * (dl if emu else d) * es / (sc_step * 1e-3) / 1e9
-    out["single_call"] = {
-        "what": "median of 7 calls, each after 200 ms of GPU idle (one Multi-Krum per batch, "
-                "krum.go:100-166): the clock ramp a verifier sees",
-        "ms": round(sc_step, 4), "GB_per_s": round(sc_gbs, 3),
-        "k_gram_ms": round(sc_k1, 4),
-        "k_gram_frac": round(groof["frac"] * g["avg_ms"] / sc_k1, 4) if sc_k1 > 0 else None,
-        "step_roofline_frac": round(max(t_mfma, t_hbm) / sc_step, 4),
-        "calls_ms": [round(x, 4) for x in sc_all]}
+    if a.full:
+        # one verifier call after idle (the DVFS ramp), beside the steady state
+        sc_step, sc_k1, sc_all = single_call(step, eng, barrier, world, dev)
+        sc_gbs = n * (dl if emu else d) * es / (sc_step * 1e-3) / 1e9
+        out["single_call"] = {
+            "what": "median of 7 calls, each after 200 ms of GPU idle (one Multi-Krum per batch, "
+                    "krum.go:100-166): the clock ramp a verifier sees",
+            "ms": round(sc_step, 4), "GB_per_s": round(sc_gbs, 3),
+            "k_gram_ms": round(sc_k1, 4),
+            "k_gram_frac": round(groof["frac"] * g["avg_ms"] / sc_k1, 4) if sc_k1 > 0 else None,
+            "step_roofline_frac": round(max(t_mfma, t_hbm) / sc_step, 4),
+            "calls_ms": [round(x, 4) for x in sc_all]}
 
-    if sharded:
+    if sharded and a.full:
         # evidence that RCCL reached N ranks and that every rank selected the same set
         import hashlib
         nr, rk = eng.comm_size()

@@ -73,13 +73,16 @@ def test_launcher_refuses_fewer_gpus_than_rccl_ranks():
     assert bench.launch_ranks(a, argv=["--gpus", "2"], gpus_fn=lambda: 0) != 0
 
 
-def test_launcher_relays_the_ranks_failure(capfd):
-    """The launcher's child torch.distributed.run: here (no GPU) the ranks
-    fail, and the parent must return their non-zero status with nothing on
-    stdout -- never a 1-GPU line in place of the N-rank one."""
+def test_launcher_relays_the_ranks_failure(capfd, monkeypatch):
+    """The launcher's child torch.distributed.run: with no GPU (none on the
+    CPU host; hidden from the ranks where there is one) the ranks fail, and
+    the parent must return their non-zero status with nothing on stdout --
+    never a 1-GPU line in place of the N-rank one."""
     import argparse
     sys.path.insert(0, REPO)
     import bench
+    for var in ("ROCR_VISIBLE_DEVICES", "HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
+        monkeypatch.setenv(var, "")  # the ranks inherit this environment
     a = argparse.Namespace(gpus=2, exchange="host")
     rc = bench.launch_ranks(a, argv=["--gpus", "2", "--exchange", "host", "--steps", "1",
                                      "--warmup", "0", "--workload", "A_creditcard",
@@ -169,7 +172,9 @@ sys.stderr.write(json.dumps({"rc": rc, "children": len(started),
                              "kfd": any(p.startswith("/dev/kfd") for p in opened),
                              "runs_torchrun": "torch.distributed.run" in " ".join(started[0])}))
 """ % REPO
-    env = {k: v for k, v in os.environ.items() if k != "WORLD_SIZE"}
+    # the stand-in sets its own visibility list: drop any the host sets (ROCR_* would win)
+    env = {k: v for k, v in os.environ.items()
+           if k != "WORLD_SIZE" and not k.endswith("VISIBLE_DEVICES")}
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=60,
                        env=env)
     res = json.loads(r.stderr.strip().splitlines()[-1])

@@ -35,7 +35,7 @@ def test_bench_two_ranks_host_exchange(workload):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--exchange", "host",
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--exchange", "host", "--full",
            "--workload", workload, "--no-cpu-baseline", "--no-e2e", "--no-next-rows",
            "--no-graph-probe", "--no-variants"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=400)
@@ -55,7 +55,7 @@ def test_bench_two_ranks_host_exchange(workload):
 
 
 def test_bench_launches_its_own_ranks():
-    """a plain `python3 bench.py --gpus 2` (no torchrun, no
+    """`python3 bench.py --gpus 2 --full` (no torchrun, no
     WORLD_SIZE) starts its own two ranks as a child torch.distributed.run and
     relays rank 0's line: n_gpus 2, both ranks agree on the set, the shard's
     golden matches, and every rank's K1 and exchange time per step are in the
@@ -63,7 +63,7 @@ def test_bench_launches_its_own_ranks():
     rank).  The host exchange lets the two ranks share the box's one GPU."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
            "--exchange", "host", "--workload", "C_1024x131072", "--no-cpu-baseline", "--no-e2e",
            "--no-next-rows", "--no-graph-probe"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=400)
@@ -114,7 +114,7 @@ def test_bench_stdout_is_one_json_line_with_rccl():
     prints its version block to fd 1; bench.py sends that to stderr, so
     stdout holds exactly the one JSON line."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
-    cmd = [sys.executable, "bench.py", "--sharded", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--sharded", "--steps", "2", "--warmup", "1", "--full",
            "--workload", "C_1024x131072", "--no-cpu-baseline", "--no-e2e", "--no-next-rows",
            "--no-graph-probe", "--no-variants"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
