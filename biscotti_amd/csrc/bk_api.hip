@@ -258,6 +258,9 @@ struct bk_ctx {
     int wait_value_ok = -1;         // hipDeviceAttributeCanUseStreamWaitValue (-1: not asked)
     int64_t exchanges = 0;        // exchanges of the packed Gram (bk_comm_stats)
     double exchanged_bytes = 0;   // bytes each rank put into them
+    // bk_collect_*: the incremental collection (bk_collect.hip), which owns its
+    // buffers -- none of the workspace above, so batch calls leave it intact
+    bk::Collect *collect = nullptr;
 };
 
 namespace {
@@ -1727,6 +1730,37 @@ int host_certified_rerun(bk_ctx *c, const void *dX, int dtype, int64_t n, int64_
 
 }  // namespace
 
+// the hooks of bk_collect.hip (bk_internal.h)
+namespace bk {
+
+int api_fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+CtxRef ctx_ref(bk_ctx *c) { return CtxRef{&c->mu, c->device, c->num_cu, &c->stream, &c->collect}; }
+
+int ctx_finish_upper(bk_ctx *c, const double *U, int64_t n, int64_t f, int64_t *d_sel,
+                     double *d_scores) {
+    Plan pl;
+    pl.n = (int)n;
+    pl.T = (int)((n + 63) / 64);
+    pl.ntile = pl.T * (pl.T + 1) / 2;
+    return stage_finish(c, U, pl, nullptr, BK_F64, n, 0, 0, f, d_sel, d_scores, nullptr);
+}
+
+int ctx_wait_finish(bk_ctx *c) {
+    HIPCHK(wait_stream(c));
+    return check_margin_readback(c);
+}
+
+}  // namespace bk
+
 extern "C" {
 
 int bk_abi_version(void) { return BK_ABI_VERSION; }
@@ -1841,6 +1875,7 @@ void bk_destroy(bk_ctx *c) {
             if (sgc) (void)hipFree(sgc);
         if (c->hsig) (void)hipHostFree(c->hsig);
         if (c->rstage) (void)hipHostFree(c->rstage);
+        collect_destroy(c->collect);
         delete c->hpool;
         if (c->copy) (void)hipStreamDestroy(c->copy);
         for (void *p : c->staged) (void)hipHostFree(p);

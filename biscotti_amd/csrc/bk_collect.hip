@@ -1,0 +1,550 @@
+// bk_collect.hip -- incremental Multi-Krum (include/bk.h bk_collect_*): the
+// verifier's updates arrive one RPC at a time (VerifyUpdateKRUM, krum.go:227-365),
+// so each row is uploaded and folded into the Gram when it arrives, and only
+// the scores, the selection and the mean remain after the last arrival.
+//
+// Per collection (one per context, all on the context stream):
+//   store   n_cap x ld rows in the input dtype, 16-B aligned rows, pad columns 0
+//   G       the Gram by arrival slot, fp64, lower-triangular packed: row j holds
+//           G[j][0..j] at j (j + 1) / 2, so an arrival writes one contiguous run
+//   ring    a small pinned ring through which pageable rows cross PCIe
+// Kernels:
+//   k_border         <x_i, x_j> partials of up to BORDER_ROWS new slots j against
+//                    every slot i <= j, per chunk of BORDER_CHUNK_BYTES of a row
+//   k_border_reduce  the chunks' partials summed in a fixed order -> G
+//   k_collect_gather G, through the caller's order -> the packed upper + record
+//   k_collect_selmap the selection mapped to arrival slots, for K4 on the store
+// Every element of G is the same sum whatever the add's count and however many
+// rows are resident: chunk s covers the same columns, one wave sums a chunk's
+// products in lane order and the chunks are added in the same tree, so the
+// order depends on (d, dtype) alone.  No atomics, plain vector stores.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "../../include/bk.h"
+#include "bk_internal.h"
+
+using namespace bk;
+
+namespace {
+
+constexpr int BORDER_ROWS = 8;            // new rows per k_border launch (their chunks in LDS)
+constexpr int BORDER_CHUNK_BYTES = 8192;  // of one row per workgroup: 64 lanes x 8 loads x 16 B
+constexpr int BORDER_VPL = BORDER_CHUNK_BYTES / 16 / 64;  // 16-B loads per lane per row
+constexpr size_t RING_SLOT_BYTES = (size_t)1 << 20;
+constexpr int RING_SLOTS = 8;
+
+typedef double cd2 __attribute__((ext_vector_type(2)));
+typedef float cf4 __attribute__((ext_vector_type(4)));
+template <typename T>
+struct Vec16;
+template <>
+struct Vec16<double> {
+    typedef cd2 type;
+    static constexpr int N = 2;
+};
+template <>
+struct Vec16<float> {
+    typedef cf4 type;
+    static constexpr int N = 4;
+};
+
+// grid (S chunks, row blocks of rpb rows), 256 threads.  Chunk s = columns
+// [s KC, s KC + KC), KC = BORDER_CHUNK_BYTES / sizeof(T).  The C new rows'
+// chunks sit in LDS (C x 8 KiB); each wave streams one resident (or new) row i
+// of its block straight into registers, 8 x 16 B per lane, and keeps C x N fp64
+// accumulators: element e of load t multiplies the new row's element of the
+// same column (fp32 widened: the product is exact) and is added by one fma, t
+// ascending; the N accumulators are added in order, then the 64 lanes by a
+// xor butterfly (32, 16, .., 1).  P[(s C + c) jend + i] = the chunk's partial
+// of <x_i, x_{j0 + c}>, written for i <= j0 + c < jend only.
+template <typename T, int C>
+__global__ __launch_bounds__(256) void k_border(const T *__restrict__ store, int64_t ld, int64_t d,
+                                                int j0, int jend, int rpb,
+                                                double *__restrict__ P) {
+    typedef typename Vec16<T>::type V;
+    constexpr int N = Vec16<T>::N;
+    constexpr int VPC = BORDER_CHUNK_BYTES / 16;  // 16-B vectors per row chunk
+    extern __shared__ __attribute__((aligned(16))) unsigned char border_lds[];
+    V *lv = reinterpret_cast<V *>(border_lds);
+    const int tid = threadIdx.x, s = blockIdx.x;
+    const int64_t c0 = (int64_t)s * (VPC * N);
+    for (int v = tid; v < C * VPC; v += 256) {
+        const int c = v / VPC, q = v % VPC;
+        const int jr = j0 + c < jend ? j0 + c : jend - 1;  // a launch of fewer than C rows
+        const int64_t col = c0 + (int64_t)q * N;
+        V x = {};
+        if (col < d) x = *reinterpret_cast<const V *>(store + (int64_t)jr * ld + col);
+        lv[v] = x;
+    }
+    __syncthreads();
+    const int w = tid >> 6, lane = tid & 63;
+    const int r0 = (int)blockIdx.y * rpb;
+    const int r1 = r0 + rpb < jend ? r0 + rpb : jend;
+    for (int i = r0 + w; i < r1; i += 4) {
+        const T *row = store + (int64_t)i * ld + c0;
+        V x[BORDER_VPL];
+#pragma unroll
+        for (int t = 0; t < BORDER_VPL; ++t) {
+            const int q = t * 64 + lane;
+            V z = {};
+            x[t] = c0 + (int64_t)q * N < d
+                       ? __builtin_nontemporal_load(reinterpret_cast<const V *>(row) + q)
+                       : z;
+        }
+        double acc[C][N];
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+#pragma unroll
+            for (int e = 0; e < N; ++e) acc[c][e] = 0.0;
+        // C = 1: the new row's chunk stays in registers across the rows (the
+        // LDS reads hoist); more new rows would take C x 32 registers and the
+        // occupancy with them, so their reads stay in the loop
+        int ll = lane;
+        if constexpr (C > 1) asm volatile("" : "+v"(ll));
+#pragma unroll
+        for (int t = 0; t < BORDER_VPL; ++t)
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const V y = lv[c * VPC + t * 64 + ll];
+#pragma unroll
+                for (int e = 0; e < N; ++e)
+                    acc[c][e] = __builtin_fma((double)x[t][e], (double)y[e], acc[c][e]);
+            }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            double v = acc[c][0];
+#pragma unroll
+            for (int e = 1; e < N; ++e) v += acc[c][e];
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+            if (lane == c && j0 + c < jend && i <= j0 + c)
+                P[((int64_t)s * C + c) * jend + i] = v;
+        }
+    }
+}
+
+// one wave per element (c, i), i <= j0 + c: lane l adds the partials of chunks
+// l, l + 64, .. in that order, then the lanes by the same butterfly -> G
+__global__ __launch_bounds__(256) void k_border_reduce(const double *__restrict__ P, int S, int C,
+                                                       int j0, int jend, double *__restrict__ G) {
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (item >= (int64_t)(jend - j0) * jend) return;  // wave-uniform
+    const int c = (int)(item / jend), i = (int)(item % jend);
+    const int j = j0 + c;
+    if (i > j) return;
+    double v = 0.0;
+    for (int s = lane; s < S; s += 64) v += P[((int64_t)s * C + c) * jend + i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    if (lane == 0) G[(int64_t)j * (j + 1) / 2 + i] = v;
+}
+
+// The packed upper of the caller's rows 0..n-1 (bk_upper_elems(n): 64x64
+// sub-tiles, diagonal tiles valid for ir <= ic; the rest 0) from G through
+// order (row a of the caller = arrival slot order[a]), and the trailing
+// record {d, 0, 0, 0}.  One sub-tile per workgroup.
+__global__ __launch_bounds__(256) void k_collect_gather(const double *__restrict__ G,
+                                                        const int64_t *__restrict__ order, int n,
+                                                        int T, double dcols,
+                                                        double *__restrict__ U) {
+    __shared__ int64_t so[128];
+    int br = 0, rem = (int)blockIdx.x;
+    while (rem >= T - br) {
+        rem -= T - br;
+        ++br;
+    }
+    const int bc = br + rem;
+    if (threadIdx.x < 128) {
+        const int r = (threadIdx.x < 64 ? br * 64 : bc * 64 - 64) + (int)threadIdx.x;
+        so[threadIdx.x] = r < n ? order[r] : -1;
+    }
+    __syncthreads();
+    double *tile = U + (int64_t)blockIdx.x * 4096;
+    for (int e = threadIdx.x; e < 4096; e += 256) {
+        const int ir = e >> 6, ic = e & 63;
+        const int64_t oa = so[ir], ob = so[64 + ic];
+        double v = 0.0;
+        if (oa >= 0 && ob >= 0 && (br < bc || ir <= ic)) {
+            const int64_t hi = oa > ob ? oa : ob, lo = oa > ob ? ob : oa;
+            v = G[hi * (hi + 1) / 2 + lo];
+        }
+        tile[e] = v;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < BK_UPPER_TRAIL)
+        U[(int64_t)T * (T + 1) / 2 * 4096 + threadIdx.x] = threadIdx.x == 0 ? dcols : 0.0;
+}
+
+// K4 reads the row store: its sel list is the selection (the caller's row
+// indices, ascending) mapped to arrival slots, in the same order
+__global__ __launch_bounds__(256) void k_collect_selmap(const int64_t *__restrict__ sel,
+                                                        const int64_t *__restrict__ order, int m,
+                                                        int64_t *__restrict__ slots) {
+    const int r = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (r < m) slots[r] = order[sel[r]];
+}
+
+template <typename T>
+hipError_t launch_border_t(const T *store, int64_t ld, int64_t d, int j0, int cnt, int S, int rpb,
+                           int RB, double *P, hipStream_t st) {
+    const dim3 grid((unsigned)S, (unsigned)RB), block(256);
+    const int jend = j0 + cnt;
+#define BK_BORDER(C)                                                                        \
+    hipLaunchKernelGGL((k_border<T, C>), grid, block, (size_t)(C) * BORDER_CHUNK_BYTES, st, \
+                       store, ld, d, j0, jend, rpb, P)
+    if (cnt == 1)
+        BK_BORDER(1);
+    else if (cnt == 2)
+        BK_BORDER(2);
+    else if (cnt <= 4)
+        BK_BORDER(4);
+    else
+        BK_BORDER(8);
+#undef BK_BORDER
+    return hipGetLastError();
+}
+
+int border_c(int cnt) { return cnt == 1 ? 1 : cnt == 2 ? 2 : cnt <= 4 ? 4 : 8; }
+
+struct Buf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    bool pinned = false;
+};
+
+}  // namespace
+
+namespace bk {
+
+struct Collect {
+    bool begun = false;
+    int dtype = BK_F64;
+    int64_t n_cap = 0, d = 0, ld = 0, count = 0;
+    int S = 0;  // chunks of a row: ceil(d es / BORDER_CHUNK_BYTES)
+    Buf store, G, P, U, sel, slots, scores, mean, mean_part, order, horder, ring;
+    hipEvent_t ev_slot[RING_SLOTS] = {};
+    bool slot_used[RING_SLOTS] = {};
+    int ring_next = 0;
+    hipEvent_t ev_up = nullptr;
+};
+
+void collect_destroy(Collect *k) {
+    if (!k) return;
+    for (Buf *b : {&k->store, &k->G, &k->P, &k->U, &k->sel, &k->slots, &k->scores, &k->mean,
+                   &k->mean_part, &k->order, &k->horder, &k->ring})
+        if (b->p) (void)(b->pinned ? hipHostFree(b->p) : hipFree(b->p));
+    for (hipEvent_t ev : k->ev_slot)
+        if (ev) (void)hipEventDestroy(ev);
+    if (k->ev_up) (void)hipEventDestroy(k->ev_up);
+    delete k;
+}
+
+}  // namespace bk
+
+namespace {
+
+#define CHIP(expr)                                                                             \
+    do {                                                                                       \
+        hipError_t _e = (expr);                                                                \
+        if (_e != hipSuccess)                                                                  \
+            return api_fail(_e == hipErrorOutOfMemory ? BK_ENOMEM : BK_EHIP, "%s: %s (%s:%d)", \
+                            #expr, hipGetErrorString(_e), __FILE__, __LINE__);                 \
+    } while (0)
+#define CCHK(expr)                  \
+    do {                            \
+        int _s = (expr);            \
+        if (_s != BK_OK) return _s; \
+    } while (0)
+
+struct DevGuard {
+    int prev = -1;
+    explicit DevGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        (void)hipSetDevice(dev);
+    }
+    ~DevGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// an error path of add / finish: queued copies may still read the caller's rows
+struct Drain {
+    hipStream_t st;
+    bool armed = true;
+    ~Drain() {
+        if (armed) (void)hipStreamSynchronize(st);
+    }
+};
+
+size_t esz(int dtype) { return dtype == BK_F64 ? 8 : 4; }
+
+// Grow the buffers in `want` to their sizes, all or nothing: the new blocks are
+// allocated first, and only when every one exists are the old ones freed
+int grow_all(const std::vector<std::pair<Buf *, size_t>> &want) {
+    std::vector<void *> fresh(want.size(), nullptr);
+    for (size_t i = 0; i < want.size(); ++i) {
+        Buf *b = want[i].first;
+        const size_t bytes = want[i].second < 256 ? 256 : want[i].second;
+        if (bytes <= b->bytes) continue;
+        const hipError_t e = b->pinned ? hipHostMalloc(&fresh[i], bytes, hipHostMallocPortable)
+                                       : hipMalloc(&fresh[i], bytes);
+        if (e != hipSuccess) {
+            for (size_t q = 0; q < i; ++q)
+                if (fresh[q]) (void)(want[q].first->pinned ? hipHostFree(fresh[q]) : hipFree(fresh[q]));
+            return api_fail(BK_ENOMEM, "bk_collect_begin: %s(%zu bytes): %s",
+                            b->pinned ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
+        }
+    }
+    for (size_t i = 0; i < want.size(); ++i) {
+        if (!fresh[i]) continue;
+        Buf *b = want[i].first;
+        if (b->p) (void)(b->pinned ? hipHostFree(b->p) : hipFree(b->p));
+        b->p = fresh[i];
+        b->bytes = want[i].second < 256 ? 256 : want[i].second;
+    }
+    return BK_OK;
+}
+
+// the border of slots [j0, j0 + cnt): groups of up to BORDER_ROWS new rows, each
+// group one k_border over every slot up to its last and one k_border_reduce
+int fold_border(Collect *k, int64_t j0, int64_t cnt, int num_cu, hipStream_t st) {
+    for (int64_t g0 = j0; g0 < j0 + cnt; g0 += BORDER_ROWS) {
+        const int gc = (int)(j0 + cnt - g0 < BORDER_ROWS ? j0 + cnt - g0 : BORDER_ROWS);
+        const int jend = (int)g0 + gc;
+        // row blocks: enough workgroups to fill the chip, at least one row per wave
+        int RB = (4 * num_cu + k->S - 1) / k->S;
+        if (RB > (jend + 3) / 4) RB = (jend + 3) / 4;
+        if (RB < 1) RB = 1;
+        if (RB > 65535) RB = 65535;
+        const int rpb = ((jend + RB - 1) / RB + 3) / 4 * 4;
+        RB = (jend + rpb - 1) / rpb;
+        hipError_t e = k->dtype == BK_F64
+                           ? launch_border_t((const double *)k->store.p, k->ld, k->d, (int)g0, gc,
+                                             k->S, rpb, RB, (double *)k->P.p, st)
+                           : launch_border_t((const float *)k->store.p, k->ld, k->d, (int)g0, gc,
+                                             k->S, rpb, RB, (double *)k->P.p, st);
+        if (e != hipSuccess) return api_fail(BK_EHIP, "k_border launch: %s", hipGetErrorString(e));
+        const int64_t items = (int64_t)gc * jend;
+        hipLaunchKernelGGL(k_border_reduce, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st,
+                           (const double *)k->P.p, k->S, border_c(gc), (int)g0, jend,
+                           (double *)k->G.p);
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return api_fail(BK_EHIP, "k_border_reduce launch: %s", hipGetErrorString(e));
+    }
+    return BK_OK;
+}
+
+// one pageable row through the pinned ring: the host copy of a piece overlaps
+// the DMA of the one before; on return the row is in the ring or on the device
+int upload_pageable(Collect *k, char *dst, const char *src, size_t bytes, hipStream_t st) {
+    for (size_t off = 0; off < bytes; off += RING_SLOT_BYTES) {
+        const size_t len = bytes - off < RING_SLOT_BYTES ? bytes - off : RING_SLOT_BYTES;
+        const int s = k->ring_next;
+        k->ring_next = (s + 1) % RING_SLOTS;
+        if (k->slot_used[s]) CHIP(hipEventSynchronize(k->ev_slot[s]));
+        char *slot = (char *)k->ring.p + (size_t)s * RING_SLOT_BYTES;
+        memcpy(slot, src + off, len);
+        CHIP(hipMemcpyAsync(dst + off, slot, len, hipMemcpyHostToDevice, st));
+        CHIP(hipEventRecord(k->ev_slot[s], st));
+        k->slot_used[s] = true;
+    }
+    return BK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bk_collect_begin(bk_ctx *c, int dtype, int64_t n_cap, int64_t d) {
+    if (!c) return api_fail(BK_EINVAL, "null context");
+    if (dtype != BK_F64 && dtype != BK_F32) return api_fail(BK_EINVAL, "bad dtype %d", dtype);
+    if (n_cap < 1 || d < 1)
+        return api_fail(BK_EINVAL, "need n_cap >= 1 and d >= 1 (n_cap=%lld d=%lld)",
+                        (long long)n_cap, (long long)d);
+    if (n_cap > BK_MAX_N)
+        return api_fail(BK_EINVAL, "n_cap=%lld exceeds BK_MAX_N=%d", (long long)n_cap, BK_MAX_N);
+    const CtxRef r = ctx_ref(c);
+    std::lock_guard<std::mutex> lk(*r.mu);
+    DevGuard dg(r.device);
+    const hipStream_t st = *r.stream;
+    Collect *k = *r.collect;
+    if (!k) {
+        k = new (std::nothrow) Collect();
+        if (!k) return api_fail(BK_ENOMEM, "host allocation of the collection failed");
+        k->horder.pinned = k->ring.pinned = true;
+        hipError_t e = hipEventCreateWithFlags(&k->ev_up, hipEventDisableTiming);
+        for (int s = 0; s < RING_SLOTS && e == hipSuccess; ++s)
+            e = hipEventCreateWithFlags(&k->ev_slot[s], hipEventDisableTiming);
+        if (e != hipSuccess) {
+            collect_destroy(k);
+            return api_fail(BK_EHIP, "bk_collect_begin: events: %s", hipGetErrorString(e));
+        }
+        *r.collect = k;
+    }
+    const size_t es = esz(dtype);
+    const int64_t per16 = 16 / (int64_t)es;
+    const int64_t ld = (d + per16 - 1) / per16 * per16;
+    const int S = (int)(((size_t)d * es + BORDER_CHUNK_BYTES - 1) / BORDER_CHUNK_BYTES);
+    const int64_t m_max = n_cap;
+    const size_t un = (size_t)n_cap;
+    // work of the old collection may still read the buffers about to be replaced
+    CHIP(hipStreamSynchronize(st));
+    CCHK(grow_all({{&k->store, un * (size_t)ld * es},
+                   {&k->G, un * (un + 1) / 2 * sizeof(double)},
+                   {&k->P, (size_t)S * BORDER_ROWS * un * sizeof(double)},
+                   {&k->U, (size_t)bk_upper_elems(n_cap) * sizeof(double)},
+                   {&k->sel, un * sizeof(int64_t)},
+                   {&k->slots, un * sizeof(int64_t)},
+                   {&k->scores, un * sizeof(double)},
+                   {&k->mean, (size_t)d * sizeof(double)},
+                   {&k->mean_part, mean_segments((int)m_max) > 1
+                                       ? (size_t)mean_segments((int)m_max) * (size_t)d * sizeof(double)
+                                       : 0},
+                   {&k->order, un * sizeof(int64_t)},
+                   {&k->horder, un * sizeof(int64_t)},
+                   {&k->ring, RING_SLOT_BYTES * RING_SLOTS}}));
+    // the rows' pad columns [d, ld) are read by k_border's 16-B loads: zero
+    if (ld > d) {
+        const hipError_t e =
+            hipMemset2DAsync((char *)k->store.p + (size_t)d * es, (size_t)ld * es, 0,
+                             (size_t)(ld - d) * es, un, st);
+        if (e != hipSuccess) {
+            k->begun = false;  // the buffers were replaced: no collection
+            k->count = 0;
+            return api_fail(BK_EHIP, "bk_collect_begin: hipMemset2DAsync: %s", hipGetErrorString(e));
+        }
+    }
+    k->begun = true;
+    k->dtype = dtype;
+    k->n_cap = n_cap;
+    k->d = d;
+    k->ld = ld;
+    k->S = S;
+    k->count = 0;
+    return BK_OK;
+}
+
+int bk_collect_add(bk_ctx *c, const void *const *rows, int64_t count, int where,
+                   int64_t *first_slot) {
+    if (!c) return api_fail(BK_EINVAL, "null context");
+    if (!rows) return api_fail(BK_EINVAL, "null rows");
+    if (count < 1) return api_fail(BK_EINVAL, "need count >= 1 (count=%lld)", (long long)count);
+    if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
+        return api_fail(BK_EINVAL, "bad where %d", where);
+    const CtxRef r = ctx_ref(c);
+    std::lock_guard<std::mutex> lk(*r.mu);
+    Collect *k = *r.collect;
+    if (!k || !k->begun) return api_fail(BK_EINVAL, "bk_collect_add without bk_collect_begin");
+    if (count > k->n_cap - k->count)
+        return api_fail(BK_EINVAL, "bk_collect_add: %lld rows past n_cap=%lld (%lld collected)",
+                        (long long)count, (long long)k->n_cap, (long long)k->count);
+    for (int64_t i = 0; i < count; ++i)
+        if (!rows[i]) return api_fail(BK_EINVAL, "null row %lld", (long long)i);
+    DevGuard dg(r.device);
+    const hipStream_t st = *r.stream;
+    Drain drain{st};
+    const size_t es = esz(k->dtype), bytes = (size_t)k->d * es;
+    const int64_t j0 = k->count;
+    for (int64_t i = 0; i < count; ++i) {
+        char *dst = (char *)k->store.p + (size_t)(j0 + i) * (size_t)k->ld * es;
+        if (where == BK_HOST)
+            CCHK(upload_pageable(k, dst, (const char *)rows[i], bytes, st));
+        else
+            CHIP(hipMemcpyAsync(dst, rows[i], bytes,
+                                where == BK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                st));
+    }
+    if (where != BK_HOST) CHIP(hipEventRecord(k->ev_up, st));
+    CCHK(fold_border(k, j0, count, r.num_cu, st));
+    // pinned and device rows are read by the copies themselves: consumed once
+    // those are done (the border runs on)
+    if (where != BK_HOST) CHIP(hipEventSynchronize(k->ev_up));
+    drain.armed = false;
+    k->count = j0 + count;
+    if (first_slot) *first_slot = j0;
+    return BK_OK;
+}
+
+int bk_collect_count(bk_ctx *c, int64_t *count) {
+    if (!c) return api_fail(BK_EINVAL, "null context");
+    if (!count) return api_fail(BK_EINVAL, "null count");
+    const CtxRef r = ctx_ref(c);
+    std::lock_guard<std::mutex> lk(*r.mu);
+    const Collect *k = *r.collect;
+    *count = k && k->begun ? k->count : 0;
+    return BK_OK;
+}
+
+int bk_collect_finish(bk_ctx *c, const int64_t *order, int64_t n, int64_t f, int64_t *sel_idx,
+                      int64_t *m_out, double *scores, double *mean_out) {
+    if (!c) return api_fail(BK_EINVAL, "null context");
+    if (!sel_idx) return api_fail(BK_EINVAL, "null sel_idx");
+    const CtxRef r = ctx_ref(c);
+    std::lock_guard<std::mutex> lk(*r.mu);
+    Collect *k = *r.collect;
+    if (!k || !k->begun) return api_fail(BK_EINVAL, "bk_collect_finish without bk_collect_begin");
+    if (n < 1 || n > k->count)
+        return api_fail(BK_EINVAL, "bk_collect_finish: n=%lld, %lld rows collected", (long long)n,
+                        (long long)k->count);
+    if (!order && n != k->count)
+        return api_fail(BK_EINVAL, "bk_collect_finish: a null order needs n = %lld, the rows "
+                                   "collected (n=%lld)",
+                        (long long)k->count, (long long)n);
+    CCHK(bk_check_args(n, k->d, f));
+    int64_t *ho = (int64_t *)k->horder.p;
+    if (order) {
+        std::vector<char> seen((size_t)k->count, 0);
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t o = order[i];
+            if (o < 0 || o >= k->count)
+                return api_fail(BK_EINVAL, "order[%lld] = %lld is no collected slot (0..%lld)",
+                                (long long)i, (long long)o, (long long)k->count - 1);
+            if (seen[(size_t)o])
+                return api_fail(BK_EINVAL, "order[%lld] = %lld repeats a slot", (long long)i,
+                                (long long)o);
+            seen[(size_t)o] = 1;
+        }
+    }
+    DevGuard dg(r.device);
+    const hipStream_t st = *r.stream;
+    Drain drain{st};
+    for (int64_t i = 0; i < n; ++i) ho[i] = order ? order[i] : i;
+    int64_t *dord = (int64_t *)k->order.p, *dsel = (int64_t *)k->sel.p;
+    double *U = (double *)k->U.p, *dsc = (double *)k->scores.p;
+    const int64_t m = n - f;
+    CHIP(hipMemcpyAsync(dord, ho, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    const int T = (int)((n + 63) / 64);
+    hipLaunchKernelGGL(k_collect_gather, dim3((unsigned)(T * (T + 1) / 2)), dim3(256), 0, st,
+                       (const double *)k->G.p, (const int64_t *)dord, (int)n, T, (double)k->d, U);
+    CHIP(hipGetLastError());
+    // K2, K3, K3b and the margin record, unchanged, on the gathered record
+    CCHK(ctx_finish_upper(c, U, n, f, dsel, dsc));
+    double *dmean = nullptr;
+    if (mean_out) {
+        dmean = (double *)k->mean.p;
+        int64_t *slots = (int64_t *)k->slots.p;
+        hipLaunchKernelGGL(k_collect_selmap, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
+                           (const int64_t *)dsel, (const int64_t *)dord, (int)m, slots);
+        CHIP(hipGetLastError());
+        CHIP(launch_mean(k->store.p, k->dtype, k->ld, k->d, slots, (int)m, dmean, r.num_cu, st,
+                         mean_segments((int)m) > 1 ? (double *)k->mean_part.p : nullptr));
+    }
+    CHIP(hipMemcpyAsync(sel_idx, dsel, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (scores)
+        CHIP(hipMemcpyAsync(scores, dsc, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (mean_out)
+        CHIP(hipMemcpyAsync(mean_out, dmean, (size_t)k->d * sizeof(double), hipMemcpyDeviceToHost,
+                            st));
+    CCHK(ctx_wait_finish(c));
+    drain.armed = false;
+    if (m_out) *m_out = m;
+    return BK_OK;
+}
+
+}  // extern "C"

@@ -5,9 +5,12 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <mutex>
 #include <vector>
 
 #include "bk_synth.h"
+
+struct bk_ctx;
 
 namespace bk {
 
@@ -304,5 +307,25 @@ hipError_t launch_small(const void *X, int dtype, int64_t ld, int n, int64_t d, 
                         double *scores_out = nullptr, int g0 = 0, int gn = -1, bool sm = true);
 hipError_t launch_synth(void *X, int dtype, int64_t ld, int64_t n, int64_t dl, int64_t c0,
                         const int64_t *perm, const SynthParams &P, hipStream_t st);
+
+// bk_collect.hip: the incremental collection of a context (bk_collect_*), which
+// owns its buffers; bk_destroy frees it (device selected, streams idle)
+struct Collect;
+void collect_destroy(Collect *k);
+// ... and what it needs of bk_api.hip: the error string, the context's mutex,
+// device, stream and collection slot, the finish (K2, K3, K3b and the margin
+// record) on a packed upper of n rows with its trailing record, and the wait
+// of a synchronous entry (then the record's error codes)
+int api_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+struct CtxRef {
+    std::mutex *mu;
+    int device, num_cu;
+    hipStream_t *stream;  // read under mu (bk_set_stream)
+    Collect **collect;
+};
+CtxRef ctx_ref(bk_ctx *c);
+int ctx_finish_upper(bk_ctx *c, const double *U, int64_t n, int64_t f, int64_t *d_sel,
+                     double *d_scores);
+int ctx_wait_finish(bk_ctx *c);
 
 }  // namespace bk

@@ -11,6 +11,7 @@ Reference surface kept (same names, argument meaning and error behaviour):
     .compute_scores()             krum.go:77-98
     .get_top_krum_index(deltas)   krum.go:100-166 (the go-python call this engine replaces)
     .flush_collected_updates()    krum.go:169-176
+    .add_update(u)                krum.go:291     (the append; collect=True streams it)
   Update                          DistSys/update.go:13-22
 
 Differences a caller can observe, all documented in DESIGN.md:
@@ -200,6 +201,81 @@ class Engine:
 
     def set_host_threads(self, threads):
         check(lib().bk_set_host_threads(self._ctx, int(threads)))
+
+    # ---- incremental Multi-Krum (bk_collect_*): each update is uploaded and
+    #      folded into the Gram when it arrives (VerifyUpdateKRUM's append,
+    #      krum.go:291); the finish is scores, selection and mean only -------
+    def collect_begin(self, n_cap, d, dtype=np.float64):
+        """Start (or restart) the context's collection of up to n_cap rows of d."""
+        dt = np.dtype(dtype)
+        if dt not in (np.float64, np.float32):
+            raise ValueError("dtype must be float64 or float32")
+        check(lib().bk_collect_begin(self._ctx, _lib.BK_F32 if dt == np.float32 else _lib.BK_F64,
+                                     int(n_cap), int(d)))
+        self._collect = (dt, int(d))
+
+    def collect_add(self, rows):
+        """One 1-D array, or a sequence of them (one add: the resident rows are
+        read once for the group): host rows of the collection's dtype and d.
+        Returns the first arrival slot."""
+        if getattr(self, "_collect", None) is None:
+            raise ValueError("collect_add without collect_begin")
+        dt, d = self._collect
+        if isinstance(rows, np.ndarray) and rows.ndim == 1:
+            rows = [rows]
+        keep = []
+        for r in rows:
+            a = np.asarray(r)
+            if a.dtype != dt or a.ndim != 1 or a.shape[0] != d:
+                raise ValueError("every row must be a 1-D %s array of length %d" % (dt, d))
+            keep.append(a if a.flags.c_contiguous else np.ascontiguousarray(a))
+        if not keep:
+            raise ValueError("no rows")
+        ptrs = (ctypes.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
+        return self.collect_add_ptr(ptrs, len(keep), _lib.BK_HOST)
+
+    def collect_add_ptr(self, row_ptrs, count, where):
+        """Raw row pointers (a ctypes c_void_p array): pageable, pinned or device."""
+        first = ctypes.c_int64(-1)
+        check(lib().bk_collect_add(self._ctx, row_ptrs, int(count), int(where),
+                                   ctypes.byref(first)))
+        return first.value
+
+    def collect_count(self):
+        cnt = ctypes.c_int64(0)
+        check(lib().bk_collect_count(self._ctx, ctypes.byref(cnt)))
+        return cnt.value
+
+    def collect_finish(self, order=None, n=None, f=None, want_scores=True, want_mean=True):
+        """Multi-Krum over the collected rows: order[i] = arrival slot of the
+        caller's row i (None: every row, in arrival order).  Returns (sel,
+        scores, mean) as multikrum, indices into the caller's rows."""
+        if getattr(self, "_collect", None) is None:
+            raise ValueError("collect_finish without collect_begin")
+        if f is None:
+            raise ValueError("f is required")
+        _, d = self._collect
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.int64)
+            if n is None:
+                n = len(order)
+            if order.ndim != 1 or len(order) < n:
+                raise ValueError("order must list n arrival slots")
+        elif n is None:
+            n = self.collect_count()
+        n, f = int(n), int(f)
+        check(lib().bk_check_args(n, d, f))
+        m = n - f
+        sel = np.empty(m, dtype=np.int64)
+        mo = ctypes.c_int64(0)
+        sc = np.empty(n, dtype=np.float64) if want_scores else None
+        mean = np.empty(d, dtype=np.float64) if want_mean else None
+        check(lib().bk_collect_finish(self._ctx, order.ctypes.data if order is not None else None,
+                                      n, f, sel.ctypes.data, ctypes.addressof(mo),
+                                      sc.ctypes.data if sc is not None else None,
+                                      mean.ctypes.data if mean is not None else None))
+        assert mo.value == m
+        return sel, sc, mean
 
     # ---- host entry with the noise applied in the H2D staging -----------
     #      (bk_multikrum_noised, SURVEY.md §8(f) row 3) -------------------
@@ -483,12 +559,20 @@ class Update:
 class KRUMValidator:
     """DistSys/krum.go:22-29, with getTopKRUMIndex running on libbk."""
 
-    def __init__(self, num_adversaries=0.5, engine: Optional[Engine] = None, device=0):
+    def __init__(self, num_adversaries=0.5, engine: Optional[Engine] = None, device=0,
+                 collect=False, n_cap=128):
+        """collect=True (opt-in): add_update streams each update's NoisedDelta
+        to the engine's collection as it arrives (bk_collect_add), and
+        compute_scores only finishes (bk_collect_finish) in SourceID order;
+        n_cap bounds the updates of one round (KRUM_UPDATETHRESH)."""
         self.UpdateList: List[Update] = []
         self.AcceptedList: List[int] = []
         self.NumAdversaries = num_adversaries  # fixed at 0.5 (main.go:783)
         self._engine = engine
         self._device = device
+        self._collect = bool(collect)
+        self._n_cap = int(n_cap)
+        self._slots: List[int] = []  # collect mode: arrival slot of UpdateList[i]
 
     def initialize(self):
         # krum.go:31-44 bound pyKRUMFunc; here: create the engine context
@@ -501,8 +585,32 @@ class KRUMValidator:
         # global is never set, main.go:843 declares a local)
         return any(self.UpdateList[i].SourceID == peer_id for i in self.AcceptedList)
 
+    def add_update(self, update):
+        """VerifyUpdateKRUM's append (krum.go:291).  In collect mode the update's
+        NoisedDelta is uploaded and folded into the Gram now."""
+        if self._collect:
+            if self._engine is None:
+                self.initialize()
+            row = np.ascontiguousarray(update.NoisedDelta, dtype=np.float64)
+            if not self._slots:
+                self._engine.collect_begin(self._n_cap, row.shape[0], np.float64)
+            self._slots.append(self._engine.collect_add(row))
+        self.UpdateList.append(update)
+
     def compute_scores(self):
         # krum.go:77-98
+        if self._collect:
+            # krum.go:202-210 / 306-314: the updates sorted by SourceID, then Krum;
+            # the finish takes the matching arrival slots as its order
+            by_id = sorted(range(len(self.UpdateList)), key=lambda i: self.UpdateList[i].SourceID)
+            self.UpdateList = [self.UpdateList[i] for i in by_id]
+            self._slots = [self._slots[i] for i in by_id]
+            n = len(self.UpdateList)
+            clip = int(self.NumAdversaries * float(n))
+            sel, _, _ = self._engine.collect_finish(order=self._slots, n=n, f=clip,
+                                                    want_scores=False, want_mean=False)
+            self.AcceptedList = [int(i) for i in sel]
+            return
         running = [u.NoisedDelta for u in self.UpdateList]
         self.AcceptedList = self.get_top_krum_index(running)
 
@@ -523,3 +631,4 @@ class KRUMValidator:
         if not collecting_updates:
             self.UpdateList = []
             self.AcceptedList = []
+            self._slots = []  # collect mode: the next add_update begins again

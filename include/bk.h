@@ -126,6 +126,61 @@ int bk_multikrum_rows(bk_ctx *ctx, const void *const *rows, int dtype, int64_t n
  * calls. */
 int bk_set_host_threads(bk_ctx *ctx, int threads);
 
+/* ---- incremental Multi-Krum: fold each update into the Gram as it arrives ----
+ * VerifyUpdateKRUM (krum.go:227-365) appends one update per RPC and waits
+ * seconds for its peers; only at the threshold or the deadline (krum.go:178-224)
+ * does it sort by SourceID, optionally sample (sampleUpdates, krum.go:368-388)
+ * and call Krum.  A collection takes each update when it arrives: the row is
+ * uploaded into a device row store and its inner products with every row
+ * already there are written into a Gram kept by arrival slot, while the
+ * verifier waits for the next peer.  After the last arrival only the scores,
+ * the selection and the mean remain.
+ * One collection per context, serialised by the context mutex, on the context
+ * stream.  It owns its buffers (row store, the fp64 Gram -- lower-triangular
+ * packed, n_cap (n_cap + 1) / 2 doubles, 1 GiB at BK_MAX_N -- and a small
+ * pinned ring for pageable rows): any other call on the context between two
+ * adds, bk_multikrum* included, leaves it intact.
+ * Arithmetic: every Gram element is an fp64 FMA sum of the products (fp32 rows
+ * widened per element, so exact products, as BK_F32_EXACT) in an order that
+ * depends on (d, dtype) alone -- not on how the rows were grouped into adds nor
+ * on how many were resident -- without atomics: the same sequence of calls
+ * gives the same bits.  bk_set_f32_mode / bk_set_f64_mode do not apply to
+ * collections (no fp32-MFMA, no int8 Gram).  Against bk_multikrum on the same
+ * rows in the finish's order: the selection (wherever bk_selection_margin
+ * reports no near tie) and the mean are BITWISE equal; the scores agree within
+ * rounding (1e-9 of the largest finite score; another summation order of the
+ * Gram), with the same NaN / inf pattern.
+ * Errors are BK_EINVAL (a null ctx, rows, row or required output; add or
+ * finish without begin; add past n_cap; n_cap > BK_MAX_N; an out-of-range or
+ * repeated slot in order; n / f outside bk_check_args) or BK_ENOMEM, and leave
+ * the collection as it was before the call. */
+
+/* Start (or restart: flushCollectedUpdates, krum.go:169-176) a collection of up to
+ * n_cap rows of d elements of dtype.  Reuses the buffers of an earlier collection
+ * of the same or smaller footprint. */
+int bk_collect_begin(bk_ctx *ctx, int dtype, int64_t n_cap, int64_t d);
+/* count >= 1 rows arrive: rows[i] points at d elements (where: BK_HOST, any
+ * alignment, pageable; BK_HOST_PINNED; BK_DEVICE).  They take the next `count`
+ * arrival slots; *first_slot (nullable) gets the first.  On return the rows
+ * have been consumed (cgo: no pointer retained): pageable rows sit in the
+ * pinned ring or on the device, pinned and device rows have been copied; the
+ * upload's tail and the Gram border run asynchronously on the context stream.
+ * The resident rows are read once per group of up to 8 new rows. */
+int bk_collect_add(bk_ctx *ctx, const void *const *rows, int64_t count, int where,
+                   int64_t *first_slot);
+/* rows collected since the last begin (0 before any) */
+int bk_collect_count(bk_ctx *ctx, int64_t *count);
+/* Multi-Krum over n of the collected rows: order[i] = arrival slot of the caller's
+ * row i (NULL: slots 0..count-1 in arrival order, n must equal count).  A subset
+ * and any permutation are allowed: the deadline path, sampleUpdates, the sort by
+ * SourceID.  Outputs and contract as bk_multikrum (host pointers, synchronous;
+ * scores and mean_out nullable); indices refer to the caller's rows 0..n-1.
+ * Does not consume the collection: more rows may be added and finish called
+ * again.  bk_selection_margin* then reports this finish's record (d = the
+ * collection's d, u_G = 2^-53). */
+int bk_collect_finish(bk_ctx *ctx, const int64_t *order, int64_t n, int64_t f,
+                      int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out);
+
 /* Device-resident, asynchronous on the context stream.  All pointers are
  * device pointers; d_sel_idx gets m = n-f ascending indices; d_scores (n) and
  * d_mean (d) are nullable.  A failure inside the kernels (k_small's hand-off
