@@ -25,8 +25,7 @@
 #include <new>
 #include <vector>
 
-#include "../../include/bk.h"
-#include "bk_internal.h"
+#include "bk_ctx.h"
 
 using namespace bk;
 
@@ -248,30 +247,6 @@ void collect_destroy(Collect *k) {
 
 namespace {
 
-#define CHIP(expr)                                                                             \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess)                                                                  \
-            return api_fail(_e == hipErrorOutOfMemory ? BK_ENOMEM : BK_EHIP, "%s: %s (%s:%d)", \
-                            #expr, hipGetErrorString(_e), __FILE__, __LINE__);                 \
-    } while (0)
-#define CCHK(expr)                  \
-    do {                            \
-        int _s = (expr);            \
-        if (_s != BK_OK) return _s; \
-    } while (0)
-
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        (void)hipSetDevice(dev);
-    }
-    ~DevGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 // an error path of add / finish: queued copies may still read the caller's rows
 struct Drain {
     hipStream_t st;
@@ -280,8 +255,6 @@ struct Drain {
         if (armed) (void)hipStreamSynchronize(st);
     }
 };
-
-size_t esz(int dtype) { return dtype == BK_F64 ? 8 : 4; }
 
 // Grow the buffers in `want` to their sizes, all or nothing: the new blocks are
 // allocated first, and only when every one exists are the old ones freed
@@ -296,8 +269,8 @@ int grow_all(const std::vector<std::pair<Buf *, size_t>> &want) {
         if (e != hipSuccess) {
             for (size_t q = 0; q < i; ++q)
                 if (fresh[q]) (void)(want[q].first->pinned ? hipHostFree(fresh[q]) : hipFree(fresh[q]));
-            return api_fail(BK_ENOMEM, "bk_collect_begin: %s(%zu bytes): %s",
-                            b->pinned ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
+            return fail(BK_ENOMEM, "bk_collect_begin: %s(%zu bytes): %s",
+                        b->pinned ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
         }
     }
     for (size_t i = 0; i < want.size(); ++i) {
@@ -328,14 +301,14 @@ int fold_border(Collect *k, int64_t j0, int64_t cnt, int num_cu, hipStream_t st)
                                              k->S, rpb, RB, (double *)k->P.p, st)
                            : launch_border_t((const float *)k->store.p, k->ld, k->d, (int)g0, gc,
                                              k->S, rpb, RB, (double *)k->P.p, st);
-        if (e != hipSuccess) return api_fail(BK_EHIP, "k_border launch: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(BK_EHIP, "k_border launch: %s", hipGetErrorString(e));
         const int64_t items = (int64_t)gc * jend;
         hipLaunchKernelGGL(k_border_reduce, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st,
                            (const double *)k->P.p, k->S, border_c(gc), (int)g0, jend,
                            (double *)k->G.p);
         e = hipGetLastError();
         if (e != hipSuccess)
-            return api_fail(BK_EHIP, "k_border_reduce launch: %s", hipGetErrorString(e));
+            return fail(BK_EHIP, "k_border_reduce launch: %s", hipGetErrorString(e));
     }
     return BK_OK;
 }
@@ -347,11 +320,11 @@ int upload_pageable(Collect *k, char *dst, const char *src, size_t bytes, hipStr
         const size_t len = bytes - off < RING_SLOT_BYTES ? bytes - off : RING_SLOT_BYTES;
         const int s = k->ring_next;
         k->ring_next = (s + 1) % RING_SLOTS;
-        if (k->slot_used[s]) CHIP(hipEventSynchronize(k->ev_slot[s]));
+        if (k->slot_used[s]) HIPCHK(hipEventSynchronize(k->ev_slot[s]));
         char *slot = (char *)k->ring.p + (size_t)s * RING_SLOT_BYTES;
         memcpy(slot, src + off, len);
-        CHIP(hipMemcpyAsync(dst + off, slot, len, hipMemcpyHostToDevice, st));
-        CHIP(hipEventRecord(k->ev_slot[s], st));
+        HIPCHK(hipMemcpyAsync(dst + off, slot, len, hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(k->ev_slot[s], st));
         k->slot_used[s] = true;
     }
     return BK_OK;
@@ -362,53 +335,52 @@ int upload_pageable(Collect *k, char *dst, const char *src, size_t bytes, hipStr
 extern "C" {
 
 int bk_collect_begin(bk_ctx *c, int dtype, int64_t n_cap, int64_t d) {
-    if (!c) return api_fail(BK_EINVAL, "null context");
-    if (dtype != BK_F64 && dtype != BK_F32) return api_fail(BK_EINVAL, "bad dtype %d", dtype);
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (dtype != BK_F64 && dtype != BK_F32) return fail(BK_EINVAL, "bad dtype %d", dtype);
     if (n_cap < 1 || d < 1)
-        return api_fail(BK_EINVAL, "need n_cap >= 1 and d >= 1 (n_cap=%lld d=%lld)",
-                        (long long)n_cap, (long long)d);
+        return fail(BK_EINVAL, "need n_cap >= 1 and d >= 1 (n_cap=%lld d=%lld)", (long long)n_cap,
+                    (long long)d);
     if (n_cap > BK_MAX_N)
-        return api_fail(BK_EINVAL, "n_cap=%lld exceeds BK_MAX_N=%d", (long long)n_cap, BK_MAX_N);
-    const CtxRef r = ctx_ref(c);
-    std::lock_guard<std::mutex> lk(*r.mu);
-    DevGuard dg(r.device);
-    const hipStream_t st = *r.stream;
-    Collect *k = *r.collect;
+        return fail(BK_EINVAL, "n_cap=%lld exceeds BK_MAX_N=%d", (long long)n_cap, BK_MAX_N);
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    const hipStream_t st = c->stream;
+    Collect *k = c->collect;
     if (!k) {
         k = new (std::nothrow) Collect();
-        if (!k) return api_fail(BK_ENOMEM, "host allocation of the collection failed");
+        if (!k) return fail(BK_ENOMEM, "host allocation of the collection failed");
         k->horder.pinned = k->ring.pinned = true;
         hipError_t e = hipEventCreateWithFlags(&k->ev_up, hipEventDisableTiming);
         for (int s = 0; s < RING_SLOTS && e == hipSuccess; ++s)
             e = hipEventCreateWithFlags(&k->ev_slot[s], hipEventDisableTiming);
         if (e != hipSuccess) {
             collect_destroy(k);
-            return api_fail(BK_EHIP, "bk_collect_begin: events: %s", hipGetErrorString(e));
+            return fail(BK_EHIP, "bk_collect_begin: events: %s", hipGetErrorString(e));
         }
-        *r.collect = k;
+        c->collect = k;
     }
-    const size_t es = esz(dtype);
+    const size_t es = esize(dtype);
     const int64_t per16 = 16 / (int64_t)es;
     const int64_t ld = (d + per16 - 1) / per16 * per16;
     const int S = (int)(((size_t)d * es + BORDER_CHUNK_BYTES - 1) / BORDER_CHUNK_BYTES);
     const int64_t m_max = n_cap;
     const size_t un = (size_t)n_cap;
     // work of the old collection may still read the buffers about to be replaced
-    CHIP(hipStreamSynchronize(st));
-    CCHK(grow_all({{&k->store, un * (size_t)ld * es},
-                   {&k->G, un * (un + 1) / 2 * sizeof(double)},
-                   {&k->P, (size_t)S * BORDER_ROWS * un * sizeof(double)},
-                   {&k->U, (size_t)bk_upper_elems(n_cap) * sizeof(double)},
-                   {&k->sel, un * sizeof(int64_t)},
-                   {&k->slots, un * sizeof(int64_t)},
-                   {&k->scores, un * sizeof(double)},
-                   {&k->mean, (size_t)d * sizeof(double)},
-                   {&k->mean_part, mean_segments((int)m_max) > 1
-                                       ? (size_t)mean_segments((int)m_max) * (size_t)d * sizeof(double)
-                                       : 0},
-                   {&k->order, un * sizeof(int64_t)},
-                   {&k->horder, un * sizeof(int64_t)},
-                   {&k->ring, RING_SLOT_BYTES * RING_SLOTS}}));
+    HIPCHK(hipStreamSynchronize(st));
+    CHK(grow_all({{&k->store, un * (size_t)ld * es},
+                  {&k->G, un * (un + 1) / 2 * sizeof(double)},
+                  {&k->P, (size_t)S * BORDER_ROWS * un * sizeof(double)},
+                  {&k->U, (size_t)bk_upper_elems(n_cap) * sizeof(double)},
+                  {&k->sel, un * sizeof(int64_t)},
+                  {&k->slots, un * sizeof(int64_t)},
+                  {&k->scores, un * sizeof(double)},
+                  {&k->mean, (size_t)d * sizeof(double)},
+                  {&k->mean_part, mean_segments((int)m_max) > 1
+                                      ? (size_t)mean_segments((int)m_max) * (size_t)d * sizeof(double)
+                                      : 0},
+                  {&k->order, un * sizeof(int64_t)},
+                  {&k->horder, un * sizeof(int64_t)},
+                  {&k->ring, RING_SLOT_BYTES * RING_SLOTS}}));
     // the rows' pad columns [d, ld) are read by k_border's 16-B loads: zero
     if (ld > d) {
         const hipError_t e =
@@ -417,7 +389,7 @@ int bk_collect_begin(bk_ctx *c, int dtype, int64_t n_cap, int64_t d) {
         if (e != hipSuccess) {
             k->begun = false;  // the buffers were replaced: no collection
             k->count = 0;
-            return api_fail(BK_EHIP, "bk_collect_begin: hipMemset2DAsync: %s", hipGetErrorString(e));
+            return fail(BK_EHIP, "bk_collect_begin: hipMemset2DAsync: %s", hipGetErrorString(e));
         }
     }
     k->begun = true;
@@ -432,39 +404,38 @@ int bk_collect_begin(bk_ctx *c, int dtype, int64_t n_cap, int64_t d) {
 
 int bk_collect_add(bk_ctx *c, const void *const *rows, int64_t count, int where,
                    int64_t *first_slot) {
-    if (!c) return api_fail(BK_EINVAL, "null context");
-    if (!rows) return api_fail(BK_EINVAL, "null rows");
-    if (count < 1) return api_fail(BK_EINVAL, "need count >= 1 (count=%lld)", (long long)count);
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!rows) return fail(BK_EINVAL, "null rows");
+    if (count < 1) return fail(BK_EINVAL, "need count >= 1 (count=%lld)", (long long)count);
     if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
-        return api_fail(BK_EINVAL, "bad where %d", where);
-    const CtxRef r = ctx_ref(c);
-    std::lock_guard<std::mutex> lk(*r.mu);
-    Collect *k = *r.collect;
-    if (!k || !k->begun) return api_fail(BK_EINVAL, "bk_collect_add without bk_collect_begin");
+        return fail(BK_EINVAL, "bad where %d", where);
+    std::lock_guard<std::mutex> lk(c->mu);
+    Collect *k = c->collect;
+    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_add without bk_collect_begin");
     if (count > k->n_cap - k->count)
-        return api_fail(BK_EINVAL, "bk_collect_add: %lld rows past n_cap=%lld (%lld collected)",
-                        (long long)count, (long long)k->n_cap, (long long)k->count);
+        return fail(BK_EINVAL, "bk_collect_add: %lld rows past n_cap=%lld (%lld collected)",
+                    (long long)count, (long long)k->n_cap, (long long)k->count);
     for (int64_t i = 0; i < count; ++i)
-        if (!rows[i]) return api_fail(BK_EINVAL, "null row %lld", (long long)i);
-    DevGuard dg(r.device);
-    const hipStream_t st = *r.stream;
+        if (!rows[i]) return fail(BK_EINVAL, "null row %lld", (long long)i);
+    DeviceGuard dg(c->device);
+    const hipStream_t st = c->stream;
     Drain drain{st};
-    const size_t es = esz(k->dtype), bytes = (size_t)k->d * es;
+    const size_t es = esize(k->dtype), bytes = (size_t)k->d * es;
     const int64_t j0 = k->count;
     for (int64_t i = 0; i < count; ++i) {
         char *dst = (char *)k->store.p + (size_t)(j0 + i) * (size_t)k->ld * es;
         if (where == BK_HOST)
-            CCHK(upload_pageable(k, dst, (const char *)rows[i], bytes, st));
+            CHK(upload_pageable(k, dst, (const char *)rows[i], bytes, st));
         else
-            CHIP(hipMemcpyAsync(dst, rows[i], bytes,
-                                where == BK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                st));
+            HIPCHK(hipMemcpyAsync(dst, rows[i], bytes,
+                                  where == BK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                  st));
     }
-    if (where != BK_HOST) CHIP(hipEventRecord(k->ev_up, st));
-    CCHK(fold_border(k, j0, count, r.num_cu, st));
+    if (where != BK_HOST) HIPCHK(hipEventRecord(k->ev_up, st));
+    CHK(fold_border(k, j0, count, c->num_cu, st));
     // pinned and device rows are read by the copies themselves: consumed once
     // those are done (the border runs on)
-    if (where != BK_HOST) CHIP(hipEventSynchronize(k->ev_up));
+    if (where != BK_HOST) HIPCHK(hipEventSynchronize(k->ev_up));
     drain.armed = false;
     k->count = j0 + count;
     if (first_slot) *first_slot = j0;
@@ -472,76 +443,79 @@ int bk_collect_add(bk_ctx *c, const void *const *rows, int64_t count, int where,
 }
 
 int bk_collect_count(bk_ctx *c, int64_t *count) {
-    if (!c) return api_fail(BK_EINVAL, "null context");
-    if (!count) return api_fail(BK_EINVAL, "null count");
-    const CtxRef r = ctx_ref(c);
-    std::lock_guard<std::mutex> lk(*r.mu);
-    const Collect *k = *r.collect;
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!count) return fail(BK_EINVAL, "null count");
+    std::lock_guard<std::mutex> lk(c->mu);
+    const Collect *k = c->collect;
     *count = k && k->begun ? k->count : 0;
     return BK_OK;
 }
 
 int bk_collect_finish(bk_ctx *c, const int64_t *order, int64_t n, int64_t f, int64_t *sel_idx,
                       int64_t *m_out, double *scores, double *mean_out) {
-    if (!c) return api_fail(BK_EINVAL, "null context");
-    if (!sel_idx) return api_fail(BK_EINVAL, "null sel_idx");
-    const CtxRef r = ctx_ref(c);
-    std::lock_guard<std::mutex> lk(*r.mu);
-    Collect *k = *r.collect;
-    if (!k || !k->begun) return api_fail(BK_EINVAL, "bk_collect_finish without bk_collect_begin");
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!sel_idx) return fail(BK_EINVAL, "null sel_idx");
+    std::lock_guard<std::mutex> lk(c->mu);
+    Collect *k = c->collect;
+    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_finish without bk_collect_begin");
     if (n < 1 || n > k->count)
-        return api_fail(BK_EINVAL, "bk_collect_finish: n=%lld, %lld rows collected", (long long)n,
-                        (long long)k->count);
+        return fail(BK_EINVAL, "bk_collect_finish: n=%lld, %lld rows collected", (long long)n,
+                    (long long)k->count);
     if (!order && n != k->count)
-        return api_fail(BK_EINVAL, "bk_collect_finish: a null order needs n = %lld, the rows "
-                                   "collected (n=%lld)",
-                        (long long)k->count, (long long)n);
-    CCHK(bk_check_args(n, k->d, f));
+        return fail(BK_EINVAL, "bk_collect_finish: a null order needs n = %lld, the rows "
+                               "collected (n=%lld)",
+                    (long long)k->count, (long long)n);
+    CHK(bk_check_args(n, k->d, f));
     int64_t *ho = (int64_t *)k->horder.p;
     if (order) {
         std::vector<char> seen((size_t)k->count, 0);
         for (int64_t i = 0; i < n; ++i) {
             const int64_t o = order[i];
             if (o < 0 || o >= k->count)
-                return api_fail(BK_EINVAL, "order[%lld] = %lld is no collected slot (0..%lld)",
-                                (long long)i, (long long)o, (long long)k->count - 1);
+                return fail(BK_EINVAL, "order[%lld] = %lld is no collected slot (0..%lld)",
+                            (long long)i, (long long)o, (long long)k->count - 1);
             if (seen[(size_t)o])
-                return api_fail(BK_EINVAL, "order[%lld] = %lld repeats a slot", (long long)i,
-                                (long long)o);
+                return fail(BK_EINVAL, "order[%lld] = %lld repeats a slot", (long long)i,
+                            (long long)o);
             seen[(size_t)o] = 1;
         }
     }
-    DevGuard dg(r.device);
-    const hipStream_t st = *r.stream;
+    DeviceGuard dg(c->device);
+    const hipStream_t st = c->stream;
     Drain drain{st};
     for (int64_t i = 0; i < n; ++i) ho[i] = order ? order[i] : i;
     int64_t *dord = (int64_t *)k->order.p, *dsel = (int64_t *)k->sel.p;
     double *U = (double *)k->U.p, *dsc = (double *)k->scores.p;
     const int64_t m = n - f;
-    CHIP(hipMemcpyAsync(dord, ho, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dord, ho, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
     const int T = (int)((n + 63) / 64);
     hipLaunchKernelGGL(k_collect_gather, dim3((unsigned)(T * (T + 1) / 2)), dim3(256), 0, st,
                        (const double *)k->G.p, (const int64_t *)dord, (int)n, T, (double)k->d, U);
-    CHIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     // K2, K3, K3b and the margin record, unchanged, on the gathered record
-    CCHK(ctx_finish_upper(c, U, n, f, dsel, dsc));
+    Plan pl;
+    pl.n = (int)n;
+    pl.T = (int)((n + 63) / 64);
+    pl.ntile = pl.T * (pl.T + 1) / 2;
+    CHK(stage_finish(c, U, pl, nullptr, BK_F64, n, 0, 0, f, dsel, dsc, nullptr));
     double *dmean = nullptr;
     if (mean_out) {
         dmean = (double *)k->mean.p;
         int64_t *slots = (int64_t *)k->slots.p;
         hipLaunchKernelGGL(k_collect_selmap, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st,
                            (const int64_t *)dsel, (const int64_t *)dord, (int)m, slots);
-        CHIP(hipGetLastError());
-        CHIP(launch_mean(k->store.p, k->dtype, k->ld, k->d, slots, (int)m, dmean, r.num_cu, st,
-                         mean_segments((int)m) > 1 ? (double *)k->mean_part.p : nullptr));
+        HIPCHK(hipGetLastError());
+        HIPCHK(launch_mean(k->store.p, k->dtype, k->ld, k->d, slots, (int)m, dmean, c->num_cu, st,
+                           mean_segments((int)m) > 1 ? (double *)k->mean_part.p : nullptr));
     }
-    CHIP(hipMemcpyAsync(sel_idx, dsel, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(sel_idx, dsel, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     if (scores)
-        CHIP(hipMemcpyAsync(scores, dsc, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(scores, dsc, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (mean_out)
-        CHIP(hipMemcpyAsync(mean_out, dmean, (size_t)k->d * sizeof(double), hipMemcpyDeviceToHost,
-                            st));
-    CCHK(ctx_wait_finish(c));
+        HIPCHK(hipMemcpyAsync(mean_out, dmean, (size_t)k->d * sizeof(double), hipMemcpyDeviceToHost,
+                              st));
+    HIPCHK(wait_stream(c));
+    CHK(check_margin_readback(c));
     drain.armed = false;
     if (m_out) *m_out = m;
     return BK_OK;

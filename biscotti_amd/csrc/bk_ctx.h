@@ -1,0 +1,377 @@
+// bk_ctx.h -- the context behind the C ABI (struct bk_ctx) and what its entry
+// families share: the error string, the status macros, the staging of K1..K4
+// and the guards.  Private to the files that implement include/bk.h (bk_api,
+// bk_stage, bk_host, bk_comm, bk_group, bk_entries and the host half of
+// bk_collect); the kernels see bk_internal.h only.  Not installed.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <array>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/bk.h"
+#include "bk_internal.h"
+
+namespace bk {
+
+class HostPool;  // bk_hostpool.h
+
+// bk_last_error()'s text, per thread (bk_api.hip)
+extern thread_local std::string g_err;
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+#define HIPCHK(expr)                                                                      \
+    do {                                                                                  \
+        hipError_t _e = (expr);                                                           \
+        if (_e != hipSuccess)                                                             \
+            return fail(_e == hipErrorOutOfMemory ? BK_ENOMEM : BK_EHIP, "%s: %s (%s:%d)", \
+                        #expr, hipGetErrorString(_e), __FILE__, __LINE__);                \
+    } while (0)
+
+#define RCCLCHK(expr)                                                                        \
+    do {                                                                                     \
+        ncclResult_t _r = (expr);                                                            \
+        if (_r != ncclSuccess)                                                               \
+            return fail(BK_ERCCL, "%s: %s (%s:%d)", #expr, ncclGetErrorString(_r), __FILE__, \
+                        __LINE__);                                                           \
+    } while (0)
+
+#define CHK(expr)              \
+    do {                       \
+        int _s = (expr);       \
+        if (_s != BK_OK) return _s; \
+    } while (0)
+
+extern const char *kKernelNames[BK_NUM_KERNELS];
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    uint64_t *epoch = nullptr;  // the owning context's ws_epoch (graph invalidation)
+};
+
+// A K1 plan's (or K1i8 layout's) split into k launches whose sub-tiles are
+// contiguous pieces of the packed upper, for the exchange overlapped with
+// the Gram (bk_comm_set_mode 2): piece p's elements are U[e[p], e[p + 1]),
+// the last piece's range ending with the trailing record
+struct Pieces {
+    int k = 0;                // pieces built for (0: none yet)
+    bool ok = false;          // false: the plan has no k-piece split
+    std::vector<int64_t> e;   // k + 1 element bounds of U
+    std::vector<int> nwg;     // per piece: launched workgroups (K1 v3) / items (K1i8)
+    std::vector<size_t> off;  // per piece: its table's offset in d (ints)
+    int *d = nullptr;         // device copy of the tables, concatenated
+};
+
+inline void free_pieces(Pieces &pc) {
+    if (pc.d) (void)hipFree(pc.d);
+    pc = Pieces();
+}
+
+}  // namespace bk
+
+// the C ABI's opaque handle, hence at global scope; its field types are bk::'s
+using namespace bk;
+
+struct bk_ctx {
+    int device = 0;
+    int num_cu = 256;
+    hipStream_t own = nullptr;
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+    // workspace (grow-only)
+    DevBuf part, U, Ug, scores, mask, sel, X, mean, perm, trace, idx;
+    // the selection margin of the last finish (K2 diag, K3 boundary scores, K3b record)
+    DevBuf diag, bnd;
+    DevBuf Ut;  // K2 at large n: transposed off-diagonal tiles + diagonal (k_transpose)
+    // k_small (n <= 128, one launch): its queue counters (zeroed once; every
+    // launch leaves them zero) and the split-K partials
+    DevBuf small_ctr, small_part;
+    DevBuf mean_part;  // K4 of a large selection: per-segment column sums (launch_mean)
+    int small_on = 1;
+    uint64_t small_spin_max = SMALL_SPIN_MAX;  // test knob BK_SMALL_SPIN_MAX=<polls>[,<launches>]
+    int64_t small_spin_left = -1;              // ... for this many launches (-1: all)
+    int small_check_lines = 0;                 // debug knob BK_SMALL_CHECK_LINES (bk_create)
+    int margin_valid = 0;
+    // a finish ran since its record's error codes were last read (bk_synchronize
+    // reads them: an asynchronous caller learns of an invalid call there)
+    int margin_unchecked = 0;
+    int64_t spin_us = 2000;  // wait_stream: poll this long before blocking (BK_SPIN_US)
+    // the record of the last finish, written by the kernels straight into mapped
+    // pinned memory (GPU-cached, written back at the kernel's end): the host
+    // reads it after the stream has finished, with no device-to-host copy
+    double *hmargin = nullptr;
+    double *dmargin = nullptr;  // its device address
+    // pinned: the n <= 128 host entries' outputs {margin, sel, scores, mean},
+    // read back in one copy (a D2H into pageable memory goes through HIP's
+    // staging: ~20 us per copy at config B)
+    void *hout = nullptr;  // the host small path's mapped output block (pinned)
+    size_t hout_bytes = 0;
+    double *hout_dev = nullptr;          // its device address
+    const double *hout_host_margin = nullptr;  // its record, as the host reads it
+    const double *margin_host = nullptr;  // non-null: the last call's record is there
+    // BK_F32_CERTIFIED: 1 while the exact re-run of a near-tie call is in progress
+    int force_exact = 0;
+    int64_t certified_reruns = 0;
+    // RONI: the validation set (bk_roni_set_validation) and per-call scratch
+    DevBuf roni_X, roni_y, roni_w, roni_d, roni_cnt, roni_s;
+    int64_t roni_nv = 0, roni_dim = 0;
+    // the torch-path (softmax) RONI: its validation set (fp32 samples, int32
+    // labels; bk_roni_softmax_set_validation) and the prepared models
+    DevBuf rmc_X, rmc_y, rmc_ws, rmc_xn, rmc_idx, rmc_nt;
+    int64_t rmc_nv = 0, rmc_din = 0, rmc_C = 0;
+    // bk_multikrum_noised: a 2-slot ring of noise chunks, filled on a copy
+    // stream while K6 consumes the previous chunk on `stream` (created lazily)
+    DevBuf noise;
+    hipStream_t copy = nullptr;
+    hipEvent_t ev_go = nullptr, ev_cp[2] = {nullptr, nullptr}, ev_use[2] = {nullptr, nullptr};
+    // host-side pinned allocations handed out by bk_stage_alloc
+    std::vector<void *> staged;
+    // bk_multikrum_rows: worker threads packing the caller's separate host rows
+    // into a pinned ring (both created on first use), and the ring slots'
+    // copy-done events
+    bk::HostPool *hpool = nullptr;
+    int hthreads = 0;  // packing threads incl. the caller (bk_set_host_threads; 0: default)
+    void *rstage = nullptr;
+    size_t rstage_bytes = 0;
+    hipEvent_t ev_rows[4] = {nullptr, nullptr, nullptr, nullptr};
+    // timing
+    uint32_t timing = 0;  // bit k: record HIP events around kernel k (bk_timing_select)
+    int tstride = 1;      // ... on every tstride-th launch of it (bk_timing_stride)
+    int64_t tseq[BK_NUM_KERNELS] = {0};
+    struct Ev {
+        int kid;
+        hipEvent_t a, b;
+    };
+    std::vector<Ev> pending;
+    std::vector<hipEvent_t> pool;
+    double tot_ms[BK_NUM_KERNELS] = {0};
+    int64_t cnt[BK_NUM_KERNELS] = {0};
+    // K1 v3 plans (device tables), cached per (n, d)
+    struct CachedPlan {
+        int n;
+        int64_t d;
+        int bk;  // columns per k-block (16 fp64, 32 fp32)
+        Plan3 p;
+        Pieces pc;
+    };
+    std::vector<CachedPlan> plans;
+    // K1i8 (BK_F32_I8): layouts and device tables per (n, d), and the workspace
+    struct I8Cached {
+        int64_t n = 0, d = 0;
+        I8Layout L;
+        void *tables = nullptr;
+        Pieces pc;
+    };
+    std::vector<I8Cached> i8;
+    DevBuf i8ws;
+    // K1i8 signatures {n, d, element size, digits} whose workspace failed to
+    // allocate: they run exact until the mode is set again (bk_set_f*_mode)
+    std::vector<std::array<int64_t, 4>> i8_failed;
+    int gram_variant = 3;  // 3: LDS-shared v3 for aligned fp64; 1: v1 everywhere (BK_GRAM=v1)
+    int gram_mode = 0;     // BK_GRAM_MODE: timing-only ablations of v3 (tools/, never tests)
+    int f32_mode = BK_F32_EXACT;  // fp32 rows: widened onto the fp64 MFMA, or the fp32 MFMA
+    int f64_mode = BK_F64_EXACT;  // fp64 rows: the fp64 MFMA, or K1i8 (bk_set_f64_mode)
+    // hipGraph replay of bk_multikrum_device (bk_graph_enable): one captured
+    // launch sequence per call signature; every workspace reallocation or plan
+    // eviction bumps ws_epoch, which retires the graphs that baked the old
+    // pointers in
+    int graph_on = 0;
+    uint64_t ws_epoch = 0;
+    struct CachedGraph {
+        const void *X;
+        int dtype;
+        int64_t n, d, ld, f;
+        const void *sel, *scores, *mean;
+        uint64_t epoch;
+        hipGraph_t g;
+        hipGraphExec_t exec;
+    };
+    std::vector<CachedGraph> graphs;
+    // RCCL
+    ncclComm_t comm = nullptr;
+    int nranks = 1, rank = 0;
+    int deterministic = 0;
+    // the sharded entry's status agreement (sharded_once): the signature of the
+    // last agreed call, and the device word the agreement all-reduces
+    int64_t agreed_n = -1, agreed_f = -1;
+    int agreed_dtype = -1, agreed_det = -1;
+    DevBuf status;
+    int test_fail_exchange = 0;  // test knob BK_TEST_FAIL_BEFORE_EXCHANGE (bk_create)
+    int test_i8_enomem = 0;      // test knob BK_TEST_I8_ENOMEM: K1i8's workspace "fails" (bk_create)
+    int test_fail_piece = 0;     // test knob BK_TEST_FAIL_PIECE=p: the overlapped Gram's piece p-1 fails
+    int test_pieces_disagree = 0;  // test knob BK_TEST_PIECES_DISAGREE=1: act as if a peer cut the pieces differently
+    // the overlapped exchange's piece layout as agreed at the signature's first
+    // call: false when the ranks' layouts differed (every rank then exchanges
+    // whole, serially, for that signature)
+    bool overlap_agreed = true;
+    // split scoring (stage_finish): at n >= split_min_n each rank of a sharded
+    // call scores its share of the rows and the ranks all-gather the scores
+    // (BK_SPLIT_SCORES_MIN_N; 0 turns it off).  Knobs for a 1-rank
+    // communicator (bk_create): BK_TEST_SPLIT_SCORES=R scores in R row chunks,
+    // one launch each, as R ranks would (the arithmetic of the split, tested on
+    // one GPU); BK_EMU_SPLIT_SCORES=R scores only rank 0's chunk once a mode's
+    // first call has scored them all (bench.py --emulate-ranks: one rank's time;
+    // TIMING ONLY -- the other shares keep that first call's scores, so the
+    // outputs and the margin of later calls are not valid, and new data at the
+    // same n is not rescored)
+    int64_t split_min_n = 2049;
+    int test_split_scores = 0, emu_split_scores = 0;
+    int test_split_fail = 0;   // BK_TEST_SPLIT_FAIL=p: under BK_TEST_SPLIT_SCORES, share p - 1 "fails"
+    int64_t emu_split_n = -1;  // emulation: the n whose other chunks are scored
+    DevBuf sgather;            // the gathered scores: parts x chunk doubles
+    DevBuf pcnt;               // the overlapped exchange's per-piece arrival counts
+    // bk_comm_set_mode 2: the exchange overlapped with the Gram in this many
+    // pieces (BK_OVERLAP_PIECES, default 2; 0: off), all-reduced on cstream
+    int overlap = 0;
+    hipStream_t cstream = nullptr;
+    hipEvent_t ev_piece[8] = {};
+    hipEvent_t ev_cdone = nullptr;
+    unsigned *sigcnt[8] = {};       // probe A/B only (BK_PIECES_DEVWAIT): signal memory for hipStreamWaitValue32
+    // the pieces' completion words, polled by the host: fine-grained pinned
+    // host memory, one 64-B line per piece (the Gram's last workgroup of a
+    // piece stores 1 there, system scope)
+    unsigned *hsig = nullptr;       // host address
+    unsigned *hsig_d = nullptr;     // the same words as the device addresses them
+    bool sig_pending = false;       // a launched Gram's piece words not all seen yet
+    int wait_value_ok = -1;         // hipDeviceAttributeCanUseStreamWaitValue (-1: not asked)
+    int64_t exchanges = 0;        // exchanges of the packed Gram (bk_comm_stats)
+    double exchanged_bytes = 0;   // bytes each rank put into them
+    // bk_collect_*: the incremental collection (bk_collect.hip), which owns its
+    // buffers -- none of the workspace above, so batch calls leave it intact
+    bk::Collect *collect = nullptr;
+};
+
+namespace bk {
+
+// Split scoring over the ranks of a sharded call (after the
+// exchange every rank holds the whole Gram, and K2 -- n sorts of n distances,
+// 0.2 ms at n = 4,096 -- was repeated on every rank): rank r scores rows
+// [r ch, r ch + ch), ch = ceil(n / parts), into slice r of a parts x (ch + 1)
+// buffer whose last word is the rank's status (0, or NaN when its share
+// failed), and ONE in-place RCCL all-gather hands every rank all n scores.
+// Each row's score is K2's, bitwise, whichever rank computes it.
+// k_split_unpack then copies the scores to the caller's array and hands K3b
+// the Gram's trailing record, made NaN if any rank's status is not 0 -- so a
+// rank that failed its share marks the call invalid on every rank
+// (MARGIN_POISONED), as a shard that fails before the exchange does.  Only on
+// the transposed K2 path (n >= 2049), whose contiguous diagonal K3b reads
+// instead of the per-row diag K2 writes for its own rows only.
+enum { SPLIT_NONE = 0, SPLIT_RCCL = 1, SPLIT_TEST = 2, SPLIT_EMU = 3 };
+struct ScoreSplit {
+    int mode = SPLIT_NONE;
+    int parts = 1, part = 0;
+};
+
+// bk_api.hip
+int ensure(DevBuf &b, size_t bytes);
+int get_event(bk_ctx *c, hipEvent_t *out);
+bool timing_on(bk_ctx *c, int kid);
+int check_common(bk_ctx *c, const void *X, int dtype, int64_t n, int64_t d, int64_t ld);
+size_t esize(int dtype);
+bool certified(const bk_ctx *c, int dtype);
+// bk_stage.hip
+void free_plan(Plan3 &p);
+int get_plan3(bk_ctx *c, int64_t n, int64_t d, int bk, Plan3 **out);
+int v3_bk(int dtype);
+bool f32_mfma_now(const bk_ctx *c, int dtype);
+bk_ctx::I8Cached *i8_prepared(bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d,
+                              int64_t ld);
+int prepare_gram(bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d, int64_t ld);
+int poison_upper(bk_ctx *c, double *U, int64_t n);
+int stage_gram(bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d, int64_t ld,
+               double *U, Plan &pl);
+int gram_pieces(bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d, int64_t ld, int k,
+                const Pieces **out);
+int prepare_finish(bk_ctx *c, int64_t n, const ScoreSplit &sp, bool own_scores);
+int stage_finish(bk_ctx *c, const double *U, const Plan &pl, const void *dX, int dtype,
+                 int64_t n, int64_t d, int64_t ld, int64_t f, int64_t *d_sel, double *d_scores,
+                 double *d_mean, const ScoreSplit &sp = ScoreSplit());
+bool small_ok(const bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d, int64_t ld);
+int run_small(bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d, int64_t ld, int64_t f,
+              int64_t *d_sel, double *d_scores, double *d_mean, double *margin_out = nullptr,
+              double *scores_out = nullptr, int g0 = 0, int gn = -1, bool sm = true);
+int run_device(bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d, int64_t ld, int64_t f,
+               int64_t *d_sel, double *d_scores, double *d_mean);
+hipError_t wait_stream(bk_ctx *c);
+int margin_status(const double *mg);
+int read_margin(bk_ctx *c, double (&mg)[MARGIN_WORDS]);
+int check_margin_readback(bk_ctx *c);
+// bk_host.hip
+int stage_host_pipelined(bk_ctx *c, const void *X, int64_t ld, int dtype, const double *noise,
+                         int64_t k, int64_t noise_ld, int64_t n, int64_t d, char *dX,
+                         int64_t dld, double *U, Plan &pl);
+
+// Error paths of the host entries: queued H2D copies may still read the
+// caller's buffers, so both streams are drained unless the entry disarms this.
+struct HostDrain {
+    bk_ctx *c;
+    bool armed = true;
+    ~HostDrain() {
+        if (!armed) return;
+        if (c->copy) (void)hipStreamSynchronize(c->copy);
+        (void)hipStreamSynchronize(c->stream);
+    }
+};
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// Bracket one launch with events when timing is on (timing_on).
+template <typename F>
+int timed(bk_ctx *c, int kid, F &&launch) {
+    hipEvent_t a = nullptr, b = nullptr;
+    const bool on = timing_on(c, kid);
+    if (on) {
+        CHK(get_event(c, &a));
+        CHK(get_event(c, &b));
+        HIPCHK(hipEventRecord(a, c->stream));
+    }
+    hipError_t e = launch();
+    if (e != hipSuccess)
+        return fail(BK_EHIP, "%s launch: %s", kKernelNames[kid], hipGetErrorString(e));
+    if (on) {
+        HIPCHK(hipEventRecord(b, c->stream));
+        c->pending.push_back({kid, a, b});
+    }
+    return BK_OK;
+}
+
+// BK_F32_CERTIFIED: run on the fp32 MFMA; if the selection margin does not
+// clear the fp32 error bound, run again on the exact path (fp32 widened onto
+// the fp64 MFMA), whose outputs replace the first run's.  Synchronous (the
+// decision needs the margin on the host).  In the sharded entry every rank
+// holds the same summed Gram, hence the same margin and the same decision, so
+// the re-run's exchange is joined by all ranks.
+template <typename F>
+int run_certified(bk_ctx *c, F &&run) {
+    CHK(run());
+    double mg[MARGIN_WORDS];
+    CHK(read_margin(c, mg));
+    // only a near tie of a call whose Gram ran on the fp32 MFMA (u_G > 2^-53)
+    // is re-run: an exact first pass (k_small, n <= 128) would repeat itself
+    if (mg[2] == 0.0 || !(mg[8] > 0x1p-53)) return BK_OK;
+    // (BK_EMU_SPLIT_SCORES, timing only: the exact re-run's Gram is another
+    // one, so its first call scores every share again, and so does the next
+    // approximate call -- ADVICE r5)
+    c->emu_split_n = -1;
+    c->force_exact = 1;
+    const int st = run();
+    c->force_exact = 0;
+    c->emu_split_n = -1;
+    if (st == BK_OK) ++c->certified_reruns;
+    return st;
+}
+
+}  // namespace bk

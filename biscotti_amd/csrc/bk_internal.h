@@ -1,16 +1,16 @@
-// bk_internal.h -- shared declarations between the C ABI (bk_api.hip) and the
-// kernels (bk_kernels.hip).  Not installed; the public surface is include/bk.h.
+// bk_internal.h -- what the kernel files (bk_kernels, bk_small, bk_i8,
+// bk_aggregate, bk_roni, bk_collect) and the planner (bk_plan) offer the files
+// that implement the C ABI: plans, layouts and launchers.  The context those
+// files share among themselves is bk_ctx.h, which the kernels never see.  Not
+// installed; the public surface is include/bk.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
-#include <mutex>
 #include <vector>
 
 #include "bk_synth.h"
-
-struct bk_ctx;
 
 namespace bk {
 
@@ -312,20 +312,5 @@ hipError_t launch_synth(void *X, int dtype, int64_t ld, int64_t n, int64_t dl, i
 // owns its buffers; bk_destroy frees it (device selected, streams idle)
 struct Collect;
 void collect_destroy(Collect *k);
-// ... and what it needs of bk_api.hip: the error string, the context's mutex,
-// device, stream and collection slot, the finish (K2, K3, K3b and the margin
-// record) on a packed upper of n rows with its trailing record, and the wait
-// of a synchronous entry (then the record's error codes)
-int api_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-struct CtxRef {
-    std::mutex *mu;
-    int device, num_cu;
-    hipStream_t *stream;  // read under mu (bk_set_stream)
-    Collect **collect;
-};
-CtxRef ctx_ref(bk_ctx *c);
-int ctx_finish_upper(bk_ctx *c, const double *U, int64_t n, int64_t f, int64_t *d_sel,
-                     double *d_scores);
-int ctx_wait_finish(bk_ctx *c);
 
 }  // namespace bk
