@@ -14,6 +14,8 @@
 //   k_border_reduce  the chunks' partials summed in a fixed order -> G
 //   k_collect_gather G, through the caller's order -> the packed upper + record
 //   k_collect_selmap the selection mapped to arrival slots, for K4 on the store
+// A finish of n <= 128 rows, d <= 32,768 (small_ok) takes none of the last two
+// nor K2..K4: one k_collect_small launch (bk_small.hip) does it all.
 // Every element of G is the same sum whatever the add's count and however many
 // rows are resident: chunk s covers the same columns, one wave sums a chunk's
 // products in lane order and the chunks are added in the same tree, so the
@@ -330,6 +332,45 @@ int upload_pageable(Collect *k, char *dst, const char *src, size_t bytes, hipStr
     return BK_OK;
 }
 
+// The finish of the deployed shapes (small_ok: n <= 128, d <= 32,768) in one
+// launch: k_collect_small reads the Gram and the row store through the order
+// in its own arguments and writes {margin, sel, scores, mean} into the
+// context's mapped output block, so nothing is uploaded before it and nothing
+// copied after it -- one launch, one wait, then host memcpys.  The arguments
+// are validated by the caller.
+int finish_small(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
+                 int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
+    static_assert(BK_MAX_N <= 65536, "arrival slots travel as 16-bit kernel arguments");
+    const int64_t m = n - f, d = k->d;
+    constexpr size_t MPAD = HOUT_MPAD;
+    CHK(ensure_small_queue(c));
+    CHK(ensure(c->diag, (size_t)n * sizeof(double)));
+    CHK(ensure_hout(c, MPAD + 2 * (size_t)n + (mean_out ? (size_t)d : 0)));
+    double *blk = c->hout_dev;
+    const uint64_t spin = c->small_spin_left == 0 ? SMALL_SPIN_MAX : c->small_spin_max;
+    if (c->small_spin_left > 0) --c->small_spin_left;
+    CHK(timed(c, BK_K_SMALL, [&] {
+        return launch_collect_small(k->store.p, k->dtype, k->ld, (int)n, d, (int)f,
+                                    (const double *)k->G.p, order, (double *)k->scores.p,
+                                    (double *)c->diag.p, (int64_t *)(blk + MPAD),
+                                    mean_out ? blk + MPAD + 2 * n : nullptr, blk,
+                                    scores ? blk + MPAD + n : nullptr, (unsigned *)c->small_ctr.p,
+                                    c->num_cu, c->stream, spin, c->small_check_lines);
+    }));
+    c->margin_valid = 1;
+    c->margin_host = c->hout_host_margin;
+    c->margin_unchecked = 1;
+    HIPCHK(wait_stream(c));
+    const double *h = (const double *)c->hout;
+    c->margin_unchecked = 0;
+    CHK(margin_status(h));
+    memcpy(sel_idx, h + MPAD, (size_t)m * sizeof(int64_t));
+    if (scores) memcpy(scores, h + MPAD + n, (size_t)n * sizeof(double));
+    if (mean_out) memcpy(mean_out, h + MPAD + 2 * n, (size_t)d * sizeof(double));
+    if (m_out) *m_out = m;
+    return BK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -466,7 +507,6 @@ int bk_collect_finish(bk_ctx *c, const int64_t *order, int64_t n, int64_t f, int
                                "collected (n=%lld)",
                     (long long)k->count, (long long)n);
     CHK(bk_check_args(n, k->d, f));
-    int64_t *ho = (int64_t *)k->horder.p;
     if (order) {
         std::vector<char> seen((size_t)k->count, 0);
         for (int64_t i = 0; i < n; ++i) {
@@ -481,8 +521,11 @@ int bk_collect_finish(bk_ctx *c, const int64_t *order, int64_t n, int64_t f, int
         }
     }
     DeviceGuard dg(c->device);
+    if (small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
+        return finish_small(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
     const hipStream_t st = c->stream;
     Drain drain{st};
+    int64_t *ho = (int64_t *)k->horder.p;
     for (int64_t i = 0; i < n; ++i) ho[i] = order ? order[i] : i;
     int64_t *dord = (int64_t *)k->order.p, *dsel = (int64_t *)k->sel.p;
     double *U = (double *)k->U.p, *dsc = (double *)k->scores.p;

@@ -290,6 +290,9 @@ int prepare_finish(bk_ctx *c, int64_t n, const ScoreSplit &sp, bool own_scores);
 int stage_finish(bk_ctx *c, const double *U, const Plan &pl, const void *dX, int dtype,
                  int64_t n, int64_t d, int64_t ld, int64_t f, int64_t *d_sel, double *d_scores,
                  double *d_mean, const ScoreSplit &sp = ScoreSplit());
+constexpr size_t HOUT_MPAD = 16;  // doubles kept for the record at the head of c->hout
+int ensure_hout(bk_ctx *c, size_t words);
+int ensure_small_queue(bk_ctx *c);
 bool small_ok(const bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d, int64_t ld);
 int run_small(bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d, int64_t ld, int64_t f,
               int64_t *d_sel, double *d_scores, double *d_mean, double *margin_out = nullptr,

@@ -277,39 +277,8 @@ int run_host_small(bk_ctx *c, const void *X, int where, int64_t ld, int dtype, c
     // no device-to-host copy after the kernel (a D2H costs ~15 us of PCIe
     // round trip at config B, more than the 63 KB it moves), one synchronize,
     // then copied to the caller's arrays on the host
-    constexpr size_t MPAD = 16;
-    const size_t words = MPAD + 2 * (size_t)n + (mean_out ? (size_t)d : 0);
-    if (c->hout_bytes < words * sizeof(double)) {
-        // an earlier asynchronous call's record may be unchecked: if it lives
-        // in the block about to be freed, read it first (its stream is done
-        // once wait_stream returns); a record in the context's own block stays
-        if (c->margin_host && c->margin_host == c->hout_host_margin) {
-            HIPCHK(wait_stream(c));
-            if (c->margin_unchecked) {
-                c->margin_unchecked = 0;
-                CHK(margin_status(c->margin_host));
-            }
-            c->margin_host = nullptr;
-            c->margin_valid = 0;
-        }
-        if (c->hout) (void)hipHostFree(c->hout);
-        c->hout = nullptr;
-        c->hout_bytes = 0;
-        c->hout_dev = nullptr;
-        c->hout_host_margin = nullptr;
-        const size_t bytes = std::max<size_t>(words * sizeof(double), 64 * 1024);
-#ifdef BK_HOUT_COHERENT  // ablation: uncached host block (each store crosses PCIe at once)
-        const unsigned hflags = hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent;
-#else  // GPU-cached, written back at the kernel's end: 156 vs 157 us per call at B
-        const unsigned hflags = hipHostMallocPortable | hipHostMallocMapped | hipHostMallocNonCoherent;
-#endif
-        HIPCHK(hipHostMalloc(&c->hout, bytes, hflags));
-        c->hout_bytes = bytes;
-        void *dp = nullptr;
-        HIPCHK(hipHostGetDevicePointer(&dp, c->hout, 0));
-        c->hout_dev = (double *)dp;
-        c->hout_host_margin = (const double *)c->hout;
-    }
+    constexpr size_t MPAD = HOUT_MPAD;
+    CHK(ensure_hout(c, MPAD + 2 * (size_t)n + (mean_out ? (size_t)d : 0)));
     double *blk = c->hout_dev;
     int64_t *dsel = (int64_t *)(blk + MPAD);
     double *dmean = mean_out ? blk + MPAD + 2 * n : nullptr;

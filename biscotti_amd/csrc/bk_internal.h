@@ -305,6 +305,17 @@ hipError_t launch_small(const void *X, int dtype, int64_t ld, int n, int64_t d, 
                         hipStream_t st, long long *trace = nullptr,
                         uint64_t spin_max = SMALL_SPIN_MAX, int check_lines = 0,
                         double *scores_out = nullptr, int g0 = 0, int gn = -1, bool sm = true);
+// k_collect_small: the finish of an incremental collection for n <= 128 in one
+// launch -- k_small's S and M items on the collection's Gram G (by arrival
+// slot, lower packed) and row store, through order (nullable: 0..n-1; it
+// travels in the kernel arguments).  sel, mean (nullable), margin and
+// scores_out (nullable) may be mapped host memory; scores and diag are device
+// scratch of n doubles; ctr: k_small's queue lines
+hipError_t launch_collect_small(const void *store, int dtype, int64_t ld, int n, int64_t d, int f,
+                                const double *G, const int64_t *order, double *scores,
+                                double *diag, int64_t *sel, double *mean, double *margin,
+                                double *scores_out, unsigned *ctr, int num_cu, hipStream_t st,
+                                uint64_t spin_max = SMALL_SPIN_MAX, int check_lines = 0);
 hipError_t launch_synth(void *X, int dtype, int64_t ld, int64_t n, int64_t dl, int64_t c0,
                         const int64_t *perm, const SynthParams &P, hipStream_t st);
 

@@ -36,6 +36,9 @@
 // The last workgroup to exit resets the counters for the next launch.  A wait
 // gives up after ~1 s and raises an error word instead of hanging the GPU.
 // Results are deterministic: every sum has a fixed order.
+//
+// k_collect_small (below k_small) is the same queue with the S and M items
+// only, for the finish of an incremental collection whose Gram already exists.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -456,60 +459,22 @@ __device__ __forceinline__ int blk_idx(int bi, int bj, int NB) {
     return bi * NB - bi * (bi - 1) / 2 + (bj - bi);
 }
 
-// S item i: row i with the whole workgroup, straight from the G items'
-// full-square partials (no separate reduce phase): G_ij (the upper element
-// (min, max), as the packed upper U held it) and every G_jj, each summed over
-// the P chunk partials in chunk order.  Then the distances, a sort by
-// counting (thread t ranks key t & 127 against half of the row, t >> 7; key e
-// goes to position #{keys before it in the (value, index) total order}), and
-// K2's summation with its own 256 threads: thread t sums rank 1 + t, the wave
-// butterfly, the 4 waves in order -- the same sorted array and the same
-// shape, so the score is K2's bitwise for the same Gram.
+// The second half of an S item, shared by k_small and k_collect_small: row i's
+// Gram entries are in LDS (gv[j] = G_ij, gv[NP + j] = G_jj for j < n, NP =
+// 16 NB; the workgroup has passed a barrier since they were written).  The
+// distances, a sort by counting (thread t ranks key t & 127 against its part
+// of the row; key e goes to position #{keys before it in the (value, index)
+// total order}), and K2's summation with its own 256 threads: thread t sums
+// rank 1 + t, the wave butterfly, the 4 waves in order -- the same sorted
+// array and the same shape, so the score is K2's bitwise for the same Gram.
+// Publishes scores[i] and diag[i] with sc1 stores.
 template <int NB>
-__device__ __forceinline__ void small_scores(const SmallArgs &a, int i, int tid, uint64_t *kbuf,
-                                             double *sbuf, int *rk, double *gv, d2v *gv2,
-                                             double *red, long long *tr) {
+__device__ __forceinline__ void small_rank_sum(const SmallArgs &a, int i, int tid, uint64_t *kbuf,
+                                               double *sbuf, int *rk, const double *gv, double *red,
+                                               long long *tr) {
     const int n = a.n, lane = tid & 63, wave = tid >> 6;
     const int64_t k = n - a.f - 2 > 0 ? n - a.f - 2 : 0;
-    // 16-B element pairs of the row (NP/2) and of the diagonal vector (NP/2),
-    // each summed over the P chunk partials in two fixed chains (chunks
-    // [0, P/2) and [P/2, P), each in order), then chain 0 + chain 1; a
-    // wave's lanes read consecutive 16-B granules (sc1 16-B loads move ~1.5x
-    // the bytes per second of 8-B ones)
     const int NP = 16 * NB;
-    const int64_t stride = (int64_t)NP * NP + NP;
-    const int pr = tid % NP, ch = tid / NP;  // pair pr < NP (row: pr < NP/2), chain ch < 256/NP
-    const int half = (a.P + 1) >> 1;
-    if (ch < 2) {
-        const unsigned e0 = pr < NP / 2 ? (unsigned)(i * NP + 2 * pr) : (unsigned)(NP * NP + 2 * pr - NP);
-        const unsigned nbytes = (unsigned)(a.P * stride * 8);
-        const int sb = ch ? half : 0, se = ch ? a.P : half;
-        d2v acc = {0.0, 0.0};
-        for (int s0 = sb; s0 < se; s0 += 32) {  // P <= 256: 4 rounds at most
-            d2v v[32];
-            // every load unconditional (past the chain's end: its last chunk
-            // again, dropped below), so no branch per load; acc starts at
-            // +0.0 and is never -0.0, so adding +0.0 leaves it bit for bit
-#pragma unroll
-            for (int u = 0; u < 32; ++u)
-                v[u] = ld1_16(a.part, nbytes, (unsigned)((e0 + (s0 + u < se ? s0 + u : se - 1) * stride) * 8));
-#pragma unroll
-            for (int u = 0; u < 32; ++u) {
-                const bool on = s0 + u < se;
-                acc.x += on ? v[u].x : 0.0;
-                acc.y += on ? v[u].y : 0.0;
-            }
-        }
-        gv2[ch * NP + pr] = acc;
-    }
-    __syncthreads();
-    // gv[j] = G_ij (j < NP), gv[NP + j] = G_jj
-    if (tid < NP) {
-        const d2v c0 = gv2[tid], c1 = gv2[NP + tid];
-        gv[2 * tid] = c0.x + c1.x;
-        gv[2 * tid + 1] = c0.y + c1.y;
-    }
-    __syncthreads();
     stamp(tr, 0);
     const int e = tid & 127, h = tid >> 7;
     const double di = gv[NP + i];
@@ -560,12 +525,64 @@ __device__ __forceinline__ void small_scores(const SmallArgs &a, int i, int tid,
     }
 }
 
+// S item i: row i with the whole workgroup, straight from the G items'
+// full-square partials (no separate reduce phase): G_ij (the upper element
+// (min, max), as the packed upper U held it) and every G_jj, each summed over
+// the P chunk partials in chunk order.  Then small_rank_sum.
+template <int NB>
+__device__ __forceinline__ void small_scores(const SmallArgs &a, int i, int tid, uint64_t *kbuf,
+                                             double *sbuf, int *rk, double *gv, d2v *gv2,
+                                             double *red, long long *tr) {
+    // 16-B element pairs of the row (NP/2) and of the diagonal vector (NP/2),
+    // each summed over the P chunk partials in two fixed chains (chunks
+    // [0, P/2) and [P/2, P), each in order), then chain 0 + chain 1; a
+    // wave's lanes read consecutive 16-B granules (sc1 16-B loads move ~1.5x
+    // the bytes per second of 8-B ones)
+    const int NP = 16 * NB;
+    const int64_t stride = (int64_t)NP * NP + NP;
+    const int pr = tid % NP, ch = tid / NP;  // pair pr < NP (row: pr < NP/2), chain ch < 256/NP
+    const int half = (a.P + 1) >> 1;
+    if (ch < 2) {
+        const unsigned e0 = pr < NP / 2 ? (unsigned)(i * NP + 2 * pr) : (unsigned)(NP * NP + 2 * pr - NP);
+        const unsigned nbytes = (unsigned)(a.P * stride * 8);
+        const int sb = ch ? half : 0, se = ch ? a.P : half;
+        d2v acc = {0.0, 0.0};
+        for (int s0 = sb; s0 < se; s0 += 32) {  // P <= 256: 4 rounds at most
+            d2v v[32];
+            // every load unconditional (past the chain's end: its last chunk
+            // again, dropped below), so no branch per load; acc starts at
+            // +0.0 and is never -0.0, so adding +0.0 leaves it bit for bit
+#pragma unroll
+            for (int u = 0; u < 32; ++u)
+                v[u] = ld1_16(a.part, nbytes, (unsigned)((e0 + (s0 + u < se ? s0 + u : se - 1) * stride) * 8));
+#pragma unroll
+            for (int u = 0; u < 32; ++u) {
+                const bool on = s0 + u < se;
+                acc.x += on ? v[u].x : 0.0;
+                acc.y += on ? v[u].y : 0.0;
+            }
+        }
+        gv2[ch * NP + pr] = acc;
+    }
+    __syncthreads();
+    // gv[j] = G_ij (j < NP), gv[NP + j] = G_jj
+    if (tid < NP) {
+        const d2v c0 = gv2[tid], c1 = gv2[NP + tid];
+        gv[2 * tid] = c0.x + c1.x;
+        gv[2 * tid + 1] = c0.y + c1.y;
+    }
+    __syncthreads();
+    small_rank_sum<NB>(a, i, tid, kbuf, sbuf, rk, gv, red, tr);
+}
+
 // M item c, part 1 (before the scores exist): columns [64 c, 64 c + 64) of
 // every row into LDS as fp64 (exact for fp32 rows), every load in flight --
 // so after the scores only LDS work is left.  Thread t: column t & 63, rows
-// t >> 6, + 4, ...
-template <typename T, int NB>
-__device__ __forceinline__ void small_mean_stage(const SmallArgs &a, int c, int tid, double *cols) {
+// t >> 6, + 4, ...  Staged row r is row `row(r)` of X (k_small: r itself;
+// k_collect_small: its arrival slot in the row store).
+template <typename T, int NB, typename R>
+__device__ __forceinline__ void small_mean_stage(const SmallArgs &a, int c, int tid, double *cols,
+                                                 R row) {
     if (!a.mean) return;
     const int cl = tid & 63, r0 = tid >> 6;
     const int64_t col = (int64_t)c * 64 + cl;
@@ -577,7 +594,7 @@ __device__ __forceinline__ void small_mean_stage(const SmallArgs &a, int c, int 
 #pragma unroll
     for (int u = 0; u < RU; ++u) {
         const int r = r0 + SMALL_NW * u;
-        v[u] = (double)X[(int64_t)(r < a.n ? r : a.n - 1) * a.ld];
+        v[u] = (double)X[(int64_t)row(r < a.n ? r : a.n - 1) * a.ld];
     }
 #pragma unroll
     for (int u = 0; u < RU; ++u) cols[(r0 + SMALL_NW * u) * 64 + cl] = v[u];
@@ -691,6 +708,46 @@ __device__ __forceinline__ void small_mean(const SmallArgs &a, int c, int tid, i
     if (col < a.d) a.mean[col] = acc / (double)m;
 }
 
+// the last workgroup out resets the queue for the next launch (stream
+// order: the next launch starts after this one has completed)
+__device__ __forceinline__ void small_last_out(const SmallArgs &a, unsigned *ctr, int tid) {
+    __shared__ unsigned s_err;
+    if (tid == 0) s_err = ctr_load(cline(ctr, C_ERR));
+    __syncthreads();
+    if (s_err) {
+        // a wait gave up: the outputs are invalid.  The margin says so
+        // (read_margin: BK_EHIP, from bk_synchronize, the synchronous
+        // entries and bk_selection_margin*), and so does the data path:
+        // every selected index becomes -1
+        if (tid == 0) {
+            a.margin[0] = __builtin_nan("");
+            a.margin[2] = MARGIN_HANDOFF_TIMEOUT;
+        }
+        if (a.sel && tid < a.n - a.f) a.sel[tid] = -1;
+    }
+    if (a.check_lines) {
+        // debug (BK_SMALL_CHECK_LINES): the reset below clears word 0 of
+        // each line only, because no other word is ever written; check
+        // that invariant over every word of every line, clear any word
+        // that breaks it and report the launch (MARGIN_QUEUE_DIRTY)
+        __shared__ unsigned s_dirty;
+        if (tid == 0) s_dirty = 0;
+        __syncthreads();
+        for (int w = tid; w < C_LINES * 32; w += SMALL_NT) {
+            if ((w & 31) == 0) continue;
+            if (ctr_load(ctr + w) != 0u) {
+                __hip_atomic_store(ctr + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                s_dirty = 1;  // benign race: every writer stores 1
+            }
+        }
+        __syncthreads();
+        if (tid == 0 && s_dirty) a.margin[2] = MARGIN_QUEUE_DIRTY;
+    }
+    __syncthreads();
+    // only word 0 of each line is ever written (checked under check_lines)
+    if (tid < C_LINES) __hip_atomic_store(ctr + 32 * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 template <typename T, bool VEC, int NB>
 __global__ __launch_bounds__(SMALL_NT) void k_small(SmallArgs a) {
     __shared__ int s_item;
@@ -766,7 +823,7 @@ __global__ __launch_bounds__(SMALL_NT) void k_small(SmallArgs a) {
             // while the scores are computed: this item's 64 columns of every
             // row into LDS, so after the scores only LDS work is left
             double *cols = reinterpret_cast<double *>(tile);
-            small_mean_stage<T, NB>(b, it - NGI - a.n, ot, cols);
+            small_mean_stage<T, NB>(b, it - NGI - a.n, ot, cols, [](int r) { return r; });
             wg_wait_flag(ctr, F_S, a.spin_max);
             if (a.trace && tid == 0) a.trace[8 * it + 1] = (long long)__builtin_amdgcn_s_memrealtime();
             small_mean<NB>(b, it - NGI - a.n, ot, wave, olane, kbuf, srow, dgl, bnd, balw, rk, cols,
@@ -782,46 +839,98 @@ __global__ __launch_bounds__(SMALL_NT) void k_small(SmallArgs a) {
             a.trace[8 * it + 5] = (long long)__builtin_amdgcn_s_memtime();
         }
     }
-    // the last workgroup out resets the queue for the next launch (stream
-    // order: the next launch starts after this one has completed)
-    if (last_out) {
-        __shared__ unsigned s_err;
-        if (tid == 0) s_err = ctr_load(cline(ctr, C_ERR));
-        __syncthreads();
-        if (s_err) {
-            // a wait gave up: the outputs are invalid.  The margin says so
-            // (read_margin: BK_EHIP, from bk_synchronize, the synchronous
-            // entries and bk_selection_margin*), and so does the data path:
-            // every selected index becomes -1
-            if (tid == 0) {
-                a.margin[0] = __builtin_nan("");
-                a.margin[2] = MARGIN_HANDOFF_TIMEOUT;
-            }
-            if (a.sel && tid < a.n - a.f) a.sel[tid] = -1;
-        }
-        if (a.check_lines) {
-            // debug (BK_SMALL_CHECK_LINES): the reset below clears word 0 of
-            // each line only, because no other word is ever written; check
-            // that invariant over every word of every line, clear any word
-            // that breaks it and report the launch (MARGIN_QUEUE_DIRTY)
-            __shared__ unsigned s_dirty;
-            if (tid == 0) s_dirty = 0;
-            __syncthreads();
-            for (int w = tid; w < C_LINES * 32; w += SMALL_NT) {
-                if ((w & 31) == 0) continue;
-                if (ctr_load(ctr + w) != 0u) {
-                    __hip_atomic_store(ctr + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    s_dirty = 1;  // benign race: every writer stores 1
-                }
-            }
-            __syncthreads();
-            if (tid == 0 && s_dirty) a.margin[2] = MARGIN_QUEUE_DIRTY;
-        }
-        __syncthreads();
-        // only word 0 of each line is ever written (checked under check_lines)
-        if (tid < C_LINES) __hip_atomic_store(ctr + 32 * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (last_out) small_last_out(a, ctr, tid);
     if (a.trace && tid == 0) a.trace[8 * total + 2 * blockIdx.x + 1] = (long long)__builtin_amdgcn_s_memrealtime();
+}
+
+// k_collect_small: the finish of an incremental collection (bk_collect.hip)
+// for n <= 128 in ONE launch.  The Gram exists already (by arrival slot, lower
+// packed: G[h (h + 1) / 2 + l], l <= h, written by earlier launches on the
+// stream, so plain loads see it), hence no G items: k_small's S and M items,
+// with the caller's row r read at arrival slot order[r] -- the S items' Gram
+// row from G, the M items' staged rows from the row store (s.X, s.ld).  The
+// order travels in the kernel arguments (slots < BK_MAX_N fit 16 bits), so
+// nothing is uploaded before the launch; entries past n are 0.
+struct CollectSmallArgs {
+    SmallArgs s;  // gn = 0, sm = 1; X = the row store; part, U, trace unused
+    const double *G;
+    uint16_t order[128];
+};
+
+// S item i, first half: thread j < n loads G_ij, thread 128 + j loads G_jj
+template <int NB>
+__device__ __forceinline__ void collect_row(const SmallArgs &a, const double *G,
+                                            const uint16_t *ord, int i, int tid, double *gv) {
+    const int j = tid & 127;
+    if (tid < 256 && j < a.n) {
+        const int64_t oj = ord[j], oi = tid < 128 ? (int64_t)ord[i] : oj;
+        const int64_t hi = oi > oj ? oi : oj, lo = oi > oj ? oj : oi;
+        gv[(tid < 128 ? 0 : 16 * NB) + j] = G[hi * (hi + 1) / 2 + lo];
+    }
+    __syncthreads();
+}
+
+// Items 0..n-1 are the S items (the first min(n, grid) of them held by
+// blockIdx: they wait for nothing), items n.. the M items (always dequeued;
+// they wait for F_S, raised by S items, all numbered before them).  Queue
+// words, hand-off form, timeout and reset are k_small's; the two kernels share
+// the context's queue lines and stream order keeps their launches apart.
+template <typename T, int NB>
+__global__ __launch_bounds__(SMALL_NT) void k_collect_small(CollectSmallArgs ca) {
+    __shared__ int s_item;
+    __shared__ unsigned s_old;
+    __shared__ __attribute__((aligned(16))) double cols[16 * NB * 64];  // M: rows x 64 columns
+    __shared__ uint64_t kbuf[128];                                      // S / selection keys
+    __shared__ __attribute__((aligned(16))) double sbuf[128];          // S: the sorted row
+    __shared__ int rk[(SMALL_NT / 128 - 1) * 128];                      // partial ranks
+    __shared__ double red[4];                                           // S waves
+    __shared__ double bnd[2];
+    __shared__ double dgl[128];
+    __shared__ int srow[128];
+    __shared__ uint64_t balw[2];
+    __shared__ uint16_t ord[128];
+    const SmallArgs &a = ca.s;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const int total = a.n + a.C;
+    unsigned *ctr = a.ctr;
+    if (tid < 128) ord[tid] = ca.order[tid];  // (the item loop's first barrier follows)
+    const int S0 = a.n < (int)gridDim.x ? a.n : (int)gridDim.x;
+    bool last_out = false;
+    for (bool first = true;; first = false) {
+        if (first && (int)blockIdx.x < S0) {
+            if (tid == 0) s_item = (int)blockIdx.x;
+        } else if (tid == 0) {
+            s_item = S0 + (int)__hip_atomic_fetch_add(cline(ctr, C_HEAD), 1u, __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        const int it = s_item;
+        // the item's view of the arguments and of the thread index, opaque to
+        // the optimizer (k_small: nothing hoisted out of the item loop)
+        SmallArgs b = a;
+        asm volatile("" : "+s"(b.n), "+s"(b.f), "+s"(b.C), "+s"(b.d), "+s"(b.ld));
+        int ot = tid;
+        asm volatile("" : "+v"(ot));
+        __syncthreads();
+        if (it >= total) {
+            // every workgroup ends on exactly one failed dequeue; the last of
+            // them (its add returned total - S0 + grid - 1) is the last one out
+            last_out = it == total + (int)gridDim.x - 1;
+            break;
+        }
+        if (it < a.n) {
+            // the S item's Gram row lives in the (idle) M columns
+            collect_row<NB>(b, ca.G, ord, it, ot, cols);
+            small_rank_sum<NB>(b, it, ot, kbuf, sbuf, rk, cols, red, nullptr);
+            if (wg_arrive(ctr, C_S, S_GRP, it, a.n, &s_old)) wg_raise(ctr, F_S);
+        } else {
+            small_mean_stage<T, NB>(b, it - a.n, ot, cols, [&](int r) { return (int)ord[r]; });
+            wg_wait_flag(ctr, F_S, a.spin_max);
+            small_mean<NB>(b, it - a.n, ot, wave, ot & 63, kbuf, srow, dgl, bnd, balw, rk, cols,
+                           nullptr);
+        }
+    }
+    if (last_out) small_last_out(a, ctr, tid);
 }
 
 // k_tiny: the whole call in ONE workgroup for n <= 16, d <= 128 (config A,
@@ -1033,6 +1142,60 @@ hipError_t launch_small(const void *X, int dtype, int64_t ld, int n, int64_t d, 
         launch_small_t<float, true>(a, p.nb16, grid, st);
     else
         launch_small_t<float, false>(a, p.nb16, grid, st);
+    return hipGetLastError();
+}
+
+template <typename T>
+static void launch_collect_small_t(const CollectSmallArgs &a, int NBv, int grid, hipStream_t st) {
+    switch (NBv) {
+    case 1: hipLaunchKernelGGL((k_collect_small<T, 1>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_collect_small<T, 2>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
+    case 3: hipLaunchKernelGGL((k_collect_small<T, 3>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
+    case 4: hipLaunchKernelGGL((k_collect_small<T, 4>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
+    case 5: hipLaunchKernelGGL((k_collect_small<T, 5>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
+    case 6: hipLaunchKernelGGL((k_collect_small<T, 6>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
+    case 7: hipLaunchKernelGGL((k_collect_small<T, 7>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
+    default: hipLaunchKernelGGL((k_collect_small<T, 8>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
+    }
+}
+
+hipError_t launch_collect_small(const void *store, int dtype, int64_t ld, int n, int64_t d, int f,
+                                const double *G, const int64_t *order, double *scores,
+                                double *diag, int64_t *sel, double *mean, double *margin,
+                                double *scores_out, unsigned *ctr, int num_cu, hipStream_t st,
+                                uint64_t spin_max, int check_lines) {
+    if (n < 1 || n > 128) return hipErrorInvalidValue;
+    CollectSmallArgs ca = {};
+    SmallArgs &a = ca.s;
+    a.X = store;
+    a.ld = ld;
+    a.d = d;
+    a.n = n;
+    a.f = f;
+    a.nS = n;
+    a.C = mean ? (int)((d + 63) / 64) : 1;  // item 0 writes sel and the margin even without a mean
+    a.sm = 1;
+    a.scores = scores;
+    a.diag = diag;
+    a.mean = mean;
+    a.margin = margin;
+    a.scores_out = scores_out;
+    a.sel = sel;
+    a.ctr = ctr;
+    a.spin_max = spin_max;
+    a.check_lines = check_lines;
+    ca.G = G;
+    for (int i = 0; i < n; ++i) {
+        const int64_t o = order ? order[i] : i;
+        if (o < 0 || o > 0xFFFF) return hipErrorInvalidValue;
+        ca.order[i] = (uint16_t)o;
+    }
+    const int total = n + a.C;
+    const int grid = total < num_cu ? total : num_cu;
+    if (dtype == 0)
+        launch_collect_small_t<double>(ca, (n + 15) / 16, grid, st);
+    else
+        launch_collect_small_t<float>(ca, (n + 15) / 16, grid, st);
     return hipGetLastError();
 }
 

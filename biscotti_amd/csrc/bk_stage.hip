@@ -381,6 +381,52 @@ static int margin_rec(bk_ctx *c) {
     return BK_OK;
 }
 
+// The n <= 128 synchronous entries' output block {margin (HOUT_MPAD doubles),
+// sel (n), scores (n), mean (d)}: mapped pinned memory the kernel writes
+// itself, grown to `words` doubles (grow-only; every user is synchronous, so
+// no launch still writes the old block when it is replaced)
+int ensure_hout(bk_ctx *c, size_t words) {
+    if (c->hout_bytes >= words * sizeof(double)) return BK_OK;
+    // an earlier asynchronous call's record may be unchecked: if it lives
+    // in the block about to be freed, read it first (its stream is done
+    // once wait_stream returns); a record in the context's own block stays
+    if (c->margin_host && c->margin_host == c->hout_host_margin) {
+        HIPCHK(wait_stream(c));
+        if (c->margin_unchecked) {
+            c->margin_unchecked = 0;
+            CHK(margin_status(c->margin_host));
+        }
+        c->margin_host = nullptr;
+        c->margin_valid = 0;
+    }
+    if (c->hout) (void)hipHostFree(c->hout);
+    c->hout = nullptr;
+    c->hout_bytes = 0;
+    c->hout_dev = nullptr;
+    c->hout_host_margin = nullptr;
+    const size_t bytes = std::max<size_t>(words * sizeof(double), 64 * 1024);
+#ifdef BK_HOUT_COHERENT  // ablation: uncached host block (each store crosses PCIe at once)
+    const unsigned hflags = hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent;
+#else  // GPU-cached, written back at the kernel's end: 156 vs 157 us per call at B
+    const unsigned hflags = hipHostMallocPortable | hipHostMallocMapped | hipHostMallocNonCoherent;
+#endif
+    HIPCHK(hipHostMalloc(&c->hout, bytes, hflags));
+    c->hout_bytes = bytes;
+    void *dp = nullptr;
+    HIPCHK(hipHostGetDevicePointer(&dp, c->hout, 0));
+    c->hout_dev = (double *)dp;
+    c->hout_host_margin = (const double *)c->hout;
+    return BK_OK;
+}
+
+// k_small's queue lines (zeroed once; every launch leaves them zero)
+int ensure_small_queue(bk_ctx *c) {
+    if (c->small_ctr.p) return BK_OK;
+    CHK(ensure(c->small_ctr, SMALL_CTR_WORDS * sizeof(unsigned)));
+    HIPCHK(hipMemsetAsync(c->small_ctr.p, 0, SMALL_CTR_WORDS * sizeof(unsigned), c->stream));
+    return BK_OK;
+}
+
 // stage_finish's workspace, allocated before a sharded call's exchange so that
 // a failure is caught by the ranks' status agreement: with split scoring
 // stage_finish holds a collective, which no rank may skip
@@ -585,10 +631,7 @@ int run_small(bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d, int64_
               int64_t *d_sel, double *d_scores, double *d_mean, double *margin_out,
               double *scores_out, int g0, int gn, bool sm) {
     const SmallPlan sp = small_plan((int)n, d, c->num_cu);
-    if (!c->small_ctr.p) {
-        CHK(ensure(c->small_ctr, SMALL_CTR_WORDS * sizeof(unsigned)));
-        HIPCHK(hipMemsetAsync(c->small_ctr.p, 0, SMALL_CTR_WORDS * sizeof(unsigned), c->stream));
-    }
+    CHK(ensure_small_queue(c));
     // per chunk: the full-square partial Gram (16 nb16)^2 + its diagonal (bk_small.hip)
     const size_t np16 = (size_t)16 * sp.nb16;
     CHK(ensure(c->small_part, (size_t)sp.P * (np16 * np16 + np16) * sizeof(double)));

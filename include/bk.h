@@ -177,7 +177,9 @@ int bk_collect_count(bk_ctx *ctx, int64_t *count);
  * scores and mean_out nullable); indices refer to the caller's rows 0..n-1.
  * Does not consume the collection: more rows may be added and finish called
  * again.  bk_selection_margin* then reports this finish's record (d = the
- * collection's d, u_G = 2^-53). */
+ * collection's d, u_G = 2^-53).  For n <= 128 and d <= 32,768 the finish is one
+ * kernel launch with no copy before or after it (bk_set_small_path(ctx, 0)
+ * gives the general launch chain instead; the outputs are bitwise the same). */
 int bk_collect_finish(bk_ctx *ctx, const int64_t *order, int64_t n, int64_t f,
                       int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out);
 

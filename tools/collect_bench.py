@@ -1,9 +1,10 @@
 """Measure the incremental collection (bk_collect_*) against the packed call.
 
-    python tools/collect_bench.py [--out profiles/r07/collect_bench.json]
+    python tools/collect_bench.py [--out profiles/r08/collect_bench.json]
+                                  [--small-path {on,off}] [--shapes A,B,D]
 
-Per shape (B: 100 x 7,850, D: 512 x 1,048,576; fp64, pinned host rows), in a
-child process of its own under a time limit:
+Per shape (A: 10 x 25, B: 100 x 7,850, D: 512 x 1,048,576; fp64, pinned host
+rows), in a child process of its own under a time limit:
   1. last_add_to_finish_ms: every row but the last is collected and the stream
      idle (the verifier waiting for its last peer); then the time from the
      start of the last bk_collect_add to the return of bk_collect_finish --
@@ -16,7 +17,11 @@ child process of its own under a time limit:
      (bk_timing_read; m rows read once).
   3. finish_ms: bk_collect_finish alone (gather, K2, K3, K3b, K4, outputs)
      against the packed call's K1b..K4 from bk_timing_read (at B the packed
-     call is ONE launch, k_small, which is reported whole).
+     call is ONE launch, k_small, which is reported whole), and the launches
+     of one finish per kernel from bk_timing_read (finish_launches).
+--small-path off runs every n <= 128 call on the general chain
+(bk_set_small_path), the collection's finish included: the A/B of the
+one-launch finish.
 Not a pass/fail gate; prints one JSON line per shape and writes them all.
 """
 import argparse
@@ -32,10 +37,11 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-SHAPES = {"B": (100, 7850, 30, 20, 120), "D": (512, 1048576, 153, 3, 420)}  # n, d, f, reps, limit s
+SHAPES = {"A": (10, 25, 2, 20, 120), "B": (100, 7850, 30, 20, 120),
+          "D": (512, 1048576, 153, 3, 420)}  # n, d, f, reps, limit s
 
 
-def run_shape(tag):
+def run_shape(tag, small_path=True):
     import numpy as np
     import torch
     from biscotti_amd import _lib
@@ -46,6 +52,7 @@ def run_shape(tag):
     eng = Engine(0)
     stream = torch.cuda.Stream()
     eng.set_stream(stream.cuda_stream)
+    eng.set_small_path(small_path)
     Xd = torch.empty((n, d), dtype=torch.float64, device="cuda")
     eng.synth_fill_ptr(Xd.data_ptr(), _lib.BK_F64, n, d, d, 0, d, 20261019, f)
     eng.synchronize()
@@ -68,6 +75,7 @@ def run_shape(tag):
                                        sc.ctypes.data, mean.ctypes.data))
 
     out = {"shape": tag, "n": n, "d": d, "f": f, "dtype": "float64", "reps": reps,
+           "small_path": bool(small_path),
            "device": torch.cuda.get_device_name(0)}
     # ---- the packed call: wall time, then its kernels ----------------------
     packed()
@@ -111,6 +119,15 @@ def run_shape(tag):
     out["finish_ms"] = {"median": statistics.median(fin), "min": min(fin)}
     out["last_add_to_finish_over_packed"] = (out["last_add_to_finish_ms"]["median"] /
                                              out["packed_pinned_ms"]["median"])
+    out["finish_over_packed"] = out["finish_ms"]["median"] / out["packed_pinned_ms"]["median"]
+    # the finish's launches per kernel (the collection of the last repetition)
+    eng.timing_enable(True)
+    for _ in range(reps):
+        finish()
+    tf = eng.timing_read()
+    eng.timing_enable(False)
+    out["finish_launches"] = {k: v["count"] / reps for k, v in tf.items()}
+    out["finish_kernels_avg_ms"] = {k: v["avg_ms"] for k, v in tf.items()}
     # ---- 2: the border at count = 1 against the resident rows ------------------
     del Xp
     eng.collect_begin(n, d, np.float64)
@@ -137,17 +154,25 @@ def run_shape(tag):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r07", "collect_bench.json"))
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r08", "collect_bench.json"))
     ap.add_argument("--shape", choices=sorted(SHAPES), help="(child) measure this shape only")
+    ap.add_argument("--shapes", default=",".join(sorted(SHAPES)),
+                    help="comma-separated shapes to measure (default: all)")
+    ap.add_argument("--small-path", choices=("on", "off"), default="on",
+                    help="off: n <= 128 calls take the general chain (bk_set_small_path)")
     args = ap.parse_args()
     if args.shape:
-        run_shape(args.shape)
+        run_shape(args.shape, args.small_path == "on")
         return 0
+    tags = [t for t in args.shapes.split(",") if t]
+    if any(t not in SHAPES for t in tags):
+        ap.error("unknown shape in --shapes (have %s)" % ",".join(sorted(SHAPES)))
     results = []
-    for tag in sorted(SHAPES):
+    for tag in tags:
         # a fresh child per shape, under its own time limit; a failed step ends the run
         r = subprocess.run(["timeout", "-k", "10", str(SHAPES[tag][4]), sys.executable,
-                            os.path.abspath(__file__), "--shape", tag], stdout=subprocess.PIPE,
+                            os.path.abspath(__file__), "--shape", tag, "--small-path",
+                            args.small_path], stdout=subprocess.PIPE,
                            text=True)
         if r.returncode != 0:
             print("shape %s failed with status %d" % (tag, r.returncode), file=sys.stderr)
