@@ -216,7 +216,9 @@ void bk_destroy(bk_ctx *c) {
                           &c->roni_X, &c->roni_y, &c->roni_w, &c->roni_d, &c->roni_cnt, &c->roni_s,
                           &c->noise, &c->diag, &c->bnd, &c->Ut, &c->small_ctr, &c->small_part,
                           &c->mean_part, &c->status, &c->rmc_X, &c->rmc_y, &c->rmc_ws,
-                      &c->rmc_xn, &c->rmc_idx, &c->rmc_nt, &c->i8ws, &c->sgather, &c->pcnt};
+                      &c->rmc_xn, &c->rmc_idx, &c->rmc_nt, &c->i8ws, &c->sgather, &c->pcnt,
+                          &c->batch_ctr, &c->batch_part, &c->batch_diag, &c->batch_scores,
+                          &c->batch_rec, &c->batch_X, &c->batch_sel, &c->batch_hsc, &c->batch_mean};
         if (c->hmargin) (void)hipHostFree(c->hmargin);
         if (c->hout) (void)hipHostFree(c->hout);
         if (c->copy) (void)hipStreamSynchronize(c->copy);

@@ -1,7 +1,7 @@
 // bk_ctx.h -- the context behind the C ABI (struct bk_ctx) and what its entry
 // families share: the error string, the status macros, the staging of K1..K4
 // and the guards.  Private to the files that implement include/bk.h (bk_api,
-// bk_stage, bk_host, bk_comm, bk_group, bk_entries and the host half of
+// bk_stage, bk_host, bk_comm, bk_group, bk_entries, bk_batch and the host half of
 // bk_collect); the kernels see bk_internal.h only.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -90,6 +90,22 @@ struct bk_ctx {
     // k_small (n <= 128, one launch): its queue counters (zeroed once; every
     // launch leaves them zero) and the split-K partials
     DevBuf small_ctr, small_part;
+    // bk_multikrum_batch*: buffers of their own (a single call or a collection
+    // finish between two batched calls is unaffected): the queue lines (the
+    // launch's, then one set per problem; zeroed at allocation, every launch
+    // leaves them zero), the partials of one launch, per-problem diag and
+    // scratch scores, the batch x MARGIN_WORDS records, and the host entry's
+    // device copies of X and of the outputs
+    DevBuf batch_ctr, batch_part, batch_diag, batch_scores, batch_rec;
+    DevBuf batch_X, batch_sel, batch_hsc, batch_mean;
+    // the records of the last batched call on the host (fetched by the first
+    // reader once the stream is done) and the one bk_selection_margin* reports
+    // (margin_host points at batch_pick while a batched call is the last finish)
+    std::vector<double> batch_rec_h;
+    int64_t batch_last = 0;   // problems of the last batched call
+    int batch_fetched = 0;
+    int batch_one = 0;        // the last batched call had one problem: the single call's own record
+    double batch_pick[MARGIN_WORDS] = {0};
     DevBuf mean_part;  // K4 of a large selection: per-segment column sums (launch_mean)
     int small_on = 1;
     uint64_t small_spin_max = SMALL_SPIN_MAX;  // test knob BK_SMALL_SPIN_MAX=<polls>[,<launches>]
@@ -303,6 +319,8 @@ hipError_t wait_stream(bk_ctx *c);
 int margin_status(const double *mg);
 int read_margin(bk_ctx *c, double (&mg)[MARGIN_WORDS]);
 int check_margin_readback(bk_ctx *c);
+// bk_batch.hip
+int batch_fetch(bk_ctx *c);
 // bk_host.hip
 int stage_host_pipelined(bk_ctx *c, const void *X, int64_t ld, int dtype, const double *noise,
                          int64_t k, int64_t noise_ld, int64_t n, int64_t d, char *dX,

@@ -1,4 +1,4 @@
-// bk_internal.h -- what the kernel files (bk_kernels, bk_small, bk_i8,
+// bk_internal.h -- what the kernel files (bk_kernels, bk_small, bk_small_batch, bk_i8,
 // bk_aggregate, bk_roni, bk_collect) and the planner (bk_plan) offer the files
 // that implement the C ABI: plans, layouts and launchers.  The context those
 // files share among themselves is bk_ctx.h, which the kernels never see.  Not
@@ -316,6 +316,18 @@ hipError_t launch_collect_small(const void *store, int dtype, int64_t ld, int n,
                                 double *diag, int64_t *sel, double *mean, double *margin,
                                 double *scores_out, unsigned *ctr, int num_cu, hipStream_t st,
                                 uint64_t spin_max = SMALL_SPIN_MAX, int check_lines = 0);
+// bk_small_batch.hip, k_small_batch / k_tiny_batch: W problems of one shape in one launch (problem
+// b's rows at X + b * stride elements).  Per problem: part_stride doubles of
+// partials, n scores, n diag, m = n - f sel, d mean (nullable), MARGIN_WORDS of
+// margin; lines: (1 + W) * SMALL_CTR_WORDS zeroed queue words (the launch's,
+// then each problem's; every launch leaves them zero).  part and lines are
+// unused (nullable) when tiny_ok(n, d)
+constexpr int SMALL_BATCH_MAX_W = 1024;  // problems per launch (9 KiB of queue lines each)
+hipError_t launch_small_batch(const void *X, int dtype, int64_t ld, int64_t stride, int W, int n,
+                              int64_t d, int f, const SmallPlan &p, double *part,
+                              int64_t part_stride, double *scores, double *diag, int64_t *sel,
+                              double *mean, double *margin, unsigned *lines, int num_cu,
+                              hipStream_t st, uint64_t spin_max = SMALL_SPIN_MAX);
 hipError_t launch_synth(void *X, int dtype, int64_t ld, int64_t n, int64_t dl, int64_t c0,
                         const int64_t *perm, const SynthParams &P, hipStream_t st);
 

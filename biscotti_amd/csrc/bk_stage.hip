@@ -745,6 +745,8 @@ int read_margin(bk_ctx *c, double (&mg)[MARGIN_WORDS]) {
     // the record sits in mapped host memory (the context's, or the n <= 128
     // host entry's output block): once the stream is done it is readable
     HIPCHK(wait_stream(c));
+    // after a batched call: its records are fetched and one picked (bk_batch.hip)
+    if (c->margin_host == c->batch_pick) CHK(batch_fetch(c));
     memcpy(mg, c->margin_host, sizeof mg);
     c->margin_unchecked = 0;
     return margin_status(mg);

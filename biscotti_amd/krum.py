@@ -31,8 +31,8 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 
-__all__ = ["Engine", "krum", "get_krum_scores", "krum_mean", "KRUMValidator", "Update",
-           "default_engine"]
+__all__ = ["Engine", "krum", "krum_batch", "get_krum_scores", "krum_mean", "KRUMValidator",
+           "Update", "default_engine"]
 
 
 def _p(x):
@@ -329,6 +329,65 @@ class Engine:
         check(lib().bk_multikrum_device(self._ctx, _p(x_ptr), dtype, n, d, ld, f, _p(sel_ptr),
                                         _p(scores_ptr), _p(mean_ptr)))
 
+    # ---- batched entries (bk_multikrum_batch*): B problems of one shape ----
+    def multikrum_batch(self, X, f, want_scores=True, want_mean=True, pinned=False):
+        """X: (B, n, d) float64 / float32, C-contiguous or with uniform strides
+        (unit element stride; row and problem strides whole elements, the
+        problems not overlapping) -- B independent Multi-Krum problems.  Returns
+        sel (B, n - f) int64, scores (B, n) or None, mean (B, d) or None; problem
+        b's are bitwise multikrum's on X[b].  pinned: X lies in pinned host
+        memory (BK_HOST_PINNED)."""
+        X = np.asarray(X)
+        if X.dtype not in (np.float64, np.float32):
+            X = X.astype(np.float64)
+        if X.ndim != 3:
+            raise ValueError("X must be 3-D (B problems x n updates x d)")
+        B, n, d = X.shape
+        it = X.itemsize
+        if B < 1:
+            raise ValueError("need at least one problem (B=%d)" % B)
+        if (X.strides[2] != it or X.strides[1] % it or X.strides[0] % it or
+                X.strides[1] < d * it or X.strides[0] < (n - 1) * X.strides[1] + d * it):
+            X = np.ascontiguousarray(X)
+        ld = X.strides[1] // it
+        stride = X.strides[0] // it
+        f = int(f)
+        check(lib().bk_check_args(n, d, f))
+        m = n - f
+        sel = np.empty((B, m), dtype=np.int64)
+        mo = ctypes.c_int64(0)
+        sc = np.empty((B, n), dtype=np.float64) if want_scores else None
+        mean = np.empty((B, d), dtype=np.float64) if want_mean else None
+        dt = _lib.BK_F32 if X.dtype == np.float32 else _lib.BK_F64
+        check(lib().bk_multikrum_batch(self._ctx, X.ctypes.data,
+                                       _lib.BK_HOST_PINNED if pinned else _lib.BK_HOST, dt, B, n,
+                                       d, ld, stride, f, sel.ctypes.data, ctypes.addressof(mo),
+                                       sc.ctypes.data if sc is not None else None,
+                                       mean.ctypes.data if mean is not None else None))
+        assert mo.value == m
+        return sel, sc, mean
+
+    def multikrum_batch_device_ptr(self, x_ptr, dtype, batch, n, d, ld, stride, f, sel_ptr,
+                                   scores_ptr=None, mean_ptr=None):
+        check(lib().bk_multikrum_batch_device(self._ctx, _p(x_ptr), dtype, batch, n, d, ld,
+                                              stride, f, _p(sel_ptr), _p(scores_ptr),
+                                              _p(mean_ptr)))
+
+    def selection_margin_batch(self, batch):
+        """The records of the last batched call, one dict per problem (the keys
+        of selection_margin); batch: that call's problem count."""
+        rec = (ctypes.c_double * (8 * batch))()
+        check(lib().bk_selection_margin_batch(self._ctx, rec, batch))
+        keys = ("gap", "err_bound", "near_tie", "M", "s_lo", "s_hi", "d", "k")
+        out = []
+        for b in range(batch):
+            r = dict(zip(keys, (float(x) for x in rec[8 * b:8 * b + 8])))
+            r["near_tie"] = bool(r["near_tie"])
+            r["d"] = int(r["d"])
+            r["k"] = int(r["k"])
+            out.append(r)
+        return out
+
     def multikrum_sharded_ptr(self, x_ptr, dtype, n, d_local, ld, f, sel_ptr, scores_ptr=None,
                               mean_ptr=None):
         check(lib().bk_multikrum_sharded_device(self._ctx, _p(x_ptr), dtype, n, d_local, ld, f,
@@ -516,6 +575,21 @@ def krum(deltas, clip, engine: Optional[Engine] = None):
         raise ValueError("kth(=%d) out of bounds (%d)" % (n - clip, n))
     sel, _, _ = (engine or default_engine()).multikrum(X, clip, want_scores=False,
                                                        want_mean=False)
+    return sel
+
+
+def krum_batch(deltas, clip, engine: Optional[Engine] = None):
+    """krum(deltas[b], clip) for every batch b of a sequence of equally shaped
+    batches (B x n x d), in one call: a (B, n - clip) array of ascending
+    indices.  Raises krum's ValueError for clip outside [1, n)."""
+    X = _as_matrix(deltas)
+    if X.ndim != 3:
+        raise ValueError("deltas must be B batches of n updates of d values")
+    n = X.shape[1]
+    if clip < 1 or clip >= n:
+        raise ValueError("kth(=%d) out of bounds (%d)" % (n - clip, n))
+    sel, _, _ = (engine or default_engine()).multikrum_batch(X, clip, want_scores=False,
+                                                             want_mean=False)
     return sel
 
 

@@ -191,6 +191,47 @@ int bk_collect_finish(bk_ctx *ctx, const int64_t *order, int64_t n, int64_t f,
 int bk_multikrum_device(bk_ctx *ctx, const void *dX, int dtype, int64_t n, int64_t d,
                         int64_t ld, int64_t f, int64_t *d_sel_idx, double *d_scores,
                         double *d_mean);
+/* ---- many small problems in one call (throughput mode) ---------------------
+ * `batch` independent Multi-Krum problems of one shape (n, d, f):
+ * problem b is the row-major n x d matrix at X + b*stride elements (row
+ * stride ld; stride >= (n-1)*ld + d).  Outputs are per problem:
+ * d_sel_idx batch x (n-f), d_scores batch x n (nullable),
+ * d_mean batch x d (nullable).  Device pointers, asynchronous on the
+ * context stream.
+ * Every output of problem b -- sel, scores, mean and its margin record -- is
+ * bitwise what bk_multikrum_device gives on that problem alone under the same
+ * context settings.  Within the one-launch range (n <= 128, d <= 32768, the
+ * small path on) the problems share launches: k_small_batch runs k_small's
+ * work items of W problems from one queue (k_tiny_batch: one workgroup per
+ * problem for n <= 16, d <= 128), W bounded by the launch's partial workspace
+ * (the environment variable BK_BATCH_WS_BYTES, read at the call, may lower its
+ * 1 GiB default; a larger batch runs as consecutive launches).  Any other
+ * shape, bk_set_small_path(ctx, 0) and batch = 1 run the single-problem device
+ * path once per problem on the stream (the f32 / f64 modes and certification
+ * apply per problem).  hipGraph replay does not apply.
+ * A hand-off give-up in any problem of a launch invalidates the launch: every
+ * d_sel_idx entry of its problems is -1 and bk_synchronize returns BK_EHIP.
+ * Afterwards bk_selection_margin / _record report the record of the
+ * lowest-index problem with near_tie = 1, or, if there is none, of the problem
+ * with the smallest gap - err_bound; bk_selection_margin_batch gives them all.
+ * BK_EINVAL: null ctx, X or d_sel_idx; batch < 1; stride too small; n, f
+ * outside bk_check_args.  BK_ENOTSUP: batch > BK_MAX_BATCH.  The shape checks
+ * come first and need no GPU. */
+#define BK_MAX_BATCH 65536
+int bk_multikrum_batch_device(bk_ctx *ctx, const void *dX, int dtype, int64_t batch, int64_t n,
+                              int64_t d, int64_t ld, int64_t stride, int64_t f,
+                              int64_t *d_sel_idx, double *d_scores, double *d_mean);
+/* X on the host (BK_HOST / BK_HOST_PINNED), host outputs (sel_idx batch x
+ * (n-f), *m_out = n-f, scores and mean_out nullable), synchronous: one H2D
+ * copy of the whole batch, (batch-1)*stride + (n-1)*ld + d elements, then the
+ * device entry and the copies back. */
+int bk_multikrum_batch(bk_ctx *ctx, const void *X, int where, int dtype, int64_t batch, int64_t n,
+                       int64_t d, int64_t ld, int64_t stride, int64_t f, int64_t *sel_idx,
+                       int64_t *m_out, double *scores, double *mean_out);
+/* the batch x 8 margin records of the last batched call (the layout of
+ * bk_selection_margin_record, one per problem); batch must be that call's */
+int bk_selection_margin_batch(bk_ctx *ctx, double *records, int64_t batch);
+
 /* Small batches (n <= 128, d <= 32768: Biscotti's deployed shapes, configs A
  * and B) run as ONE launch,
  * k_small: split-K Gram, reduce, scores, selection and mean pulled as work
