@@ -104,6 +104,7 @@ SIGNATURES = {
     "bk_multikrum_batch": (_i, [_p, _p, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p,
                                 _p]),
     "bk_selection_margin_batch": (_i, [_p, _pd, _i64]),
+    "bk_collect_finish_batch": (_i, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p]),
 }
 
 _lib = None

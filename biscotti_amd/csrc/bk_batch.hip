@@ -159,6 +159,15 @@ int batch_fetch(bk_ctx *c) {
                           (size_t)B * MARGIN_WORDS * sizeof(double), hipMemcpyDeviceToHost,
                           c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    batch_pick_record(c);
+    return BK_OK;
+}
+
+// batch_pick from the batch_last records in batch_rec_h (a synchronous caller
+// that has them on the host already -- bk_collect_finish_batch -- calls this
+// itself and no fetch follows)
+void batch_pick_record(bk_ctx *c) {
+    const int64_t B = c->batch_last;
     const double *r = c->batch_rec_h.data();
     int64_t pick = -1;
     for (int64_t b = 0; b < B && pick < 0; ++b)
@@ -174,7 +183,6 @@ int batch_fetch(bk_ctx *c) {
     }
     memcpy(c->batch_pick, r + pick * MARGIN_WORDS, sizeof c->batch_pick);
     c->batch_fetched = 1;
-    return BK_OK;
 }
 
 }  // namespace bk

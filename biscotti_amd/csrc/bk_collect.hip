@@ -15,7 +15,9 @@
 //   k_collect_gather G, through the caller's order -> the packed upper + record
 //   k_collect_selmap the selection mapped to arrival slots, for K4 on the store
 // A finish of n <= 128 rows, d <= 32,768 (small_ok) takes none of the last two
-// nor K2..K4: one k_collect_small launch (bk_small.hip) does it all.
+// nor K2..K4: one k_collect_small launch (bk_small.hip) does it all, and
+// bk_collect_finish_batch runs many such finishes over the one collection as
+// k_collect_small_batch launches (bk_collect_batch.hip).
 // Every element of G is the same sum whatever the add's count and however many
 // rows are resident: chunk s covers the same columns, one wave sums a chunk's
 // products in lane order and the chunks are added in the same tree, so the
@@ -228,17 +230,34 @@ struct Collect {
     int64_t n_cap = 0, d = 0, ld = 0, count = 0;
     int S = 0;  // chunks of a row: ceil(d es / BORDER_CHUNK_BYTES)
     Buf store, G, P, U, sel, slots, scores, mean, mean_part, order, horder, ring;
+    // bk_collect_finish_batch: buffers of its own (a single finish or any
+    // bk_multikrum* between two batched finishes touches none of them): the
+    // 16-bit orders and their pinned staging, per-problem scores, diag, sel and
+    // mean, and the queue lines (zeroed at allocation; every launch leaves
+    // them zero).  The records go to the context's batch record store
+    Buf b_order, b_horder, b_scores, b_diag, b_sel, b_mean, b_ctr;
     hipEvent_t ev_slot[RING_SLOTS] = {};
     bool slot_used[RING_SLOTS] = {};
     int ring_next = 0;
     hipEvent_t ev_up = nullptr;
 };
 
+// the batched finish's buffers (the stream is idle)
+static void collect_batch_release(Collect *k) {
+    for (Buf *b : {&k->b_order, &k->b_horder, &k->b_scores, &k->b_diag, &k->b_sel, &k->b_mean,
+                   &k->b_ctr}) {
+        if (b->p) (void)(b->pinned ? hipHostFree(b->p) : hipFree(b->p));
+        b->p = nullptr;
+        b->bytes = 0;
+    }
+}
+
 void collect_destroy(Collect *k) {
     if (!k) return;
     for (Buf *b : {&k->store, &k->G, &k->P, &k->U, &k->sel, &k->slots, &k->scores, &k->mean,
                    &k->mean_part, &k->order, &k->horder, &k->ring})
         if (b->p) (void)(b->pinned ? hipHostFree(b->p) : hipFree(b->p));
+    collect_batch_release(k);
     for (hipEvent_t ev : k->ev_slot)
         if (ev) (void)hipEventDestroy(ev);
     if (k->ev_up) (void)hipEventDestroy(k->ev_up);
@@ -260,7 +279,7 @@ struct Drain {
 
 // Grow the buffers in `want` to their sizes, all or nothing: the new blocks are
 // allocated first, and only when every one exists are the old ones freed
-int grow_all(const std::vector<std::pair<Buf *, size_t>> &want) {
+int grow_all(const std::vector<std::pair<Buf *, size_t>> &want, const char *who = "bk_collect_begin") {
     std::vector<void *> fresh(want.size(), nullptr);
     for (size_t i = 0; i < want.size(); ++i) {
         Buf *b = want[i].first;
@@ -271,7 +290,7 @@ int grow_all(const std::vector<std::pair<Buf *, size_t>> &want) {
         if (e != hipSuccess) {
             for (size_t q = 0; q < i; ++q)
                 if (fresh[q]) (void)(want[q].first->pinned ? hipHostFree(fresh[q]) : hipFree(fresh[q]));
-            return fail(BK_ENOMEM, "bk_collect_begin: %s(%zu bytes): %s",
+            return fail(BK_ENOMEM, "%s: %s(%zu bytes): %s", who,
                         b->pinned ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
         }
     }
@@ -332,6 +351,9 @@ int upload_pageable(Collect *k, char *dst, const char *src, size_t bytes, hipStr
     return BK_OK;
 }
 
+int finish_checked(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
+                   int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out);
+
 // The finish of the deployed shapes (small_ok: n <= 128, d <= 32,768) in one
 // launch: k_collect_small reads the Gram and the row store through the order
 // in its own arguments and writes {margin, sel, scores, mean} into the
@@ -390,7 +412,7 @@ int bk_collect_begin(bk_ctx *c, int dtype, int64_t n_cap, int64_t d) {
     if (!k) {
         k = new (std::nothrow) Collect();
         if (!k) return fail(BK_ENOMEM, "host allocation of the collection failed");
-        k->horder.pinned = k->ring.pinned = true;
+        k->horder.pinned = k->ring.pinned = k->b_horder.pinned = true;
         hipError_t e = hipEventCreateWithFlags(&k->ev_up, hipEventDisableTiming);
         for (int s = 0; s < RING_SLOTS && e == hipSuccess; ++s)
             e = hipEventCreateWithFlags(&k->ev_slot[s], hipEventDisableTiming);
@@ -408,6 +430,9 @@ int bk_collect_begin(bk_ctx *c, int dtype, int64_t n_cap, int64_t d) {
     const size_t un = (size_t)n_cap;
     // work of the old collection may still read the buffers about to be replaced
     HIPCHK(hipStreamSynchronize(st));
+    // a collection that regrows lets go of the batched finish's buffers
+    if (un * (size_t)ld * es > k->store.bytes || un * (un + 1) / 2 * sizeof(double) > k->G.bytes)
+        collect_batch_release(k);
     CHK(grow_all({{&k->store, un * (size_t)ld * es},
                   {&k->G, un * (un + 1) / 2 * sizeof(double)},
                   {&k->P, (size_t)S * BORDER_ROWS * un * sizeof(double)},
@@ -521,6 +546,16 @@ int bk_collect_finish(bk_ctx *c, const int64_t *order, int64_t n, int64_t f, int
         }
     }
     DeviceGuard dg(c->device);
+    return finish_checked(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
+}
+
+}  // extern "C"
+
+namespace {
+
+// bk_collect_finish past its checks (the context mutex held, the device selected)
+int finish_checked(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
+                   int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
     if (small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
         return finish_small(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
     const hipStream_t st = c->stream;
@@ -561,6 +596,151 @@ int bk_collect_finish(bk_ctx *c, const int64_t *order, int64_t n, int64_t f, int
     CHK(check_margin_readback(c));
     drain.armed = false;
     if (m_out) *m_out = m;
+    return BK_OK;
+}
+
+// The batch within k_collect_small's range: launches of W <= SMALL_BATCH_MAX_W
+// problems (k_collect_small_batch, bk_collect_batch.hip) on buffers of the
+// collection's own; the slots go up as 16-bit numbers in one copy from pinned
+// staging, the outputs come back after the last launch, then one wait.  The
+// records land in the context's batch record store (bk_batch.hip batch_fetch).
+int finish_batch_small(bk_ctx *c, Collect *k, const int64_t *orders, int64_t batch, int64_t n,
+                       int64_t f, int64_t *sel_idx, double *scores, double *mean_out) {
+    const int64_t m = n - f, d = k->d;
+    const hipStream_t st = c->stream;
+    const size_t ub = (size_t)batch, un = (size_t)n;
+    const int64_t W = batch < SMALL_BATCH_MAX_W ? batch : SMALL_BATCH_MAX_W;
+    const size_t lbytes =
+        (size_t)(COLLECT_BATCH_QLINES + W * COLLECT_BATCH_LINES) * 32 * sizeof(unsigned);
+    const bool new_lines = lbytes > k->b_ctr.bytes;
+    // (every user of these buffers is synchronous: none is in use when it grows)
+    CHK(grow_all({{&k->b_order, ub * un * sizeof(uint16_t)},
+                  {&k->b_horder, ub * un * sizeof(uint16_t)},
+                  {&k->b_scores, ub * un * sizeof(double)},
+                  {&k->b_diag, ub * un * sizeof(double)},
+                  {&k->b_sel, ub * (size_t)m * sizeof(int64_t)},
+                  {&k->b_mean, mean_out ? ub * (size_t)d * sizeof(double) : 0},
+                  {&k->b_ctr, lbytes}},
+                 "bk_collect_finish_batch"));
+    CHK(ensure(c->batch_rec, ub * MARGIN_WORDS * sizeof(double)));
+    if (new_lines) HIPCHK(hipMemsetAsync(k->b_ctr.p, 0, k->b_ctr.bytes, st));
+    Drain drain{st};
+    uint16_t *ho = (uint16_t *)k->b_horder.p;
+    for (size_t i = 0; i < ub * un; ++i) ho[i] = (uint16_t)orders[i];  // validated: < count <= 65,536
+    CHK(timed(c, BK_K_H2D, [&] {
+        return hipMemcpyAsync(k->b_order.p, ho, ub * un * sizeof(uint16_t), hipMemcpyHostToDevice, st);
+    }));
+    double *dsc = (double *)k->b_scores.p, *ddg = (double *)k->b_diag.p;
+    double *dmean = mean_out ? (double *)k->b_mean.p : nullptr;
+    int64_t *dsel = (int64_t *)k->b_sel.p;
+    for (int64_t b0 = 0; b0 < batch; b0 += W) {
+        const int w = (int)(batch - b0 < W ? batch - b0 : W);
+        const uint64_t spin = c->small_spin_left == 0 ? SMALL_SPIN_MAX : c->small_spin_max;
+        if (c->small_spin_left > 0) --c->small_spin_left;
+        CHK(timed(c, BK_K_SMALL, [&] {
+            return launch_collect_small_batch(
+                k->store.p, k->dtype, k->ld, w, (int)n, d, (int)f, (const double *)k->G.p,
+                (const uint16_t *)k->b_order.p + b0 * n, dsc + b0 * n, ddg + b0 * n, dsel + b0 * m,
+                dmean ? dmean + b0 * d : nullptr, (double *)c->batch_rec.p + b0 * MARGIN_WORDS,
+                (unsigned *)k->b_ctr.p, c->num_cu, st, spin);
+        }));
+    }
+    c->batch_one = 0;
+    c->margin_valid = 1;
+    c->margin_host = c->batch_pick;
+    c->margin_unchecked = 1;
+    c->batch_last = batch;
+    c->batch_fetched = 0;
+    // the records come back with the outputs, under the same wait
+    c->batch_rec_h.resize(ub * MARGIN_WORDS);
+    CHK(timed(c, BK_K_D2H, [&] {
+        hipError_t e = hipMemcpyAsync(c->batch_rec_h.data(), c->batch_rec.p,
+                                      ub * MARGIN_WORDS * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(sel_idx, dsel, ub * (size_t)m * sizeof(int64_t),
+                               hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && scores)
+            e = hipMemcpyAsync(scores, dsc, ub * un * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && mean_out)
+            e = hipMemcpyAsync(mean_out, dmean, ub * (size_t)d * sizeof(double),
+                               hipMemcpyDeviceToHost, st);
+        return e;
+    }));
+    HIPCHK(wait_stream(c));
+    drain.armed = false;
+    batch_pick_record(c);
+    c->margin_unchecked = 0;
+    return margin_status(c->batch_pick);  // an error code wins the pick: a give-up marks them all
+}
+
+// Outside that range, and for one problem: the single finish per problem.  It
+// is synchronous and leaves its record in host memory, so each problem's
+// record is copied behind its finish straight into the host side of the batch
+// record store: no copy to the device and none back
+int finish_batch_loop(bk_ctx *c, Collect *k, const int64_t *orders, int64_t batch, int64_t n,
+                      int64_t f, int64_t *sel_idx, double *scores, double *mean_out) {
+    const int64_t m = n - f;
+    std::vector<double> recs((size_t)batch * MARGIN_WORDS);
+    for (int64_t b = 0; b < batch; ++b) {
+        CHK(finish_checked(c, k, orders + b * n, n, f, sel_idx + b * m, nullptr,
+                           scores ? scores + b * n : nullptr,
+                           mean_out ? mean_out + b * k->d : nullptr));
+        memcpy(recs.data() + (size_t)b * MARGIN_WORDS, c->margin_host,
+               MARGIN_WORDS * sizeof(double));
+    }
+    c->batch_rec_h.swap(recs);
+    c->batch_one = 0;
+    c->batch_last = batch;
+    batch_pick_record(c);
+    c->margin_valid = 1;
+    c->margin_host = c->batch_pick;
+    c->margin_unchecked = 0;  // every finish checked its own record
+    return BK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bk_collect_finish_batch(bk_ctx *c, const int64_t *orders, int64_t batch, int64_t n, int64_t f,
+                            int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
+    // the shape checks first: they need no context, so they work with no GPU present
+    if (batch < 1) return fail(BK_EINVAL, "need batch >= 1 (batch=%lld)", (long long)batch);
+    if (batch > BK_MAX_BATCH)
+        return fail(BK_ENOTSUP, "batch=%lld exceeds BK_MAX_BATCH=%d", (long long)batch, BK_MAX_BATCH);
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!orders) return fail(BK_EINVAL, "null orders");
+    if (!sel_idx) return fail(BK_EINVAL, "null sel_idx");
+    std::lock_guard<std::mutex> lk(c->mu);
+    Collect *k = c->collect;
+    if (!k || !k->begun)
+        return fail(BK_EINVAL, "bk_collect_finish_batch without bk_collect_begin");
+    if (n < 1 || n > k->count)
+        return fail(BK_EINVAL, "bk_collect_finish_batch: n=%lld, %lld rows collected",
+                    (long long)n, (long long)k->count);
+    CHK(bk_check_args(n, k->d, f));
+    {
+        // seen[o] = 1 + the last problem that used slot o
+        std::vector<int64_t> seen((size_t)k->count, 0);
+        for (int64_t b = 0; b < batch; ++b)
+            for (int64_t i = 0; i < n; ++i) {
+                const int64_t o = orders[b * n + i];
+                if (o < 0 || o >= k->count)
+                    return fail(BK_EINVAL,
+                                "problem %lld: order[%lld] = %lld is no collected slot (0..%lld)",
+                                (long long)b, (long long)i, (long long)o, (long long)k->count - 1);
+                if (seen[(size_t)o] == b + 1)
+                    return fail(BK_EINVAL, "problem %lld: order[%lld] = %lld repeats a slot",
+                                (long long)b, (long long)i, (long long)o);
+                seen[(size_t)o] = b + 1;
+            }
+    }
+    DeviceGuard dg(c->device);
+    if (batch > 1 && small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
+        CHK(finish_batch_small(c, k, orders, batch, n, f, sel_idx, scores, mean_out));
+    else
+        CHK(finish_batch_loop(c, k, orders, batch, n, f, sel_idx, scores, mean_out));
+    if (m_out) *m_out = n - f;
     return BK_OK;
 }
 

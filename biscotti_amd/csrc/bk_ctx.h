@@ -321,6 +321,7 @@ int read_margin(bk_ctx *c, double (&mg)[MARGIN_WORDS]);
 int check_margin_readback(bk_ctx *c);
 // bk_batch.hip
 int batch_fetch(bk_ctx *c);
+void batch_pick_record(bk_ctx *c);
 // bk_host.hip
 int stage_host_pipelined(bk_ctx *c, const void *X, int64_t ld, int dtype, const double *noise,
                          int64_t k, int64_t noise_ld, int64_t n, int64_t d, char *dX,

@@ -328,6 +328,20 @@ hipError_t launch_small_batch(const void *X, int dtype, int64_t ld, int64_t stri
                               int64_t part_stride, double *scores, double *diag, int64_t *sel,
                               double *mean, double *margin, unsigned *lines, int num_cu,
                               hipStream_t st, uint64_t spin_max = SMALL_SPIN_MAX);
+// bk_collect_batch.hip, k_collect_small_batch: W finishes of one shape (n, f)
+// over one collection in one launch (problem b's arrival slots at orders +
+// b * n).  Per problem: n scores, n diag, m = n - f sel, d mean (nullable),
+// MARGIN_WORDS of margin, COLLECT_BATCH_LINES queue lines; lines:
+// (COLLECT_BATCH_QLINES + W * COLLECT_BATCH_LINES) * 32 zeroed queue words (the
+// launch's, then each problem's; every launch leaves them zero).  W <=
+// SMALL_BATCH_MAX_W; the slots are the caller's to validate
+constexpr int COLLECT_BATCH_LINES = 13;  // per problem: S arrivals, 8 flag copies, 4 groups
+constexpr int COLLECT_BATCH_QLINES = 2;  // per launch: the item head and the error word
+hipError_t launch_collect_small_batch(const void *store, int dtype, int64_t ld, int W, int n,
+                                      int64_t d, int f, const double *G, const uint16_t *orders,
+                                      double *scores, double *diag, int64_t *sel, double *mean,
+                                      double *margin, unsigned *lines, int num_cu, hipStream_t st,
+                                      uint64_t spin_max = SMALL_SPIN_MAX);
 hipError_t launch_synth(void *X, int dtype, int64_t ld, int64_t n, int64_t dl, int64_t c0,
                         const int64_t *perm, const SynthParams &P, hipStream_t st);
 

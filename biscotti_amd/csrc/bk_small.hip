@@ -42,7 +42,9 @@
 // k_small_batch (bk_small_batch.hip) is the same queue over W independent
 // problems of one shape (bk_multikrum_batch*): per-problem queue lines and partials, one shared item
 // head and error word, the problems' phases software-pipelined; k_tiny_batch is
-// k_tiny with one workgroup per problem.
+// k_tiny with one workgroup per problem.  k_collect_small_batch
+// (bk_collect_batch.hip) is k_collect_small's queue over W orders of one
+// collection (bk_collect_finish_batch).
 #include "bk_small_items.h"
 
 namespace bk {
@@ -156,18 +158,8 @@ struct CollectSmallArgs {
     uint16_t order[128];
 };
 
-// S item i, first half: thread j < n loads G_ij, thread 128 + j loads G_jj
-template <int NB>
-__device__ __forceinline__ void collect_row(const SmallArgs &a, const double *G,
-                                            const uint16_t *ord, int i, int tid, double *gv) {
-    const int j = tid & 127;
-    if (tid < 256 && j < a.n) {
-        const int64_t oj = ord[j], oi = tid < 128 ? (int64_t)ord[i] : oj;
-        const int64_t hi = oi > oj ? oi : oj, lo = oi > oj ? oj : oi;
-        gv[(tid < 128 ? 0 : 16 * NB) + j] = G[hi * (hi + 1) / 2 + lo];
-    }
-    __syncthreads();
-}
+// (collect_row, the S item's first half, is bk_small_items.h's: shared with
+// k_collect_small_batch, bk_collect_batch.hip)
 
 // Items 0..n-1 are the S items (the first min(n, grid) of them held by
 // blockIdx: they wait for nothing), items n.. the M items (always dequeued;

@@ -1,9 +1,10 @@
 // bk_small_items.h -- the work items of the one-launch small path, shared by
-// the kernels of bk_small.hip (k_small, k_collect_small, k_tiny) and of
-// bk_small_batch.hip (k_small_batch, k_tiny_batch): the queue words, the
-// write-through hand-off (arrive / raise / wait), the G, S and M item bodies,
-// the last workgroup's reset and k_tiny's body.  bk_small.hip's header comment
-// describes the queue.  Private to those two files.
+// the kernels of bk_small.hip (k_small, k_collect_small, k_tiny), of
+// bk_small_batch.hip (k_small_batch, k_tiny_batch) and of bk_collect_batch.hip
+// (k_collect_small_batch): the queue words, the write-through hand-off (arrive
+// / raise / wait), the G, S and M item bodies, the last workgroup's reset and
+// k_tiny's body.  bk_small.hip's header comment describes the queue.  Private
+// to those three files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -495,6 +496,22 @@ __device__ __forceinline__ void small_rank_sum(const SmallArgs &a, int i, int ti
         st1(a.scores + i, k > 0 ? sum : 0.0);
         st1(a.diag + i, di);
     }
+}
+
+// S item i of a collection finish, first half (k_collect_small,
+// k_collect_small_batch): the Gram exists already, by arrival slot, lower
+// packed (G[h (h + 1) / 2 + l], l <= h), and the caller's row r sits at slot
+// ord[r].  Thread j < n loads G_ij, thread 128 + j loads G_jj
+template <int NB>
+__device__ __forceinline__ void collect_row(const SmallArgs &a, const double *G,
+                                            const uint16_t *ord, int i, int tid, double *gv) {
+    const int j = tid & 127;
+    if (tid < 256 && j < a.n) {
+        const int64_t oj = ord[j], oi = tid < 128 ? (int64_t)ord[i] : oj;
+        const int64_t hi = oi > oj ? oi : oj, lo = oi > oj ? oj : oi;
+        gv[(tid < 128 ? 0 : 16 * NB) + j] = G[hi * (hi + 1) / 2 + lo];
+    }
+    __syncthreads();
 }
 
 // S item i: row i with the whole workgroup, straight from the G items'

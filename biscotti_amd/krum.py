@@ -277,6 +277,39 @@ class Engine:
         assert mo.value == m
         return sel, sc, mean
 
+    def collect_finish_batch(self, orders, f, want_scores=True, want_mean=True):
+        """B finishes over the one collection in one call (bk_collect_finish_batch):
+        orders is a (B, n) integer array, row b the arrival slots of problem
+        b's rows (a subset and any permutation), all with the same n and f.
+        Returns sel (B, n - f) int64, scores (B, n) or None, mean (B, d) or
+        None, shaped as multikrum_batch's; problem b's are bitwise
+        collect_finish(order=orders[b], f=f)'s."""
+        orders = np.asarray(orders)
+        if orders.ndim != 2:
+            raise ValueError("orders must be 2-D (B problems x n arrival slots)")
+        if orders.dtype.kind not in "iu":
+            raise ValueError("orders must be an integer array")
+        if getattr(self, "_collect", None) is None:
+            raise ValueError("collect_finish_batch without collect_begin")
+        orders = np.ascontiguousarray(orders, dtype=np.int64)
+        B, n = orders.shape
+        if B < 1:
+            raise ValueError("need at least one problem (B=%d)" % B)
+        _, d = self._collect
+        f = int(f)
+        check(lib().bk_check_args(n, d, f))
+        m = n - f
+        sel = np.empty((B, m), dtype=np.int64)
+        mo = ctypes.c_int64(0)
+        sc = np.empty((B, n), dtype=np.float64) if want_scores else None
+        mean = np.empty((B, d), dtype=np.float64) if want_mean else None
+        check(lib().bk_collect_finish_batch(self._ctx, orders.ctypes.data, B, n, f, sel.ctypes.data,
+                                            ctypes.addressof(mo),
+                                            sc.ctypes.data if sc is not None else None,
+                                            mean.ctypes.data if mean is not None else None))
+        assert mo.value == m
+        return sel, sc, mean
+
     # ---- host entry with the noise applied in the H2D staging -----------
     #      (bk_multikrum_noised, SURVEY.md §8(f) row 3) -------------------
     def multikrum_noised(self, delta, noise, f, want_scores=True, want_mean=True,

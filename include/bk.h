@@ -232,6 +232,47 @@ int bk_multikrum_batch(bk_ctx *ctx, const void *X, int where, int dtype, int64_t
  * bk_selection_margin_record, one per problem); batch must be that call's */
 int bk_selection_margin_batch(bk_ctx *ctx, double *records, int64_t batch);
 
+/* ---- many finishes over one collection in one call --------------------------
+ * `batch` finishes over ONE collection in one call: problem b is Multi-Krum
+ * over the n collected rows orders[b*n .. b*n+n) (arrival slots; a subset and
+ * any permutation, as bk_collect_finish's order), all with the same n and f --
+ * the resampled verdicts of sampleUpdates (krum.go:368-388), leave-one-out, a
+ * deadline subset against the full set, a bootstrap vote per peer.  Host
+ * pointers, synchronous, on the context stream under the context mutex; does
+ * not consume the collection.  Outputs are per problem: sel_idx batch x (n-f)
+ * (the caller's row indices 0..n-1 of that problem, ascending), *m_out = n-f,
+ * scores batch x n (nullable), mean_out batch x d (nullable).
+ * Every output of problem b -- sel, scores, mean and all eight margin fields --
+ * is BITWISE what bk_collect_finish(ctx, orders + b*n, n, f, ...) gives on the
+ * same collection under the same context settings.  Within the one-launch
+ * range (n <= 128, d <= 32,768, the small path on) and for batch >= 2 the
+ * problems share launches: k_collect_small_batch runs k_collect_small's work
+ * items of up to 1,024 problems from one queue, reading the collection's Gram
+ * and row store through each problem's order -- no Gram work, and nothing
+ * uploaded but the batch x n slot numbers; a larger batch runs as consecutive
+ * launches.  Any other shape, bk_set_small_path(ctx, 0) and batch = 1 run the
+ * single finish once per problem.  Its buffers are its own: a bk_collect_finish,
+ * bk_multikrum* or bk_multikrum_batch* between two calls is unaffected and
+ * affects nothing here; a bk_collect_begin that regrows the collection and
+ * bk_destroy release them.
+ * A hand-off give-up in any problem of a launch invalidates the launch: every
+ * sel_idx entry of its problems is -1 and the call returns BK_EHIP.
+ * Afterwards bk_selection_margin / _record / _batch behave as after
+ * bk_multikrum_batch: a record with an error code wins, else the lowest-index
+ * problem with near_tie = 1, else the problem with the smallest gap -
+ * err_bound; bk_selection_margin_batch gives them all.
+ * The shape checks come first and need no GPU and no collection: batch < 1 is
+ * BK_EINVAL, batch > BK_MAX_BATCH is BK_ENOTSUP.  Then, in this order,
+ * BK_EINVAL for: a null ctx, orders or sel_idx; a call without
+ * bk_collect_begin; n outside 1..count; f outside bk_check_args; an
+ * out-of-range or repeated slot in any problem (the message names the problem
+ * and the position).  Every error leaves the collection, and the last valid
+ * margin state, as they were. */
+int bk_collect_finish_batch(bk_ctx *ctx, const int64_t *orders, int64_t batch, int64_t n,
+                            int64_t f, int64_t *sel_idx /* batch x (n-f) */, int64_t *m_out,
+                            double *scores /* batch x n, nullable */,
+                            double *mean_out /* batch x d, nullable */);
+
 /* Small batches (n <= 128, d <= 32768: Biscotti's deployed shapes, configs A
  * and B) run as ONE launch,
  * k_small: split-K Gram, reduce, scores, selection and mean pulled as work
