@@ -105,6 +105,8 @@ SIGNATURES = {
                                 _p]),
     "bk_selection_margin_batch": (_i, [_p, _pd, _i64]),
     "bk_collect_finish_batch": (_i, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "bk_collect_finish_ragged": (_i, [_p, _p, _p, _p, _i64, _p, _p, _p, _p]),
+    "bk_ragged_queue_item": (_i, [_p, _i, _i, _i64, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
 }
 
 _lib = None

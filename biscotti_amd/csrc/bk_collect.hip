@@ -17,7 +17,9 @@
 // A finish of n <= 128 rows, d <= 32,768 (small_ok) takes none of the last two
 // nor K2..K4: one k_collect_small launch (bk_small.hip) does it all, and
 // bk_collect_finish_batch runs many such finishes over the one collection as
-// k_collect_small_batch launches (bk_collect_batch.hip).
+// k_collect_small_batch launches (bk_collect_batch.hip), and
+// bk_collect_finish_ragged, where every problem has its own n and f, as
+// k_collect_small_ragged launches (bk_collect_ragged.hip).
 // Every element of G is the same sum whatever the add's count and however many
 // rows are resident: chunk s covers the same columns, one wave sums a chunk's
 // products in lane order and the chunks are added in the same tree, so the
@@ -230,11 +232,14 @@ struct Collect {
     int64_t n_cap = 0, d = 0, ld = 0, count = 0;
     int S = 0;  // chunks of a row: ceil(d es / BORDER_CHUNK_BYTES)
     Buf store, G, P, U, sel, slots, scores, mean, mean_part, order, horder, ring;
-    // bk_collect_finish_batch: buffers of its own (a single finish or any
-    // bk_multikrum* between two batched finishes touches none of them): the
-    // 16-bit orders and their pinned staging, per-problem scores, diag, sel and
-    // mean, and the queue lines (zeroed at allocation; every launch leaves
-    // them zero).  The records go to the context's batch record store
+    // bk_collect_finish_batch and bk_collect_finish_ragged: buffers of their
+    // own (a single finish or any bk_multikrum* between two such finishes
+    // touches none of them; both entries are synchronous, so neither finds the
+    // other's work in them): the 16-bit orders (the ragged entry: descriptors,
+    // segment starts, then the orders) and their pinned staging, per-problem
+    // scores, diag, sel and mean, and the queue lines (zeroed at allocation;
+    // every launch leaves them zero).  The records go to the context's batch
+    // record store
     Buf b_order, b_horder, b_scores, b_diag, b_sel, b_mean, b_ctr;
     hipEvent_t ev_slot[RING_SLOTS] = {};
     bool slot_used[RING_SLOTS] = {};
@@ -741,6 +746,250 @@ int bk_collect_finish_batch(bk_ctx *c, const int64_t *orders, int64_t batch, int
     else
         CHK(finish_batch_loop(c, k, orders, batch, n, f, sel_idx, scores, mean_out));
     if (m_out) *m_out = n - f;
+    return BK_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// bk_collect_finish_ragged past its checks.  The problems within
+// k_collect_small's range go by NB = ceil(n_b / 16) into buckets, and each
+// bucket of two or more runs as k_collect_small_ragged<T, NB> launches of W <=
+// SMALL_BATCH_MAX_W problems (bk_collect_ragged.hip): small_rank_sum<NB>,
+// collect_row<NB> and small_mean<NB> take their summation shapes from NB and
+// the single finish launches with the problem's own NB, so only the same
+// instantiation gives the single finish's bits.  The descriptors, the launches'
+// segment starts and the 16-bit slots go up in ONE copy from pinned staging;
+// the kernel writes every output at its caller-order position in device arrays
+// shaped like the caller's, which come back whole after the last launch.  Every
+// other problem, and a bucket's only one, then runs the single finish straight
+// into the caller's arrays, its record into the host side of the batch record
+// store at the caller's index (finish_batch_loop).  The buffers are the batched
+// finish's (both entries are synchronous and leave the lines zero).
+int finish_ragged(bk_ctx *c, Collect *k, const int64_t *orders, const int64_t *offsets,
+                  const int64_t *fs, int64_t batch, int64_t *sel_idx, int64_t *m_out,
+                  double *scores, double *mean_out) {
+    const int64_t d = k->d;
+    const hipStream_t st = c->stream;
+    const size_t ub = (size_t)batch;
+    std::vector<int64_t> selo(ub + 1, 0);  // problem b's sel at sum_{c<b} m_c
+    for (int64_t b = 0; b < batch; ++b)
+        selo[(size_t)b + 1] = selo[(size_t)b] + (offsets[b + 1] - offsets[b]) - fs[b];
+    std::vector<int64_t> bucket[9], single;
+    for (int64_t b = 0; b < batch; ++b) {
+        const int64_t n = offsets[b + 1] - offsets[b];
+        if (small_ok(c, k->store.p, k->dtype, n, d, k->ld))
+            bucket[(n + 15) / 16].push_back(b);
+        else
+            single.push_back(b);
+    }
+    struct Launch {
+        int NB, W;
+        size_t first, seg;  // its first descriptor; its segment starts (in int32s)
+    };
+    std::vector<Launch> launches;
+    std::vector<int64_t> kern;  // the kernel's problems, in launch order
+    size_t nseg = 0, nslots = 0;
+    int maxW = 0;
+    for (int NB = 1; NB <= 8; ++NB) {
+        const std::vector<int64_t> &bk = bucket[NB];
+        if (bk.size() == 1) single.push_back(bk[0]);
+        if (bk.size() < 2) continue;
+        for (size_t b0 = 0; b0 < bk.size(); b0 += SMALL_BATCH_MAX_W) {
+            const int w = (int)(bk.size() - b0 < (size_t)SMALL_BATCH_MAX_W ? bk.size() - b0
+                                                                           : SMALL_BATCH_MAX_W);
+            launches.push_back({NB, w, kern.size(), nseg});
+            nseg += (size_t)w + 2;
+            if (w > maxW) maxW = w;
+            for (int q = 0; q < w; ++q) {
+                kern.push_back(bk[b0 + q]);
+                nslots += (size_t)(offsets[bk[b0 + q] + 1] - offsets[bk[b0 + q]]);
+            }
+        }
+    }
+    std::vector<double> recs(ub * MARGIN_WORDS);
+    if (!launches.empty()) {
+        const int C = mean_out ? (int)((d + 63) / 64) : 1;
+        // the staging block: descriptors | segment starts | 16-bit slots
+        const size_t off_seg = up16(kern.size() * sizeof(RaggedDesc));
+        const size_t off_ord = up16(off_seg + nseg * sizeof(int32_t));
+        const size_t sbytes = off_ord + nslots * sizeof(uint16_t);
+        const size_t lbytes =
+            (size_t)(COLLECT_BATCH_QLINES + maxW * COLLECT_BATCH_LINES) * 32 * sizeof(unsigned);
+        const bool new_lines = lbytes > k->b_ctr.bytes;
+        // (every user of these buffers is synchronous: none is in use when it grows)
+        CHK(grow_all({{&k->b_order, sbytes},
+                      {&k->b_horder, sbytes},
+                      {&k->b_scores, (size_t)offsets[batch] * sizeof(double)},
+                      {&k->b_diag, (size_t)offsets[batch] * sizeof(double)},
+                      {&k->b_sel, (size_t)selo[ub] * sizeof(int64_t)},
+                      {&k->b_mean, mean_out ? ub * (size_t)d * sizeof(double) : 0},
+                      {&k->b_ctr, lbytes}},
+                     "bk_collect_finish_ragged"));
+        CHK(ensure(c->batch_rec, ub * MARGIN_WORDS * sizeof(double)));
+        if (new_lines) HIPCHK(hipMemsetAsync(k->b_ctr.p, 0, k->b_ctr.bytes, st));
+        Drain drain{st};
+        char *hs = (char *)k->b_horder.p;
+        RaggedDesc *hd = (RaggedDesc *)hs;
+        int32_t *hseg = (int32_t *)(hs + off_seg);
+        uint16_t *ho = (uint16_t *)(hs + off_ord);
+        std::vector<int> lead(launches.size());
+        {
+            int64_t at = 0;  // the slots packed in launch order
+            int32_t nn[SMALL_BATCH_MAX_W];
+            for (size_t l = 0; l < launches.size(); ++l) {
+                const Launch &L = launches[l];
+                for (int q = 0; q < L.W; ++q) {
+                    const int64_t b = kern[L.first + q], n = offsets[b + 1] - offsets[b];
+                    RaggedDesc &r = hd[L.first + q];
+                    r.n = nn[q] = (int32_t)n;
+                    r.f = (int32_t)fs[b];
+                    r.m = (int32_t)(n - fs[b]);
+                    r.idx = (int32_t)b;
+                    r.ord = at;
+                    r.sc = offsets[b];
+                    r.so = selo[(size_t)b];
+                    for (int64_t i = 0; i < n; ++i)  // validated: < count <= 65,536
+                        ho[at + i] = (uint16_t)orders[offsets[b] + i];
+                    at += n;
+                }
+                ragged_seg_build(nn, L.W, C, hseg + L.seg);
+                lead[l] = L.W > 1 ? hseg[L.seg + 2] - C : hseg[L.seg + 1];
+            }
+        }
+        CHK(timed(c, BK_K_H2D, [&] {
+            return hipMemcpyAsync(k->b_order.p, hs, sbytes, hipMemcpyHostToDevice, st);
+        }));
+        const char *ds = (const char *)k->b_order.p;
+        double *dsc = (double *)k->b_scores.p, *ddg = (double *)k->b_diag.p;
+        double *dmean = mean_out ? (double *)k->b_mean.p : nullptr;
+        int64_t *dsel = (int64_t *)k->b_sel.p;
+        for (size_t l = 0; l < launches.size(); ++l) {
+            const Launch &L = launches[l];
+            const uint64_t spin = c->small_spin_left == 0 ? SMALL_SPIN_MAX : c->small_spin_max;
+            if (c->small_spin_left > 0) --c->small_spin_left;
+            CHK(timed(c, BK_K_SMALL, [&] {
+                return launch_collect_small_ragged(
+                    k->store.p, k->dtype, k->ld, L.W, L.NB, d, (const double *)k->G.p,
+                    (const RaggedDesc *)ds + L.first, (const int32_t *)(ds + off_seg) + L.seg,
+                    hseg[L.seg + L.W + 1], lead[l], (const uint16_t *)(ds + off_ord), dsc, ddg,
+                    dsel, dmean, (double *)c->batch_rec.p, (unsigned *)k->b_ctr.p, c->num_cu, st,
+                    spin);
+            }));
+        }
+        // whole arrays, as the uniform entry's: the single finishes below fill
+        // their own positions afterwards
+        CHK(timed(c, BK_K_D2H, [&] {
+            hipError_t e = hipMemcpyAsync(recs.data(), c->batch_rec.p,
+                                          ub * MARGIN_WORDS * sizeof(double), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(sel_idx, dsel, (size_t)selo[ub] * sizeof(int64_t),
+                                   hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess && scores)
+                e = hipMemcpyAsync(scores, dsc, (size_t)offsets[batch] * sizeof(double),
+                                   hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess && mean_out)
+                e = hipMemcpyAsync(mean_out, dmean, ub * (size_t)d * sizeof(double),
+                                   hipMemcpyDeviceToHost, st);
+            return e;
+        }));
+        HIPCHK(wait_stream(c));
+        drain.armed = false;
+    }
+    for (const int64_t b : single) {
+        CHK(finish_checked(c, k, orders + offsets[b], offsets[b + 1] - offsets[b], fs[b],
+                           sel_idx + selo[(size_t)b], nullptr, scores ? scores + offsets[b] : nullptr,
+                           mean_out ? mean_out + b * d : nullptr));
+        memcpy(recs.data() + (size_t)b * MARGIN_WORDS, c->margin_host,
+               MARGIN_WORDS * sizeof(double));
+    }
+    if (m_out)
+        for (int64_t b = 0; b < batch; ++b) m_out[b] = offsets[b + 1] - offsets[b] - fs[b];
+    c->batch_rec_h.swap(recs);
+    c->batch_one = 0;
+    c->batch_last = batch;
+    batch_pick_record(c);
+    c->margin_valid = 1;
+    c->margin_host = c->batch_pick;
+    c->margin_unchecked = 0;
+    return margin_status(c->batch_pick);  // an error code wins the pick: a give-up marks them all
+}
+
+}  // namespace
+
+extern "C" {
+
+int bk_collect_finish_ragged(bk_ctx *c, const int64_t *orders, const int64_t *offsets,
+                             const int64_t *fs, int64_t batch, int64_t *sel_idx, int64_t *m_out,
+                             double *scores, double *mean_out) {
+    // the shape checks first: they need no context, so they work with no GPU present
+    if (batch < 1) return fail(BK_EINVAL, "need batch >= 1 (batch=%lld)", (long long)batch);
+    if (batch > BK_MAX_BATCH)
+        return fail(BK_ENOTSUP, "batch=%lld exceeds BK_MAX_BATCH=%d", (long long)batch, BK_MAX_BATCH);
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!orders) return fail(BK_EINVAL, "null orders");
+    if (!offsets) return fail(BK_EINVAL, "null offsets");
+    if (!fs) return fail(BK_EINVAL, "null fs");
+    if (!sel_idx) return fail(BK_EINVAL, "null sel_idx");
+    std::lock_guard<std::mutex> lk(c->mu);
+    Collect *k = c->collect;
+    if (!k || !k->begun)
+        return fail(BK_EINVAL, "bk_collect_finish_ragged without bk_collect_begin");
+    if (offsets[0] != 0)
+        return fail(BK_EINVAL, "bk_collect_finish_ragged: offsets[0] = %lld, not 0",
+                    (long long)offsets[0]);
+    for (int64_t b = 0; b < batch; ++b) {
+        const int64_t lo = offsets[b], hi = offsets[b + 1];  // lo >= 0: every offset before passed
+        if (hi <= lo || (uint64_t)hi - (uint64_t)lo > (uint64_t)k->count)
+            return fail(BK_EINVAL,
+                        "problem %lld: n = offsets[%lld] - offsets[%lld] = %lld, %lld rows collected",
+                        (long long)b, (long long)b + 1, (long long)b,
+                        (long long)((uint64_t)hi - (uint64_t)lo), (long long)k->count);
+    }
+    for (int64_t b = 0; b < batch; ++b) {
+        const int st = bk_check_args(offsets[b + 1] - offsets[b], k->d, fs[b]);
+        if (st != BK_OK) {
+            const std::string why = g_err;
+            return fail(st, "problem %lld: %s", (long long)b, why.c_str());
+        }
+    }
+    {
+        // seen[o] = 1 + the last problem that used slot o
+        std::vector<int64_t> seen((size_t)k->count, 0);
+        for (int64_t b = 0; b < batch; ++b) {
+            const int64_t n = offsets[b + 1] - offsets[b];
+            for (int64_t i = 0; i < n; ++i) {
+                const int64_t o = orders[offsets[b] + i];
+                if (o < 0 || o >= k->count)
+                    return fail(BK_EINVAL,
+                                "problem %lld: order[%lld] = %lld is no collected slot (0..%lld)",
+                                (long long)b, (long long)i, (long long)o, (long long)k->count - 1);
+                if (seen[(size_t)o] == b + 1)
+                    return fail(BK_EINVAL, "problem %lld: order[%lld] = %lld repeats a slot",
+                                (long long)b, (long long)i, (long long)o);
+                seen[(size_t)o] = b + 1;
+            }
+        }
+    }
+    DeviceGuard dg(c->device);
+    return finish_ragged(c, k, orders, offsets, fs, batch, sel_idx, m_out, scores, mean_out);
+}
+
+int bk_ragged_queue_item(const int32_t *n, int W, int C, int64_t item, int *p, int *it) {
+    if (!n || !p || !it) return fail(BK_EINVAL, "null n / p / it");
+    if (W < 1 || W > SMALL_BATCH_MAX_W || C < 1)
+        return fail(BK_EINVAL, "need 1 <= W <= %d and C >= 1 (W=%d C=%d)", SMALL_BATCH_MAX_W, W, C);
+    for (int j = 0; j < W; ++j)
+        if (n[j] < 1 || n[j] > 128) return fail(BK_EINVAL, "n[%d] = %d outside 1..128", j, (int)n[j]);
+    std::vector<int32_t> seg((size_t)W + 2);
+    ragged_seg_build(n, W, C, seg.data());
+    if (item < 0 || item >= seg[(size_t)W + 1])
+        return fail(BK_EINVAL, "item %lld outside the queue (0..%d)", (long long)item,
+                    (int)seg[(size_t)W + 1] - 1);
+    ragged_queue_decode(seg.data(), W, C, (int)item, *p, *it);
     return BK_OK;
 }
 

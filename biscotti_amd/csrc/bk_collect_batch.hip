@@ -11,14 +11,6 @@
 
 namespace bk {
 
-// Per-problem queue lines (128 B each, word 0 only): the S phase's top arrival
-// counter, its flag once per XCD, the arrival counters of groups of 32 S items
-// -- what wg_arrive / wg_raise / wg_wait_flag_on take as (top, flag, grp).  The
-// launch's own lines: the item head and the error word.
-enum { CB_S = 0, CB_F = 1, CB_GRP = 9, CB_LINES = COLLECT_BATCH_LINES };
-enum { CBQ_HEAD = 0, CBQ_ERR = 1, CBQ_LINES = COLLECT_BATCH_QLINES };
-static_assert(CB_GRP + 128 / 32 == CB_LINES, "8 flag copies, 4 groups of 32 S items");
-
 // k_collect_small_batch: the S and M items of W problems of one shape (n, f)
 // over one collection.  Problem p's view: its own 16-bit order (row p of a
 // device array W x n), scores, diag, sel, mean, margin record and queue lines;

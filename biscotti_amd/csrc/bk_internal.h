@@ -342,6 +342,61 @@ hipError_t launch_collect_small_batch(const void *store, int dtype, int64_t ld, 
                                       double *scores, double *diag, int64_t *sel, double *mean,
                                       double *margin, unsigned *lines, int num_cu, hipStream_t st,
                                       uint64_t spin_max = SMALL_SPIN_MAX);
+// bk_collect_ragged.hip, k_collect_small_ragged: W finishes over one collection
+// in one launch, each with its own n and f, all of one NB = ceil(n / 16) (the
+// item bodies pick their summation shapes from NB, and the single finish runs
+// the same NB: the bitwise contract).  Problem p of the launch is desc[p]: its
+// arrival slots at orders + ord, its scores and diag at scores / diag + sc, its
+// sel at sel + so, its mean (nullable) at mean + idx * d and its record at
+// margin + idx * MARGIN_WORDS -- the caller's positions, so the launches of one
+// call fill one set of arrays.  seg: the W + 2 segment starts of the queue
+// (ragged_seg_build).  lines: as launch_collect_small_batch's
+struct RaggedDesc {
+    int32_t n, f, m, idx;   // rows, Byzantine bound, m = n - f; the problem's index in the caller's order
+    int64_t ord, sc, so;    // offsets: the 16-bit slots, scores / diag, sel
+};
+// The queue of k_collect_small_ragged, a lag-one pipeline over W problems of
+// n[p] S items and C M items each:
+//   S_0 | S_1 M_0 | S_2 M_1 | ... | S_{W-1} M_{W-2} | M_{W-1}
+// segment 0 has n[0] items, segment j (1 <= j < W) has n[j] + C, segment W has
+// C; seg[0 .. W + 1] are the segments' starts and the total.
+__host__ __device__ inline void ragged_seg_build(const int32_t *n, int W, int C, int32_t *seg) {
+    seg[0] = 0;
+    seg[1] = n[0];
+    for (int j = 1; j < W; ++j) seg[j + 1] = seg[j] + n[j] + C;
+    seg[W + 1] = seg[W] + C;
+}
+// queue position item (0 <= item < seg[W + 1]) -> problem p and k_collect_small's
+// item number it of that problem (it < n[p]: S item it; else M item it - n[p]).
+// A binary search over the W + 1 segments: <= 11 steps at W = 1,024
+__host__ __device__ inline void ragged_queue_decode(const int32_t *seg, int W, int C, int item,
+                                                    int &p, int &it) {
+    int lo = 0, hi = W + 1;  // seg[lo] <= item < seg[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (seg[mid] <= item)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const int q = item - seg[lo];
+    // rows of the problem whose S items open segment j (j < W)
+    const int nj = lo == 0 ? seg[1] : lo < W ? seg[lo + 1] - seg[lo] - C : 0;
+    if (lo < W && q < nj) {
+        p = lo;
+        it = q;
+    } else {  // an M item of the problem before: behind its n[lo - 1] S items
+        p = lo - 1;
+        it = (lo == 1 ? seg[1] : seg[lo] - seg[lo - 1] - C) + (q - nj);
+    }
+}
+hipError_t launch_collect_small_ragged(const void *store, int dtype, int64_t ld, int W, int NB,
+                                       int64_t d, const double *G, const RaggedDesc *desc,
+                                       const int32_t *seg, int total, int lead,
+                                       const uint16_t *orders, double *scores, double *diag,
+                                       int64_t *sel, double *mean, double *margin, unsigned *lines,
+                                       int num_cu, hipStream_t st,
+                                       uint64_t spin_max = SMALL_SPIN_MAX);
 hipError_t launch_synth(void *X, int dtype, int64_t ld, int64_t n, int64_t dl, int64_t c0,
                         const int64_t *perm, const SynthParams &P, hipStream_t st);
 

@@ -1,10 +1,11 @@
 // bk_small_items.h -- the work items of the one-launch small path, shared by
 // the kernels of bk_small.hip (k_small, k_collect_small, k_tiny), of
-// bk_small_batch.hip (k_small_batch, k_tiny_batch) and of bk_collect_batch.hip
-// (k_collect_small_batch): the queue words, the write-through hand-off (arrive
-// / raise / wait), the G, S and M item bodies, the last workgroup's reset and
-// k_tiny's body.  bk_small.hip's header comment describes the queue.  Private
-// to those three files.
+// bk_small_batch.hip (k_small_batch, k_tiny_batch), of bk_collect_batch.hip
+// (k_collect_small_batch) and of bk_collect_ragged.hip (k_collect_small_ragged):
+// the queue words, the write-through hand-off (arrive / raise / wait), the G, S
+// and M item bodies, the last workgroup's reset and k_tiny's body.
+// bk_small.hip's header comment describes the queue.  Private to those four
+// files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -182,6 +183,16 @@ __device__ __forceinline__ void wg_raise(unsigned *ctr, int flag) {
     __syncthreads();
     if (threadIdx.x < 8) st1(cline(ctr, flag + (int)threadIdx.x), 1u);
 }
+
+// k_collect_small_batch and k_collect_small_ragged (bk_collect_batch.hip,
+// bk_collect_ragged.hip):
+// Per-problem queue lines (128 B each, word 0 only): the S phase's top arrival
+// counter, its flag once per XCD, the arrival counters of groups of 32 S items
+// -- what wg_arrive / wg_raise / wg_wait_flag_on take as (top, flag, grp).  The
+// launch's own lines: the item head and the error word.
+enum { CB_S = 0, CB_F = 1, CB_GRP = 9, CB_LINES = COLLECT_BATCH_LINES };
+enum { CBQ_HEAD = 0, CBQ_ERR = 1, CBQ_LINES = COLLECT_BATCH_QLINES };
+static_assert(CB_GRP + 128 / 32 == CB_LINES, "8 flag copies, 4 groups of 32 S items");
 
 // upper 16x16 block b (row-major over bi <= bj) of an NB x NB block grid
 __host__ __device__ constexpr int blk_bi(int b, int NB) {

@@ -310,6 +310,54 @@ class Engine:
         assert mo.value == m
         return sel, sc, mean
 
+    def collect_finish_ragged(self, orders, fs, want_scores=True, want_mean=True):
+        """B finishes over the one collection in one call, each with its own n
+        and f (bk_collect_finish_ragged): orders is a sequence of 1-D integer
+        arrays, element b the arrival slots of problem b's rows; fs an int (the
+        same f for all) or a sequence of B of them.  Returns (sels, scores,
+        mean): sels a list of int64 arrays, scores a list of float64 arrays or
+        None, mean (B, d) or None; problem b's are bitwise
+        collect_finish(order=orders[b], f=fs[b])'s."""
+        if isinstance(orders, np.ndarray) and orders.ndim < 2:
+            raise ValueError("orders must be a sequence of 1-D integer arrays, one per problem")
+        orders = [np.asarray(o) for o in orders]
+        if not orders:
+            raise ValueError("need at least one problem")
+        for b, o in enumerate(orders):
+            if o.ndim != 1:
+                raise ValueError("orders[%d] must be 1-D (its arrival slots)" % b)
+            if o.dtype.kind not in "iu":
+                raise ValueError("orders[%d] must be an integer array" % b)
+        B = len(orders)
+        if np.ndim(fs) == 0:
+            fs = [int(fs)] * B
+        fs = np.ascontiguousarray(fs, dtype=np.int64)
+        if fs.ndim != 1 or fs.shape[0] != B:
+            raise ValueError("fs must be an int or one f per problem (%d problems)" % B)
+        if getattr(self, "_collect", None) is None:
+            raise ValueError("collect_finish_ragged without collect_begin")
+        _, d = self._collect
+        ns = np.array([len(o) for o in orders], dtype=np.int64)
+        offsets = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(ns, out=offsets[1:])
+        packed = np.ascontiguousarray(np.concatenate(orders), dtype=np.int64)
+        # room for every problem even where a check below would refuse the call
+        ms = np.maximum(ns - fs, 0)
+        sel = np.empty(max(int(ms.sum()), 1), dtype=np.int64)
+        mo = np.zeros(B, dtype=np.int64)
+        sc = np.empty(max(int(offsets[B]), 1), dtype=np.float64) if want_scores else None
+        mean = np.empty((B, d), dtype=np.float64) if want_mean else None
+        check(lib().bk_collect_finish_ragged(self._ctx, packed.ctypes.data, offsets.ctypes.data,
+                                             fs.ctypes.data, B, sel.ctypes.data, mo.ctypes.data,
+                                             sc.ctypes.data if sc is not None else None,
+                                             mean.ctypes.data if mean is not None else None))
+        assert np.array_equal(mo, ns - fs)
+        so = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(mo, out=so[1:])
+        sels = [sel[so[b]:so[b + 1]].copy() for b in range(B)]
+        scs = [sc[offsets[b]:offsets[b + 1]].copy() for b in range(B)] if want_scores else None
+        return sels, scs, mean
+
     # ---- host entry with the noise applied in the H2D staging -----------
     #      (bk_multikrum_noised, SURVEY.md §8(f) row 3) -------------------
     def multikrum_noised(self, delta, noise, f, want_scores=True, want_mean=True,

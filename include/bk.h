@@ -267,11 +267,64 @@ int bk_selection_margin_batch(bk_ctx *ctx, double *records, int64_t batch);
  * bk_collect_begin; n outside 1..count; f outside bk_check_args; an
  * out-of-range or repeated slot in any problem (the message names the problem
  * and the position).  Every error leaves the collection, and the last valid
- * margin state, as they were. */
+ * margin state, as they were.
+ * Problems that differ in n or f go to bk_collect_finish_ragged in one call. */
 int bk_collect_finish_batch(bk_ctx *ctx, const int64_t *orders, int64_t batch, int64_t n,
                             int64_t f, int64_t *sel_idx /* batch x (n-f) */, int64_t *m_out,
                             double *scores /* batch x n, nullable */,
                             double *mean_out /* batch x d, nullable */);
+
+/* ---- many finishes over one collection, each with its own n and f -----------
+ * bk_collect_finish_batch with a row count n_b and an f_b PER PROBLEM: the
+ * deadline subset (krum.go:178-224) next to the full set, an f sweep over the
+ * same rows (krum.go:110 fixes f = 0.5 n), the deadline's verdict after each
+ * arrival (the prefixes j = 2..n), leave-k-out for several k, sampleUpdates at
+ * several NUM_SAMPLES -- one call, not one per distinct (n, f).
+ * Problem b is Multi-Krum with f = fs[b] over the n_b = offsets[b+1] -
+ * offsets[b] collected rows orders[offsets[b] .. offsets[b+1]) (arrival slots:
+ * a subset and any permutation); offsets has batch + 1 entries, offsets[0] = 0.
+ * Host pointers, synchronous, on the context stream under the context mutex;
+ * does not consume the collection.  The outputs are packed in the caller's
+ * problem order: problem b's m_b = n_b - f_b selected indices (its own row
+ * indices 0..n_b-1, ascending) at sel_idx + sum_{c<b} m_c, m_out[b] = m_b
+ * (nullable, batch entries), its n_b scores at scores + offsets[b] (nullable),
+ * its mean at mean_out + b*d (nullable, batch x d).
+ * Every output of problem b -- sel, scores, mean and all eight margin fields --
+ * is BITWISE what bk_collect_finish(ctx, orders + offsets[b], n_b, fs[b], ...)
+ * gives on the same collection under the same context settings.  Problems
+ * within the one-launch range (n_b <= 128, d <= 32,768, the small path on) are
+ * grouped by ceil(n_b / 16) -- the single finish picks its summation shapes by
+ * that number, so only problems that agree in it may share a launch -- and
+ * each group of two or more runs as k_collect_small_ragged launches of up to
+ * 1,024 problems: k_collect_small's work items behind a per-problem descriptor,
+ * every output written at the caller's position.  Every other problem, and a
+ * group's only one, runs the single finish; a call may mix both.  Its buffers
+ * are bk_collect_finish_batch's, with their life-cycle: nothing between two
+ * calls (a single or a batched finish, bk_multikrum*, bk_collect_add) affects
+ * them or is affected.
+ * A hand-off give-up in a launch invalidates the launch: every sel_idx entry of
+ * its problems is -1 and the call returns BK_EHIP.
+ * Afterwards bk_selection_margin / _record follow bk_multikrum_batch's rule,
+ * and bk_selection_margin_batch(ctx, records, batch) gives the batch records in
+ * the caller's problem order.  Timed under BK_K_SMALL, BK_K_H2D and BK_K_D2H.
+ * The checks, in this order, all before any launch or state change: batch < 1
+ * is BK_EINVAL and batch > BK_MAX_BATCH is BK_ENOTSUP (no GPU, context or
+ * collection needed); then BK_EINVAL for a null ctx, orders, offsets, fs or
+ * sel_idx (named); a call without bk_collect_begin; offsets[0] != 0 or an n_b
+ * outside 1..count (the problem named); then bk_check_args(n_b, d, f_b)'s
+ * status, its message behind "problem b: "; then BK_EINVAL for an out-of-range
+ * or repeated slot within a problem (the problem and the position named).
+ * Every error leaves the collection, and the last valid margin state, as they
+ * were. */
+int bk_collect_finish_ragged(bk_ctx *ctx, const int64_t *orders, const int64_t *offsets,
+                             const int64_t *fs, int64_t batch, int64_t *sel_idx, int64_t *m_out,
+                             double *scores, double *mean_out);
+/* Host-side only; no context.  For W problems with n[] rows (1..128) and C
+ * mean items each: the queue position `item` of k_collect_small_ragged ->
+ * problem *p and k_collect_small's item number *it (it < n[p]: S item; else M
+ * item it - n[p]).  The kernel and the host entry decode with the same
+ * function.  BK_EINVAL outside the queue. */
+int bk_ragged_queue_item(const int32_t *n, int W, int C, int64_t item, int *p, int *it);
 
 /* Small batches (n <= 128, d <= 32768: Biscotti's deployed shapes, configs A
  * and B) run as ONE launch,
