@@ -19,7 +19,10 @@
 // bk_collect_finish_batch runs many such finishes over the one collection as
 // k_collect_small_batch launches (bk_collect_batch.hip), and
 // bk_collect_finish_ragged, where every problem has its own n and f, as
-// k_collect_small_ragged launches (bk_collect_ragged.hip).
+// k_collect_small_ragged launches (bk_collect_ragged.hip).  With
+// bk_set_collect_wide on, n <= 128 and 32,768 < d <= BK_COLLECT_WIDE_MAX_D take
+// one launch too: k_collect_wide, and k_collect_wide_ragged for the batched and
+// ragged entries (bk_collect_wide.hip).
 // Every element of G is the same sum whatever the add's count and however many
 // rows are resident: chunk s covers the same columns, one wave sums a chunk's
 // products in lane order and the chunks are added in the same tree, so the
@@ -398,6 +401,64 @@ int finish_small(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t
     return BK_OK;
 }
 
+// The wide one-launch range (bk_set_collect_wide, off by default): n <= 128 and
+// d past k_collect_small's cap.  The lower edge is the cap itself, not
+// small_ok's (BK_SMALL_MAX_D may lower that one for A/Bs).  The upper edge
+// depends on the mean: without one the launch does not depend on d and runs up
+// to BK_COLLECT_WIDE_MAX_D; with one it stops at BK_COLLECT_WIDE_MEAN_MAX_D,
+// past which the mean's way through the mapped block (written over PCIe by the
+// kernel, then copied by the host) was measured behind the chain's DMA copy
+// 
+bool wide_ok(const bk_ctx *c, int64_t n, int64_t d, bool mean) {
+    return c->small_on && c->collect_wide && n <= 128 && d > 32768 &&
+           d <= (mean ? BK_COLLECT_WIDE_MEAN_MAX_D : BK_COLLECT_WIDE_MAX_D);
+}
+
+// finish_small for wide rows: one k_collect_wide launch (bk_collect_wide.hip),
+// whose M items stream COLLECT_WIDE_COLS columns of the selected rows each; the
+// same mapped output block, the same one wait and host memcpys
+int finish_wide(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
+                int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
+    const int64_t m = n - f, d = k->d;
+    constexpr size_t MPAD = HOUT_MPAD;
+    CHK(ensure_small_queue(c));
+    CHK(ensure(c->diag, (size_t)n * sizeof(double)));
+    CHK(ensure_hout(c, MPAD + 2 * (size_t)n + (mean_out ? (size_t)d : 0)));
+    double *blk = c->hout_dev;
+    const uint64_t spin = c->small_spin_left == 0 ? SMALL_SPIN_MAX : c->small_spin_max;
+    if (c->small_spin_left > 0) --c->small_spin_left;
+    CHK(timed(c, BK_K_SMALL, [&] {
+        return launch_collect_wide(k->store.p, k->dtype, k->ld, (int)n, d, (int)f,
+                                   (const double *)k->G.p, order, (double *)k->scores.p,
+                                   (double *)c->diag.p, (int64_t *)(blk + MPAD),
+                                   mean_out ? blk + MPAD + 2 * n : nullptr, blk,
+                                   scores ? blk + MPAD + n : nullptr, (unsigned *)c->small_ctr.p,
+                                   c->num_cu, c->stream, spin, c->small_check_lines);
+    }));
+    c->margin_valid = 1;
+    c->margin_host = c->hout_host_margin;
+    c->margin_unchecked = 1;
+    HIPCHK(wait_stream(c));
+    const double *h = (const double *)c->hout;
+    c->margin_unchecked = 0;
+    CHK(margin_status(h));
+    memcpy(sel_idx, h + MPAD, (size_t)m * sizeof(int64_t));
+    if (scores) memcpy(scores, h + MPAD + n, (size_t)n * sizeof(double));
+    if (mean_out) memcpy(mean_out, h + MPAD + 2 * n, (size_t)d * sizeof(double));
+    if (m_out) *m_out = m;
+    return BK_OK;
+}
+
+// the mean bytes one wide batched launch may write: BK_COLLECT_WIDE_OUT_BYTES,
+// read at the call; it may only lower the default (1 GiB)
+size_t wide_out_bytes() {
+    const size_t dflt = (size_t)1 << 30;
+    const char *e = getenv("BK_COLLECT_WIDE_OUT_BYTES");
+    if (!e) return dflt;
+    const long long v = atoll(e);
+    return v > 0 && (size_t)v < dflt ? (size_t)v : dflt;
+}
+
 }  // namespace
 
 extern "C" {
@@ -563,6 +624,8 @@ int finish_checked(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64
                    int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
     if (small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
         return finish_small(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
+    if (wide_ok(c, n, k->d, mean_out != nullptr))
+        return finish_wide(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
     const hipStream_t st = c->stream;
     Drain drain{st};
     int64_t *ho = (int64_t *)k->horder.p;
@@ -703,6 +766,21 @@ int finish_batch_loop(bk_ctx *c, Collect *k, const int64_t *orders, int64_t batc
     return BK_OK;
 }
 
+int finish_ragged(bk_ctx *c, Collect *k, const int64_t *orders, const int64_t *offsets,
+                  const int64_t *fs, int64_t batch, int64_t *sel_idx, int64_t *m_out,
+                  double *scores, double *mean_out);
+
+// The batch in the wide range: the ragged finish on uniform descriptors (one
+// group, k_collect_wide_ragged launches), whose output layout for equal n and
+// f is this entry's
+int finish_batch_wide(bk_ctx *c, Collect *k, const int64_t *orders, int64_t batch, int64_t n,
+                      int64_t f, int64_t *sel_idx, double *scores, double *mean_out) {
+    std::vector<int64_t> offsets((size_t)batch + 1), fs((size_t)batch, f);
+    for (int64_t b = 0; b <= batch; ++b) offsets[(size_t)b] = b * n;
+    return finish_ragged(c, k, orders, offsets.data(), fs.data(), batch, sel_idx, nullptr, scores,
+                         mean_out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -743,6 +821,8 @@ int bk_collect_finish_batch(bk_ctx *c, const int64_t *orders, int64_t batch, int
     DeviceGuard dg(c->device);
     if (batch > 1 && small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
         CHK(finish_batch_small(c, k, orders, batch, n, f, sel_idx, scores, mean_out));
+    else if (batch > 1 && wide_ok(c, n, k->d, mean_out != nullptr))
+        CHK(finish_batch_wide(c, k, orders, batch, n, f, sel_idx, scores, mean_out));
     else
         CHK(finish_batch_loop(c, k, orders, batch, n, f, sel_idx, scores, mean_out));
     if (m_out) *m_out = n - f;
@@ -778,10 +858,18 @@ int finish_ragged(bk_ctx *c, Collect *k, const int64_t *orders, const int64_t *o
     std::vector<int64_t> selo(ub + 1, 0);  // problem b's sel at sum_{c<b} m_c
     for (int64_t b = 0; b < batch; ++b)
         selo[(size_t)b + 1] = selo[(size_t)b] + (offsets[b + 1] - offsets[b]) - fs[b];
+    // the wide range (bk_set_collect_wide): the same grouping, the launches
+    // k_collect_wide_ragged's, bounded by the mean bytes a launch writes too
+    const bool wide = wide_ok(c, 1, d, mean_out != nullptr);
+    int64_t maxw = SMALL_BATCH_MAX_W;
+    if (wide && mean_out) {
+        const int64_t fit = (int64_t)(wide_out_bytes() / ((size_t)d * sizeof(double)));
+        maxw = fit < 1 ? 1 : fit < maxw ? fit : maxw;
+    }
     std::vector<int64_t> bucket[9], single;
     for (int64_t b = 0; b < batch; ++b) {
         const int64_t n = offsets[b + 1] - offsets[b];
-        if (small_ok(c, k->store.p, k->dtype, n, d, k->ld))
+        if (small_ok(c, k->store.p, k->dtype, n, d, k->ld) || wide_ok(c, n, d, mean_out != nullptr))
             bucket[(n + 15) / 16].push_back(b);
         else
             single.push_back(b);
@@ -798,9 +886,8 @@ int finish_ragged(bk_ctx *c, Collect *k, const int64_t *orders, const int64_t *o
         const std::vector<int64_t> &bk = bucket[NB];
         if (bk.size() == 1) single.push_back(bk[0]);
         if (bk.size() < 2) continue;
-        for (size_t b0 = 0; b0 < bk.size(); b0 += SMALL_BATCH_MAX_W) {
-            const int w = (int)(bk.size() - b0 < (size_t)SMALL_BATCH_MAX_W ? bk.size() - b0
-                                                                           : SMALL_BATCH_MAX_W);
+        for (size_t b0 = 0; b0 < bk.size(); b0 += (size_t)maxw) {
+            const int w = (int)(bk.size() - b0 < (size_t)maxw ? bk.size() - b0 : (size_t)maxw);
             launches.push_back({NB, w, kern.size(), nseg});
             nseg += (size_t)w + 2;
             if (w > maxW) maxW = w;
@@ -812,7 +899,7 @@ int finish_ragged(bk_ctx *c, Collect *k, const int64_t *orders, const int64_t *o
     }
     std::vector<double> recs(ub * MARGIN_WORDS);
     if (!launches.empty()) {
-        const int C = mean_out ? (int)((d + 63) / 64) : 1;
+        const int C = !mean_out ? 1 : wide ? collect_wide_items(d) : (int)((d + 63) / 64);
         // the staging block: descriptors | segment starts | 16-bit slots
         const size_t off_seg = up16(kern.size() * sizeof(RaggedDesc));
         const size_t off_ord = up16(off_seg + nseg * sizeof(int32_t));
@@ -872,7 +959,7 @@ int finish_ragged(bk_ctx *c, Collect *k, const int64_t *orders, const int64_t *o
             const uint64_t spin = c->small_spin_left == 0 ? SMALL_SPIN_MAX : c->small_spin_max;
             if (c->small_spin_left > 0) --c->small_spin_left;
             CHK(timed(c, BK_K_SMALL, [&] {
-                return launch_collect_small_ragged(
+                return (wide ? launch_collect_wide_ragged : launch_collect_small_ragged)(
                     k->store.p, k->dtype, k->ld, L.W, L.NB, d, (const double *)k->G.p,
                     (const RaggedDesc *)ds + L.first, (const int32_t *)(ds + off_seg) + L.seg,
                     hseg[L.seg + L.W + 1], lead[l], (const uint16_t *)(ds + off_ord), dsc, ddg,

@@ -397,6 +397,31 @@ hipError_t launch_collect_small_ragged(const void *store, int dtype, int64_t ld,
                                        int64_t *sel, double *mean, double *margin, unsigned *lines,
                                        int num_cu, hipStream_t st,
                                        uint64_t spin_max = SMALL_SPIN_MAX);
+// bk_collect_wide.hip, k_collect_wide / k_collect_wide_ragged: the collection
+// finishes for wide rows (n <= 128, d past k_collect_small's cap, opted into by
+// bk_set_collect_wide).  k_collect_small's S items and queue with an M item
+// that streams: item c owns columns [c W, c W + W), W = COLLECT_WIDE_COLS in
+// both dtypes, and adds the m selected rows of the row store in ascending
+// order into one fp64 accumulator per column.  The arguments are
+// launch_collect_small's and launch_collect_small_ragged's; seg, total and
+// lead are built with collect_wide_items(d) M items per problem (1 without a
+// mean)
+constexpr int COLLECT_WIDE_COLS = 2048;  // columns per M item (a multiple of 64)
+inline int collect_wide_items(int64_t d) {
+    return (int)((d + COLLECT_WIDE_COLS - 1) / COLLECT_WIDE_COLS);
+}
+hipError_t launch_collect_wide(const void *store, int dtype, int64_t ld, int n, int64_t d, int f,
+                               const double *G, const int64_t *order, double *scores, double *diag,
+                               int64_t *sel, double *mean, double *margin, double *scores_out,
+                               unsigned *ctr, int num_cu, hipStream_t st,
+                               uint64_t spin_max = SMALL_SPIN_MAX, int check_lines = 0);
+hipError_t launch_collect_wide_ragged(const void *store, int dtype, int64_t ld, int W, int NB,
+                                      int64_t d, const double *G, const RaggedDesc *desc,
+                                      const int32_t *seg, int total, int lead,
+                                      const uint16_t *orders, double *scores, double *diag,
+                                      int64_t *sel, double *mean, double *margin, unsigned *lines,
+                                      int num_cu, hipStream_t st,
+                                      uint64_t spin_max = SMALL_SPIN_MAX);
 hipError_t launch_synth(void *X, int dtype, int64_t ld, int64_t n, int64_t dl, int64_t c0,
                         const int64_t *perm, const SynthParams &P, hipStream_t st);
 

@@ -559,6 +559,12 @@ class Engine:
         """n <= 128: the one-launch k_small path (default) or the general chain."""
         check(lib().bk_set_small_path(self._ctx, 1 if on else 0))
 
+    def set_collect_wide(self, on=True):
+        """opt-in (default off): collection finishes of n <= 128 rows with 32,768 <
+        d <= 1,048,576 in one launch as well (bk_set_collect_wide); the outputs
+        are bitwise the chain's."""
+        check(lib().bk_set_collect_wide(self._ctx, 1 if on else 0))
+
     def certified_reruns(self):
         return int(lib().bk_certified_reruns(self._ctx))
 
@@ -715,11 +721,13 @@ class KRUMValidator:
     """DistSys/krum.go:22-29, with getTopKRUMIndex running on libbk."""
 
     def __init__(self, num_adversaries=0.5, engine: Optional[Engine] = None, device=0,
-                 collect=False, n_cap=128):
+                 collect=False, n_cap=128, wide=False):
         """collect=True (opt-in): add_update streams each update's NoisedDelta
         to the engine's collection as it arrives (bk_collect_add), and
         compute_scores only finishes (bk_collect_finish) in SourceID order;
-        n_cap bounds the updates of one round (KRUM_UPDATETHRESH)."""
+        n_cap bounds the updates of one round (KRUM_UPDATETHRESH).  wide=True
+        (with collect) turns the engine's wide one-launch finish on when the
+        round begins (Engine.set_collect_wide: the CNN models' d)."""
         self.UpdateList: List[Update] = []
         self.AcceptedList: List[int] = []
         self.NumAdversaries = num_adversaries  # fixed at 0.5 (main.go:783)
@@ -727,6 +735,7 @@ class KRUMValidator:
         self._device = device
         self._collect = bool(collect)
         self._n_cap = int(n_cap)
+        self._wide = bool(wide)
         self._slots: List[int] = []  # collect mode: arrival slot of UpdateList[i]
 
     def initialize(self):
@@ -748,6 +757,8 @@ class KRUMValidator:
                 self.initialize()
             row = np.ascontiguousarray(update.NoisedDelta, dtype=np.float64)
             if not self._slots:
+                if self._wide:
+                    self._engine.set_collect_wide(True)
                 self._engine.collect_begin(self._n_cap, row.shape[0], np.float64)
             self._slots.append(self._engine.collect_add(row))
         self.UpdateList.append(update)

@@ -179,7 +179,9 @@ int bk_collect_count(bk_ctx *ctx, int64_t *count);
  * again.  bk_selection_margin* then reports this finish's record (d = the
  * collection's d, u_G = 2^-53).  For n <= 128 and d <= 32,768 the finish is one
  * kernel launch with no copy before or after it (bk_set_small_path(ctx, 0)
- * gives the general launch chain instead; the outputs are bitwise the same). */
+ * gives the general launch chain instead; the outputs are bitwise the same);
+ * bk_set_collect_wide(ctx, 1) extends that to 32,768 < d <=
+ * BK_COLLECT_WIDE_MAX_D, with the same bits. */
 int bk_collect_finish(bk_ctx *ctx, const int64_t *order, int64_t n, int64_t f,
                       int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out);
 
@@ -250,7 +252,12 @@ int bk_selection_margin_batch(bk_ctx *ctx, double *records, int64_t batch);
  * items of up to 1,024 problems from one queue, reading the collection's Gram
  * and row store through each problem's order -- no Gram work, and nothing
  * uploaded but the batch x n slot numbers; a larger batch runs as consecutive
- * launches.  Any other shape, bk_set_small_path(ctx, 0) and batch = 1 run the
+ * launches.  With bk_set_collect_wide on, 32,768 < d <= BK_COLLECT_WIDE_MAX_D
+ * shares launches too (k_collect_wide_ragged on uniform descriptors), the
+ * problems per launch bounded by 1,024 and by the mean bytes a launch writes,
+ * batch x d doubles (the environment variable BK_COLLECT_WIDE_OUT_BYTES, read
+ * at the call, may lower its 1 GiB default; a launch holds one problem at
+ * least).  Any other shape, bk_set_small_path(ctx, 0) and batch = 1 run the
  * single finish once per problem.  Its buffers are its own: a bk_collect_finish,
  * bk_multikrum* or bk_multikrum_batch* between two calls is unaffected and
  * affects nothing here; a bk_collect_begin that regrows the collection and
@@ -297,7 +304,10 @@ int bk_collect_finish_batch(bk_ctx *ctx, const int64_t *orders, int64_t batch, i
  * that number, so only problems that agree in it may share a launch -- and
  * each group of two or more runs as k_collect_small_ragged launches of up to
  * 1,024 problems: k_collect_small's work items behind a per-problem descriptor,
- * every output written at the caller's position.  Every other problem, and a
+ * every output written at the caller's position.  With bk_set_collect_wide on
+ * and 32,768 < d <= BK_COLLECT_WIDE_MAX_D the grouping is the same and the
+ * launches are k_collect_wide_ragged's, bounded as bk_collect_finish_batch's
+ * (BK_COLLECT_WIDE_OUT_BYTES).  Every other problem, and a
  * group's only one, runs the single finish; a call may mix both.  Its buffers
  * are bk_collect_finish_batch's, with their life-cycle: nothing between two
  * calls (a single or a batched finish, bk_multikrum*, bk_collect_add) affects
@@ -320,7 +330,8 @@ int bk_collect_finish_ragged(bk_ctx *ctx, const int64_t *orders, const int64_t *
                              const int64_t *fs, int64_t batch, int64_t *sel_idx, int64_t *m_out,
                              double *scores, double *mean_out);
 /* Host-side only; no context.  For W problems with n[] rows (1..128) and C
- * mean items each: the queue position `item` of k_collect_small_ragged ->
+ * mean items each (ceil(d / 64), or ceil(d / 2,048) for k_collect_wide_ragged;
+ * 1 without a mean): the queue position `item` of k_collect_small_ragged ->
  * problem *p and k_collect_small's item number *it (it < n[p]: S item; else M
  * item it - n[p]).  The kernel and the host entry decode with the same
  * function.  BK_EINVAL outside the queue. */
@@ -333,6 +344,25 @@ int bk_ragged_queue_item(const int32_t *n, int W, int C, int64_t item, int *p, i
  * results as the general path: selection, and the mean bitwise; scores within
  * rounding (another split of the Gram).  on = 0 forces the general path. */
 int bk_set_small_path(bk_ctx *ctx, int on);
+/* Opt-in (default off): the one-launch collection finishes for WIDE rows.  With
+ * on != 0 (and the small path on) bk_collect_finish, bk_collect_finish_batch
+ * and bk_collect_finish_ragged take one launch for n <= 128 and 32,768 < d <=
+ * BK_COLLECT_WIDE_MAX_D as well: k_collect_wide keeps k_collect_small's score
+ * items and queue, and its mean items stream 2,048 columns of the selected rows
+ * each from the row store (k_collect_wide_ragged behind the batched and ragged
+ * entries' descriptors).  Every output stays bitwise the launch chain's.
+ * A call that asks for the mean takes the wide launch only up to d =
+ * BK_COLLECT_WIDE_MEAN_MAX_D: the wide finish hands the mean over through
+ * mapped host memory, and past that size it was measured behind the chain's
+ * DMA copy (100 x 259,770 fp64: 181 us against 159; 100 x 163,850: 126 against
+ * 140); a call without a mean, the verifier's own, does not depend on d (24 us
+ * against 66).  bk_set_small_path(ctx, 0) still forces the chain everywhere.
+ * BK_EINVAL: a null ctx.  Added without a change of BK_ABI_VERSION (14): the
+ * entry is additive, and a library that lacks it fails at link or symbol
+ * lookup. */
+#define BK_COLLECT_WIDE_MAX_D 1048576
+#define BK_COLLECT_WIDE_MEAN_MAX_D 165888 /* 81 mean items of 2,048 columns */
+int bk_set_collect_wide(bk_ctx *ctx, int on);
 /* Replay bk_multikrum_device as a hipGraph (one captured launch sequence per
  * call signature: pointers, shape, f; up to 4 cached).  The first call of a
  * signature runs eagerly, the second captures, later ones replay; graphs are
