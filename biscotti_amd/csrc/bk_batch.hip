@@ -75,8 +75,7 @@ int run_small_batch(bk_ctx *c, const void *dX, int dtype, int64_t batch, int64_t
     const size_t es = esize(dtype);
     for (int64_t b0 = 0; b0 < batch; b0 += W) {
         const int w = (int)std::min<int64_t>(W, batch - b0);
-        const uint64_t spin = c->small_spin_left == 0 ? SMALL_SPIN_MAX : c->small_spin_max;
-        if (c->small_spin_left > 0) --c->small_spin_left;
+        const uint64_t spin = next_spin(c);
         CHK(timed(c, BK_K_SMALL, [&] {
             return launch_small_batch((const char *)dX + (size_t)b0 * stride * es, dtype, ld, stride,
                                       w, (int)n, d, (int)f, sp, (double *)c->batch_part.p,

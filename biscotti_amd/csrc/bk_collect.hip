@@ -362,14 +362,39 @@ int upload_pageable(Collect *k, char *dst, const char *src, size_t bytes, hipStr
 int finish_checked(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
                    int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out);
 
-// The finish of the deployed shapes (small_ok: n <= 128, d <= 32,768) in one
-// launch: k_collect_small reads the Gram and the row store through the order
-// in its own arguments and writes {margin, sel, scores, mean} into the
-// context's mapped output block, so nothing is uploaded before it and nothing
-// copied after it -- one launch, one wait, then host memcpys.  The arguments
-// are validated by the caller.
-int finish_small(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
-                 int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
+// every order entry a collected slot (0..count-1), none repeated within its
+// problem; slots may be reused across problems: seen[o] = 1 + the last problem
+// b that used slot o (count zeros at the call's first problem).  b < 0: the
+// single finish, whose messages carry no problem
+int check_order(const int64_t *order, int64_t n, int64_t count, std::vector<int64_t> &seen,
+                int64_t b) {
+    // (formatted on the refusal only: a batch of 256 checks 256 orders per call)
+    const auto who = [b] { return b < 0 ? std::string() : "problem " + std::to_string(b) + ": "; };
+    const int64_t mark = b < 0 ? 1 : b + 1;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t o = order[i];
+        if (o < 0 || o >= count)
+            return fail(BK_EINVAL, "%sorder[%lld] = %lld is no collected slot (0..%lld)",
+                        who().c_str(), (long long)i, (long long)o, (long long)count - 1);
+        if (seen[(size_t)o] == mark)
+            return fail(BK_EINVAL, "%sorder[%lld] = %lld repeats a slot", who().c_str(),
+                        (long long)i, (long long)o);
+        seen[(size_t)o] = mark;
+    }
+    return BK_OK;
+}
+
+// The finish of n <= 128 rows in one launch: k_collect_small for the deployed
+// shapes (small_ok: d <= 32,768; launch_collect_small) or, in the wide range
+// (wide_ok), k_collect_wide, whose M items stream COLLECT_WIDE_COLS columns of
+// the selected rows each (launch_collect_wide).  The kernel reads the Gram and
+// the row store through the order in its own arguments and writes {margin,
+// sel, scores, mean} into the context's mapped output block, so nothing is
+// uploaded before it and nothing copied after it -- one launch, one wait, then
+// host memcpys.  The arguments are validated by the caller.
+int finish_one_launch(bk_ctx *c, Collect *k, decltype(&launch_collect_small) launch,
+                      const int64_t *order, int64_t n, int64_t f, int64_t *sel_idx, int64_t *m_out,
+                      double *scores, double *mean_out) {
     static_assert(BK_MAX_N <= 65536, "arrival slots travel as 16-bit kernel arguments");
     const int64_t m = n - f, d = k->d;
     constexpr size_t MPAD = HOUT_MPAD;
@@ -377,15 +402,13 @@ int finish_small(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t
     CHK(ensure(c->diag, (size_t)n * sizeof(double)));
     CHK(ensure_hout(c, MPAD + 2 * (size_t)n + (mean_out ? (size_t)d : 0)));
     double *blk = c->hout_dev;
-    const uint64_t spin = c->small_spin_left == 0 ? SMALL_SPIN_MAX : c->small_spin_max;
-    if (c->small_spin_left > 0) --c->small_spin_left;
+    const uint64_t spin = next_spin(c);
     CHK(timed(c, BK_K_SMALL, [&] {
-        return launch_collect_small(k->store.p, k->dtype, k->ld, (int)n, d, (int)f,
-                                    (const double *)k->G.p, order, (double *)k->scores.p,
-                                    (double *)c->diag.p, (int64_t *)(blk + MPAD),
-                                    mean_out ? blk + MPAD + 2 * n : nullptr, blk,
-                                    scores ? blk + MPAD + n : nullptr, (unsigned *)c->small_ctr.p,
-                                    c->num_cu, c->stream, spin, c->small_check_lines);
+        return launch(k->store.p, k->dtype, k->ld, (int)n, d, (int)f, (const double *)k->G.p, order,
+                      (double *)k->scores.p, (double *)c->diag.p, (int64_t *)(blk + MPAD),
+                      mean_out ? blk + MPAD + 2 * n : nullptr, blk,
+                      scores ? blk + MPAD + n : nullptr, (unsigned *)c->small_ctr.p, c->num_cu,
+                      c->stream, spin, c->small_check_lines);
     }));
     c->margin_valid = 1;
     c->margin_host = c->hout_host_margin;
@@ -412,41 +435,6 @@ int finish_small(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t
 bool wide_ok(const bk_ctx *c, int64_t n, int64_t d, bool mean) {
     return c->small_on && c->collect_wide && n <= 128 && d > 32768 &&
            d <= (mean ? BK_COLLECT_WIDE_MEAN_MAX_D : BK_COLLECT_WIDE_MAX_D);
-}
-
-// finish_small for wide rows: one k_collect_wide launch (bk_collect_wide.hip),
-// whose M items stream COLLECT_WIDE_COLS columns of the selected rows each; the
-// same mapped output block, the same one wait and host memcpys
-int finish_wide(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
-                int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
-    const int64_t m = n - f, d = k->d;
-    constexpr size_t MPAD = HOUT_MPAD;
-    CHK(ensure_small_queue(c));
-    CHK(ensure(c->diag, (size_t)n * sizeof(double)));
-    CHK(ensure_hout(c, MPAD + 2 * (size_t)n + (mean_out ? (size_t)d : 0)));
-    double *blk = c->hout_dev;
-    const uint64_t spin = c->small_spin_left == 0 ? SMALL_SPIN_MAX : c->small_spin_max;
-    if (c->small_spin_left > 0) --c->small_spin_left;
-    CHK(timed(c, BK_K_SMALL, [&] {
-        return launch_collect_wide(k->store.p, k->dtype, k->ld, (int)n, d, (int)f,
-                                   (const double *)k->G.p, order, (double *)k->scores.p,
-                                   (double *)c->diag.p, (int64_t *)(blk + MPAD),
-                                   mean_out ? blk + MPAD + 2 * n : nullptr, blk,
-                                   scores ? blk + MPAD + n : nullptr, (unsigned *)c->small_ctr.p,
-                                   c->num_cu, c->stream, spin, c->small_check_lines);
-    }));
-    c->margin_valid = 1;
-    c->margin_host = c->hout_host_margin;
-    c->margin_unchecked = 1;
-    HIPCHK(wait_stream(c));
-    const double *h = (const double *)c->hout;
-    c->margin_unchecked = 0;
-    CHK(margin_status(h));
-    memcpy(sel_idx, h + MPAD, (size_t)m * sizeof(int64_t));
-    if (scores) memcpy(scores, h + MPAD + n, (size_t)n * sizeof(double));
-    if (mean_out) memcpy(mean_out, h + MPAD + 2 * n, (size_t)d * sizeof(double));
-    if (m_out) *m_out = m;
-    return BK_OK;
 }
 
 // the mean bytes one wide batched launch may write: BK_COLLECT_WIDE_OUT_BYTES,
@@ -599,17 +587,8 @@ int bk_collect_finish(bk_ctx *c, const int64_t *order, int64_t n, int64_t f, int
                     (long long)k->count, (long long)n);
     CHK(bk_check_args(n, k->d, f));
     if (order) {
-        std::vector<char> seen((size_t)k->count, 0);
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t o = order[i];
-            if (o < 0 || o >= k->count)
-                return fail(BK_EINVAL, "order[%lld] = %lld is no collected slot (0..%lld)",
-                            (long long)i, (long long)o, (long long)k->count - 1);
-            if (seen[(size_t)o])
-                return fail(BK_EINVAL, "order[%lld] = %lld repeats a slot", (long long)i,
-                            (long long)o);
-            seen[(size_t)o] = 1;
-        }
+        std::vector<int64_t> seen((size_t)k->count, 0);
+        CHK(check_order(order, n, k->count, seen, -1));
     }
     DeviceGuard dg(c->device);
     return finish_checked(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
@@ -623,9 +602,11 @@ namespace {
 int finish_checked(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
                    int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
     if (small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
-        return finish_small(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
+        return finish_one_launch(c, k, launch_collect_small, order, n, f, sel_idx, m_out, scores,
+                                 mean_out);
     if (wide_ok(c, n, k->d, mean_out != nullptr))
-        return finish_wide(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
+        return finish_one_launch(c, k, launch_collect_wide, order, n, f, sel_idx, m_out, scores,
+                                 mean_out);
     const hipStream_t st = c->stream;
     Drain drain{st};
     int64_t *ho = (int64_t *)k->horder.p;
@@ -667,6 +648,79 @@ int finish_checked(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64
     return BK_OK;
 }
 
+// What bk_collect_finish_batch's launches (finish_batch_small) and
+// bk_collect_finish_ragged's (finish_ragged) share on the host: the buffers,
+// the read-back and the closing bookkeeping.
+
+// The collection's batch buffers for `batch` problems in launches of at most W:
+// obytes of staged orders (device and pinned), nsc scores and diag, nsel
+// selected indices, the means, the queue lines (zeroed when they grow; every
+// launch leaves them zero) and the context's record store.  (Every user of
+// these buffers is synchronous: none is in use when it grows)
+int batch_buffers(bk_ctx *c, Collect *k, const char *who, int64_t batch, int64_t W, size_t obytes,
+                  size_t nsc, size_t nsel, bool mean) {
+    const size_t lbytes =
+        (size_t)(COLLECT_BATCH_QLINES + W * COLLECT_BATCH_LINES) * 32 * sizeof(unsigned);
+    const bool new_lines = lbytes > k->b_ctr.bytes;
+    CHK(grow_all({{&k->b_order, obytes},
+                  {&k->b_horder, obytes},
+                  {&k->b_scores, nsc * sizeof(double)},
+                  {&k->b_diag, nsc * sizeof(double)},
+                  {&k->b_sel, nsel * sizeof(int64_t)},
+                  {&k->b_mean, mean ? (size_t)batch * (size_t)k->d * sizeof(double) : 0},
+                  {&k->b_ctr, lbytes}},
+                 who));
+    CHK(ensure(c->batch_rec, (size_t)batch * MARGIN_WORDS * sizeof(double)));
+    if (new_lines) HIPCHK(hipMemsetAsync(k->b_ctr.p, 0, k->b_ctr.bytes, c->stream));
+    return BK_OK;
+}
+
+// The records (to recs), sel, scores and the means come back whole after the
+// last launch, under one timing bracket and the one wait
+int batch_readback(bk_ctx *c, Collect *k, int64_t batch, size_t nsc, size_t nsel, double *recs,
+                   int64_t *sel_idx, double *scores, double *mean_out) {
+    const hipStream_t st = c->stream;
+    const size_t ub = (size_t)batch;
+    CHK(timed(c, BK_K_D2H, [&] {
+        hipError_t e = hipMemcpyAsync(recs, c->batch_rec.p, ub * MARGIN_WORDS * sizeof(double),
+                                      hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(sel_idx, k->b_sel.p, nsel * sizeof(int64_t), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && scores)
+            e = hipMemcpyAsync(scores, k->b_scores.p, nsc * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && mean_out)
+            e = hipMemcpyAsync(mean_out, k->b_mean.p, ub * (size_t)k->d * sizeof(double),
+                               hipMemcpyDeviceToHost, st);
+        return e;
+    }));
+    HIPCHK(wait_stream(c));
+    return BK_OK;
+}
+
+// The stream is idle and batch_rec_h holds the call's records: the context's
+// record is the batch's pick, checked here (an error code wins the pick: a
+// give-up marks every problem of its launch)
+int batch_close(bk_ctx *c, int64_t batch) {
+    c->batch_one = 0;
+    c->batch_last = batch;
+    batch_pick_record(c);
+    c->margin_valid = 1;
+    c->margin_host = c->batch_pick;
+    c->margin_unchecked = 0;
+    return margin_status(c->batch_pick);
+}
+
+// One problem of a batch by the single finish, which is synchronous and leaves
+// its record in host memory: the record is copied behind it straight to rec,
+// the problem's place in the host side of the batch record store -- no copy to
+// the device and none back
+int finish_one_of_batch(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
+                        int64_t *sel_idx, double *scores, double *mean_out, double *rec) {
+    CHK(finish_checked(c, k, order, n, f, sel_idx, nullptr, scores, mean_out));
+    memcpy(rec, c->margin_host, MARGIN_WORDS * sizeof(double));
+    return BK_OK;
+}
+
 // The batch within k_collect_small's range: launches of W <= SMALL_BATCH_MAX_W
 // problems (k_collect_small_batch, bk_collect_batch.hip) on buffers of the
 // collection's own; the slots go up as 16-bit numbers in one copy from pinned
@@ -678,20 +732,8 @@ int finish_batch_small(bk_ctx *c, Collect *k, const int64_t *orders, int64_t bat
     const hipStream_t st = c->stream;
     const size_t ub = (size_t)batch, un = (size_t)n;
     const int64_t W = batch < SMALL_BATCH_MAX_W ? batch : SMALL_BATCH_MAX_W;
-    const size_t lbytes =
-        (size_t)(COLLECT_BATCH_QLINES + W * COLLECT_BATCH_LINES) * 32 * sizeof(unsigned);
-    const bool new_lines = lbytes > k->b_ctr.bytes;
-    // (every user of these buffers is synchronous: none is in use when it grows)
-    CHK(grow_all({{&k->b_order, ub * un * sizeof(uint16_t)},
-                  {&k->b_horder, ub * un * sizeof(uint16_t)},
-                  {&k->b_scores, ub * un * sizeof(double)},
-                  {&k->b_diag, ub * un * sizeof(double)},
-                  {&k->b_sel, ub * (size_t)m * sizeof(int64_t)},
-                  {&k->b_mean, mean_out ? ub * (size_t)d * sizeof(double) : 0},
-                  {&k->b_ctr, lbytes}},
-                 "bk_collect_finish_batch"));
-    CHK(ensure(c->batch_rec, ub * MARGIN_WORDS * sizeof(double)));
-    if (new_lines) HIPCHK(hipMemsetAsync(k->b_ctr.p, 0, k->b_ctr.bytes, st));
+    CHK(batch_buffers(c, k, "bk_collect_finish_batch", batch, W, ub * un * sizeof(uint16_t), ub * un,
+                      ub * (size_t)m, mean_out != nullptr));
     Drain drain{st};
     uint16_t *ho = (uint16_t *)k->b_horder.p;
     for (size_t i = 0; i < ub * un; ++i) ho[i] = (uint16_t)orders[i];  // validated: < count <= 65,536
@@ -703,8 +745,7 @@ int finish_batch_small(bk_ctx *c, Collect *k, const int64_t *orders, int64_t bat
     int64_t *dsel = (int64_t *)k->b_sel.p;
     for (int64_t b0 = 0; b0 < batch; b0 += W) {
         const int w = (int)(batch - b0 < W ? batch - b0 : W);
-        const uint64_t spin = c->small_spin_left == 0 ? SMALL_SPIN_MAX : c->small_spin_max;
-        if (c->small_spin_left > 0) --c->small_spin_left;
+        const uint64_t spin = next_spin(c);
         CHK(timed(c, BK_K_SMALL, [&] {
             return launch_collect_small_batch(
                 k->store.p, k->dtype, k->ld, w, (int)n, d, (int)f, (const double *)k->G.p,
@@ -713,6 +754,8 @@ int finish_batch_small(bk_ctx *c, Collect *k, const int64_t *orders, int64_t bat
                 (unsigned *)k->b_ctr.p, c->num_cu, st, spin);
         }));
     }
+    // the launches are queued: from here the context's record is this batch's,
+    // unchecked until the wait is over (batch_close states the rest again)
     c->batch_one = 0;
     c->margin_valid = 1;
     c->margin_host = c->batch_pick;
@@ -721,49 +764,24 @@ int finish_batch_small(bk_ctx *c, Collect *k, const int64_t *orders, int64_t bat
     c->batch_fetched = 0;
     // the records come back with the outputs, under the same wait
     c->batch_rec_h.resize(ub * MARGIN_WORDS);
-    CHK(timed(c, BK_K_D2H, [&] {
-        hipError_t e = hipMemcpyAsync(c->batch_rec_h.data(), c->batch_rec.p,
-                                      ub * MARGIN_WORDS * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(sel_idx, dsel, ub * (size_t)m * sizeof(int64_t),
-                               hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && scores)
-            e = hipMemcpyAsync(scores, dsc, ub * un * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && mean_out)
-            e = hipMemcpyAsync(mean_out, dmean, ub * (size_t)d * sizeof(double),
-                               hipMemcpyDeviceToHost, st);
-        return e;
-    }));
-    HIPCHK(wait_stream(c));
+    CHK(batch_readback(c, k, batch, ub * un, ub * (size_t)m, c->batch_rec_h.data(), sel_idx, scores,
+                       mean_out));
     drain.armed = false;
-    batch_pick_record(c);
-    c->margin_unchecked = 0;
-    return margin_status(c->batch_pick);  // an error code wins the pick: a give-up marks them all
+    return batch_close(c, batch);
 }
 
-// Outside that range, and for one problem: the single finish per problem.  It
-// is synchronous and leaves its record in host memory, so each problem's
-// record is copied behind its finish straight into the host side of the batch
-// record store: no copy to the device and none back
+// Outside that range, and for one problem: the single finish per problem
 int finish_batch_loop(bk_ctx *c, Collect *k, const int64_t *orders, int64_t batch, int64_t n,
                       int64_t f, int64_t *sel_idx, double *scores, double *mean_out) {
     const int64_t m = n - f;
     std::vector<double> recs((size_t)batch * MARGIN_WORDS);
-    for (int64_t b = 0; b < batch; ++b) {
-        CHK(finish_checked(c, k, orders + b * n, n, f, sel_idx + b * m, nullptr,
-                           scores ? scores + b * n : nullptr,
-                           mean_out ? mean_out + b * k->d : nullptr));
-        memcpy(recs.data() + (size_t)b * MARGIN_WORDS, c->margin_host,
-               MARGIN_WORDS * sizeof(double));
-    }
+    for (int64_t b = 0; b < batch; ++b)
+        CHK(finish_one_of_batch(c, k, orders + b * n, n, f, sel_idx + b * m,
+                                scores ? scores + b * n : nullptr,
+                                mean_out ? mean_out + b * k->d : nullptr,
+                                recs.data() + (size_t)b * MARGIN_WORDS));
     c->batch_rec_h.swap(recs);
-    c->batch_one = 0;
-    c->batch_last = batch;
-    batch_pick_record(c);
-    c->margin_valid = 1;
-    c->margin_host = c->batch_pick;
-    c->margin_unchecked = 0;  // every finish checked its own record
-    return BK_OK;
+    return batch_close(c, batch);  // (every finish checked its own record)
 }
 
 int finish_ragged(bk_ctx *c, Collect *k, const int64_t *orders, const int64_t *offsets,
@@ -803,20 +821,8 @@ int bk_collect_finish_batch(bk_ctx *c, const int64_t *orders, int64_t batch, int
                     (long long)n, (long long)k->count);
     CHK(bk_check_args(n, k->d, f));
     {
-        // seen[o] = 1 + the last problem that used slot o
         std::vector<int64_t> seen((size_t)k->count, 0);
-        for (int64_t b = 0; b < batch; ++b)
-            for (int64_t i = 0; i < n; ++i) {
-                const int64_t o = orders[b * n + i];
-                if (o < 0 || o >= k->count)
-                    return fail(BK_EINVAL,
-                                "problem %lld: order[%lld] = %lld is no collected slot (0..%lld)",
-                                (long long)b, (long long)i, (long long)o, (long long)k->count - 1);
-                if (seen[(size_t)o] == b + 1)
-                    return fail(BK_EINVAL, "problem %lld: order[%lld] = %lld repeats a slot",
-                                (long long)b, (long long)i, (long long)o);
-                seen[(size_t)o] = b + 1;
-            }
+        for (int64_t b = 0; b < batch; ++b) CHK(check_order(orders + b * n, n, k->count, seen, b));
     }
     DeviceGuard dg(c->device);
     if (batch > 1 && small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
@@ -847,8 +853,10 @@ constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 // shaped like the caller's, which come back whole after the last launch.  Every
 // other problem, and a bucket's only one, then runs the single finish straight
 // into the caller's arrays, its record into the host side of the batch record
-// store at the caller's index (finish_batch_loop).  The buffers are the batched
-// finish's (both entries are synchronous and leave the lines zero).
+// store at the caller's index (finish_one_of_batch).  The buffers, the read-back
+// and the closing bookkeeping are the batched finish's (batch_buffers,
+// batch_readback, batch_close; both entries are synchronous and leave the lines
+// zero).
 int finish_ragged(bk_ctx *c, Collect *k, const int64_t *orders, const int64_t *offsets,
                   const int64_t *fs, int64_t batch, int64_t *sel_idx, int64_t *m_out,
                   double *scores, double *mean_out) {
@@ -904,20 +912,8 @@ int finish_ragged(bk_ctx *c, Collect *k, const int64_t *orders, const int64_t *o
         const size_t off_seg = up16(kern.size() * sizeof(RaggedDesc));
         const size_t off_ord = up16(off_seg + nseg * sizeof(int32_t));
         const size_t sbytes = off_ord + nslots * sizeof(uint16_t);
-        const size_t lbytes =
-            (size_t)(COLLECT_BATCH_QLINES + maxW * COLLECT_BATCH_LINES) * 32 * sizeof(unsigned);
-        const bool new_lines = lbytes > k->b_ctr.bytes;
-        // (every user of these buffers is synchronous: none is in use when it grows)
-        CHK(grow_all({{&k->b_order, sbytes},
-                      {&k->b_horder, sbytes},
-                      {&k->b_scores, (size_t)offsets[batch] * sizeof(double)},
-                      {&k->b_diag, (size_t)offsets[batch] * sizeof(double)},
-                      {&k->b_sel, (size_t)selo[ub] * sizeof(int64_t)},
-                      {&k->b_mean, mean_out ? ub * (size_t)d * sizeof(double) : 0},
-                      {&k->b_ctr, lbytes}},
-                     "bk_collect_finish_ragged"));
-        CHK(ensure(c->batch_rec, ub * MARGIN_WORDS * sizeof(double)));
-        if (new_lines) HIPCHK(hipMemsetAsync(k->b_ctr.p, 0, k->b_ctr.bytes, st));
+        CHK(batch_buffers(c, k, "bk_collect_finish_ragged", batch, maxW, sbytes,
+                          (size_t)offsets[batch], (size_t)selo[ub], mean_out != nullptr));
         Drain drain{st};
         char *hs = (char *)k->b_horder.p;
         RaggedDesc *hd = (RaggedDesc *)hs;
@@ -956,8 +952,7 @@ int finish_ragged(bk_ctx *c, Collect *k, const int64_t *orders, const int64_t *o
         int64_t *dsel = (int64_t *)k->b_sel.p;
         for (size_t l = 0; l < launches.size(); ++l) {
             const Launch &L = launches[l];
-            const uint64_t spin = c->small_spin_left == 0 ? SMALL_SPIN_MAX : c->small_spin_max;
-            if (c->small_spin_left > 0) --c->small_spin_left;
+            const uint64_t spin = next_spin(c);
             CHK(timed(c, BK_K_SMALL, [&] {
                 return (wide ? launch_collect_wide_ragged : launch_collect_small_ragged)(
                     k->store.p, k->dtype, k->ld, L.W, L.NB, d, (const double *)k->G.p,
@@ -969,40 +964,19 @@ int finish_ragged(bk_ctx *c, Collect *k, const int64_t *orders, const int64_t *o
         }
         // whole arrays, as the uniform entry's: the single finishes below fill
         // their own positions afterwards
-        CHK(timed(c, BK_K_D2H, [&] {
-            hipError_t e = hipMemcpyAsync(recs.data(), c->batch_rec.p,
-                                          ub * MARGIN_WORDS * sizeof(double), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(sel_idx, dsel, (size_t)selo[ub] * sizeof(int64_t),
-                                   hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess && scores)
-                e = hipMemcpyAsync(scores, dsc, (size_t)offsets[batch] * sizeof(double),
-                                   hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess && mean_out)
-                e = hipMemcpyAsync(mean_out, dmean, ub * (size_t)d * sizeof(double),
-                                   hipMemcpyDeviceToHost, st);
-            return e;
-        }));
-        HIPCHK(wait_stream(c));
+        CHK(batch_readback(c, k, batch, (size_t)offsets[batch], (size_t)selo[ub], recs.data(),
+                           sel_idx, scores, mean_out));
         drain.armed = false;
     }
-    for (const int64_t b : single) {
-        CHK(finish_checked(c, k, orders + offsets[b], offsets[b + 1] - offsets[b], fs[b],
-                           sel_idx + selo[(size_t)b], nullptr, scores ? scores + offsets[b] : nullptr,
-                           mean_out ? mean_out + b * d : nullptr));
-        memcpy(recs.data() + (size_t)b * MARGIN_WORDS, c->margin_host,
-               MARGIN_WORDS * sizeof(double));
-    }
+    for (const int64_t b : single)
+        CHK(finish_one_of_batch(c, k, orders + offsets[b], offsets[b + 1] - offsets[b], fs[b],
+                                sel_idx + selo[(size_t)b], scores ? scores + offsets[b] : nullptr,
+                                mean_out ? mean_out + b * d : nullptr,
+                                recs.data() + (size_t)b * MARGIN_WORDS));
     if (m_out)
         for (int64_t b = 0; b < batch; ++b) m_out[b] = offsets[b + 1] - offsets[b] - fs[b];
     c->batch_rec_h.swap(recs);
-    c->batch_one = 0;
-    c->batch_last = batch;
-    batch_pick_record(c);
-    c->margin_valid = 1;
-    c->margin_host = c->batch_pick;
-    c->margin_unchecked = 0;
-    return margin_status(c->batch_pick);  // an error code wins the pick: a give-up marks them all
+    return batch_close(c, batch);
 }
 
 }  // namespace
@@ -1044,22 +1018,9 @@ int bk_collect_finish_ragged(bk_ctx *c, const int64_t *orders, const int64_t *of
         }
     }
     {
-        // seen[o] = 1 + the last problem that used slot o
         std::vector<int64_t> seen((size_t)k->count, 0);
-        for (int64_t b = 0; b < batch; ++b) {
-            const int64_t n = offsets[b + 1] - offsets[b];
-            for (int64_t i = 0; i < n; ++i) {
-                const int64_t o = orders[offsets[b] + i];
-                if (o < 0 || o >= k->count)
-                    return fail(BK_EINVAL,
-                                "problem %lld: order[%lld] = %lld is no collected slot (0..%lld)",
-                                (long long)b, (long long)i, (long long)o, (long long)k->count - 1);
-                if (seen[(size_t)o] == b + 1)
-                    return fail(BK_EINVAL, "problem %lld: order[%lld] = %lld repeats a slot",
-                                (long long)b, (long long)i, (long long)o);
-                seen[(size_t)o] = b + 1;
-            }
-        }
+        for (int64_t b = 0; b < batch; ++b)
+            CHK(check_order(orders + offsets[b], offsets[b + 1] - offsets[b], k->count, seen, b));
     }
     DeviceGuard dg(c->device);
     return finish_ragged(c, k, orders, offsets, fs, batch, sel_idx, m_out, scores, mean_out);

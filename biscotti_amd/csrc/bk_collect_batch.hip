@@ -5,8 +5,9 @@
 // any permutation); every problem reads the same Gram and the same row store,
 // so there is no Gram phase and nothing is uploaded but the W x n slot numbers.
 // The item bodies and the hand-off code are bk_small_items.h's, shared with
-// k_collect_small; a translation unit of its own, so the kernels of
-// bk_small.hip and bk_small_batch.hip compile exactly as they did without it.
+// k_collect_small; so are the reset of the queue lines (collect_lines_reset,
+// shared with the ragged kernels) and the launcher's NB dispatch.  A
+// translation unit of its own.
 #include "bk_small_items.h"
 
 namespace bk {
@@ -62,11 +63,7 @@ __device__ __forceinline__ void collect_batch_last_out(const CollectBatchArgs &b
         for (int64_t i = tid; i < (int64_t)ba.W * ba.m; i += SMALL_NT) a.sel[i] = -1;
     }
     __syncthreads();
-    // only word 0 of each line is ever written
-    for (int w = tid; w < ba.W * CB_LINES; w += SMALL_NT)
-        __hip_atomic_store(a.ctr + 32 * (int64_t)w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < CBQ_LINES)
-        __hip_atomic_store(ba.qh + 32 * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    collect_lines_reset(a.ctr, ba.qh, ba.W, tid);
 }
 
 template <typename T, int NB>
@@ -150,20 +147,6 @@ __global__ __launch_bounds__(SMALL_NT) void k_collect_small_batch(CollectBatchAr
     if (last_out) collect_batch_last_out(ba, tid);
 }
 
-template <typename T>
-static void launch_collect_batch_t(const CollectBatchArgs &a, int NBv, int grid, hipStream_t st) {
-    switch (NBv) {
-    case 1: hipLaunchKernelGGL((k_collect_small_batch<T, 1>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_collect_small_batch<T, 2>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_collect_small_batch<T, 3>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_collect_small_batch<T, 4>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 5: hipLaunchKernelGGL((k_collect_small_batch<T, 5>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 6: hipLaunchKernelGGL((k_collect_small_batch<T, 6>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 7: hipLaunchKernelGGL((k_collect_small_batch<T, 7>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    default: hipLaunchKernelGGL((k_collect_small_batch<T, 8>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    }
-}
-
 hipError_t launch_collect_small_batch(const void *store, int dtype, int64_t ld, int W, int n,
                                       int64_t d, int f, const double *G, const uint16_t *orders,
                                       double *scores, double *diag, int64_t *sel, double *mean,
@@ -197,9 +180,9 @@ hipError_t launch_collect_small_batch(const void *store, int dtype, int64_t ld, 
     const int64_t total = (int64_t)W * (n + a.C);  // <= 1,024 x 640
     const int grid = total < num_cu ? (int)total : num_cu;
     if (dtype == 0)
-        launch_collect_batch_t<double>(ba, (n + 15) / 16, grid, st);
+        BK_NB_LAUNCH((n + 15) / 16, k_collect_small_batch, grid, st, ba, double)
     else
-        launch_collect_batch_t<float>(ba, (n + 15) / 16, grid, st);
+        BK_NB_LAUNCH((n + 15) / 16, k_collect_small_batch, grid, st, ba, float)
     return hipGetLastError();
 }
 

@@ -4,9 +4,10 @@
 // problem's view read from a descriptor, a queue map for unequal problem sizes
 // and the outputs at the caller's positions.  The item bodies, the hand-off
 // code and the queue lines are bk_small_items.h's, shared with k_collect_small
-// and k_collect_small_batch; a translation unit of its own, so the kernels of
-// bk_small.hip, bk_small_batch.hip and bk_collect_batch.hip compile exactly as
-// they did without it.
+// and k_collect_small_batch; so are the argument block (CollectRaggedArgs), the
+// problem's view (uni, collect_ragged_view), the last workgroup's reset
+// (collect_ragged_last_out) and the launcher's argument fill, shared with
+// k_collect_wide_ragged (bk_collect_wide.hip).  A translation unit of its own.
 #include "bk_small_items.h"
 
 namespace bk {
@@ -31,69 +32,6 @@ namespace bk {
 // before the launch and by nothing in it.  The last workgroup out resets the
 // launch's lines and every problem's; a give-up in any wait marks EVERY problem
 // of the launch invalid (sel = -1, the record's timeout code).
-struct CollectRaggedArgs {
-    SmallArgs s;             // what the problems share (X = the row store, ld, d, C, spin_max) and
-                             // the bases of the caller-order outputs; ctr: problem 0's lines
-    const double *G;         // the collection's Gram by arrival slot, lower packed
-    const RaggedDesc *desc;  // W problems, in queue order
-    const int32_t *seg;      // W + 2 segment starts
-    const uint16_t *orders;  // the packed arrival slots (desc[p].ord)
-    int W, total, lead;      // problems; items (seg[W + 1]); the leading S items (S_0 and S_1)
-    unsigned *qh;            // the launch's own lines: CBQ_HEAD and CBQ_ERR
-};
-
-// a wave-uniform value into scalar registers.  The descriptors and the segment
-// starts are loaded by vector loads (the kernel stores to global memory, so the
-// compiler keeps such loads off the scalar path); every lane reads the same word
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int64_t uni(int64_t v) {
-    return (int64_t)(((uint64_t)(uint32_t)uni((int)((uint64_t)v >> 32)) << 32) |
-                     (uint32_t)uni((int)v));
-}
-
-// problem p's view of the arguments (p wave-uniform): its descriptor, read once
-// per dequeued item.  Returns the offset of its order
-__device__ __forceinline__ int64_t collect_ragged_view(SmallArgs &b, const RaggedDesc *desc, int p) {
-    const RaggedDesc &r = desc[p];
-    const int idx = uni(r.idx);
-    const int64_t sc = uni(r.sc);
-    b.n = uni(r.n);
-    b.f = uni(r.f);
-    b.nS = b.n;
-    b.scores += sc;
-    b.diag += sc;
-    if (b.mean) b.mean += (int64_t)idx * b.d;
-    b.margin += (int64_t)idx * MARGIN_WORDS;
-    b.sel += uni(r.so);
-    b.ctr += (int64_t)p * (CB_LINES * 32);
-    return uni(r.ord);
-}
-
-__device__ __forceinline__ void collect_ragged_last_out(const CollectRaggedArgs &ra, int tid) {
-    __shared__ unsigned s_err;
-    const SmallArgs &a = ra.s;
-    if (tid == 0) s_err = ctr_load(cline(ra.qh, CBQ_ERR));
-    __syncthreads();
-    if (s_err) {  // a wait gave up: every problem of the launch is invalid (small_last_out)
-        for (int p = tid; p < ra.W; p += SMALL_NT) {
-            const int64_t at = (int64_t)ra.desc[p].idx * MARGIN_WORDS;
-            a.margin[at] = __builtin_nan("");
-            a.margin[at + 2] = MARGIN_HANDOFF_TIMEOUT;
-        }
-        for (int p = 0; p < ra.W; ++p) {
-            const int m = ra.desc[p].m;
-            int64_t *sel = a.sel + ra.desc[p].so;
-            for (int i = tid; i < m; i += SMALL_NT) sel[i] = -1;
-        }
-    }
-    __syncthreads();
-    // only word 0 of each line is ever written
-    for (int w = tid; w < ra.W * CB_LINES; w += SMALL_NT)
-        __hip_atomic_store(a.ctr + 32 * (int64_t)w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < CBQ_LINES)
-        __hip_atomic_store(ra.qh + 32 * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 template <typename T, int NB>
 __global__ __launch_bounds__(SMALL_NT) void k_collect_small_ragged(CollectRaggedArgs ra) {
     __shared__ int s_item;
@@ -167,20 +105,6 @@ __global__ __launch_bounds__(SMALL_NT) void k_collect_small_ragged(CollectRagged
     if (last_out) collect_ragged_last_out(ra, tid);
 }
 
-template <typename T>
-static void launch_collect_ragged_t(const CollectRaggedArgs &a, int NBv, int grid, hipStream_t st) {
-    switch (NBv) {
-    case 1: hipLaunchKernelGGL((k_collect_small_ragged<T, 1>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_collect_small_ragged<T, 2>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_collect_small_ragged<T, 3>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_collect_small_ragged<T, 4>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 5: hipLaunchKernelGGL((k_collect_small_ragged<T, 5>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 6: hipLaunchKernelGGL((k_collect_small_ragged<T, 6>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 7: hipLaunchKernelGGL((k_collect_small_ragged<T, 7>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    default: hipLaunchKernelGGL((k_collect_small_ragged<T, 8>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    }
-}
-
 // (the descriptors are the caller's to validate: every n in 16 NB - 15 .. 16 NB,
 // 0 <= f < n, m = n - f, the offsets inside the arrays; seg = ragged_seg_build
 // of the n's, total = seg[W + 1], lead = the S items of problems 0 and 1)
@@ -195,32 +119,13 @@ hipError_t launch_collect_small_ragged(const void *store, int dtype, int64_t ld,
         !margin || !lines)
         return hipErrorInvalidValue;
     CollectRaggedArgs ra = {};
-    SmallArgs &a = ra.s;
-    a.X = store;
-    a.ld = ld;
-    a.d = d;
-    a.C = mean ? (int)((d + 63) / 64) : 1;  // item 0 writes sel and the margin even without a mean
-    a.sm = 1;
-    a.scores = scores;
-    a.diag = diag;
-    a.mean = mean;
-    a.margin = margin;
-    a.sel = sel;
-    a.spin_max = spin_max;
-    ra.G = G;
-    ra.desc = desc;
-    ra.seg = seg;
-    ra.orders = orders;
-    ra.W = W;
-    ra.total = total;  // <= 1,024 x 640
-    ra.lead = lead;
-    ra.qh = lines;
-    a.ctr = lines + CBQ_LINES * 32;
+    collect_ragged_fill(ra, (int)((d + 63) / 64), store, ld, W, d, G, desc, seg, total, lead, orders,
+                        scores, diag, sel, mean, margin, lines, spin_max);
     const int grid = total < num_cu ? total : num_cu;
     if (dtype == 0)
-        launch_collect_ragged_t<double>(ra, NB, grid, st);
+        BK_NB_LAUNCH(NB, k_collect_small_ragged, grid, st, ra, double)
     else
-        launch_collect_ragged_t<float>(ra, NB, grid, st);
+        BK_NB_LAUNCH(NB, k_collect_small_ragged, grid, st, ra, float)
     return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // bk_collect_wide.hip -- the one-launch collection finishes for WIDE rows: n <=
 // 128 and 32,768 < d <= BK_COLLECT_WIDE_MAX_D, opted into by
-// bk_set_collect_wide (bk_collect.hip finish_wide, finish_ragged).
+// bk_set_collect_wide (bk_collect.hip finish_one_launch, finish_ragged).
 //
 // k_collect_small's cap on d belongs to k_small's G items; a collection finish
 // has none (the Gram exists), but its M items give every 64 columns an item of
@@ -20,20 +20,18 @@
 //                               map (ragged_seg_build / ragged_queue_decode
 //                               with collect_wide_items(d) M items per problem)
 //
-// A translation unit of its own: every other kernel compiles exactly as it did
-// without it.
+// The argument blocks (CollectSmallArgs, CollectRaggedArgs), the ragged
+// problem's view and reset (uni, collect_ragged_view, collect_ragged_invalidate,
+// collect_lines_reset) and the launchers' argument fill are k_collect_small's and
+// k_collect_small_ragged's own, from bk_small_items.h.  A translation unit of
+// its own.
 #include "bk_wide_items.h"
 
 namespace bk {
 
-struct CollectWideArgs {
-    SmallArgs s;  // gn = 0, sm = 1; X = the row store; C = the wide M items; part, U, trace unused
-    const double *G;
-    uint16_t order[128];
-};
-
+// (s.C = the wide M items)
 template <typename T, int NB>
-__global__ __launch_bounds__(SMALL_NT) void k_collect_wide(CollectWideArgs ca) {
+__global__ __launch_bounds__(SMALL_NT) void k_collect_wide(CollectSmallArgs ca) {
     __shared__ int s_item;
     __shared__ unsigned s_old;
     __shared__ __attribute__((aligned(16))) double gv[2 * 16 * NB];  // S: the Gram row, the diagonal
@@ -89,69 +87,15 @@ __global__ __launch_bounds__(SMALL_NT) void k_collect_wide(CollectWideArgs ca) {
     if (last_out) small_last_out(a, ctr, tid);
 }
 
-struct CollectWideRaggedArgs {
-    SmallArgs s;             // what the problems share (X = the row store, ld, d, C, spin_max) and
-                             // the bases of the caller-order outputs; ctr: problem 0's lines
-    const double *G;         // the collection's Gram by arrival slot, lower packed
-    const RaggedDesc *desc;  // W problems, in queue order
-    const int32_t *seg;      // W + 2 segment starts
-    const uint16_t *orders;  // the packed arrival slots (desc[p].ord)
-    int W, total, lead;      // problems; items (seg[W + 1]); the leading S items (S_0 and S_1)
-    unsigned *qh;            // the launch's own lines: CBQ_HEAD and CBQ_ERR
-};
-
-// a wave-uniform value into scalar registers (the descriptors and the segment
-// starts are loaded by vector loads; every lane reads the same word)
-__device__ __forceinline__ int wuni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int64_t wuni(int64_t v) {
-    return (int64_t)(((uint64_t)(uint32_t)wuni((int)((uint64_t)v >> 32)) << 32) |
-                     (uint32_t)wuni((int)v));
-}
-
-// problem p's view of the arguments (p wave-uniform), as k_collect_small_ragged
-// takes it from its descriptor.  Returns the offset of its order
-__device__ __forceinline__ int64_t wide_ragged_view(SmallArgs &b, const RaggedDesc *desc, int p) {
-    const RaggedDesc &r = desc[p];
-    const int idx = wuni(r.idx);
-    const int64_t sc = wuni(r.sc);
-    b.n = wuni(r.n);
-    b.f = wuni(r.f);
-    b.nS = b.n;
-    b.scores += sc;
-    b.diag += sc;
-    if (b.mean) b.mean += (int64_t)idx * b.d;
-    b.margin += (int64_t)idx * MARGIN_WORDS;
-    b.sel += wuni(r.so);
-    b.ctr += (int64_t)p * (CB_LINES * 32);
-    return wuni(r.ord);
-}
-
-// the last workgroup out: a give-up in any wait marks every problem of the
-// launch invalid (sel = -1, the record's time-out code), then the launch's
-// lines and every problem's go back to zero
-__device__ __forceinline__ void wide_ragged_last_out(const CollectWideRaggedArgs &ra, int tid) {
+// collect_ragged_last_out under this kernel's own name (see there: the name
+// decides where the kernel's LDS words lie)
+__device__ __forceinline__ void wide_ragged_last_out(const CollectRaggedArgs &ra, int tid) {
     __shared__ unsigned s_err;
-    const SmallArgs &a = ra.s;
     if (tid == 0) s_err = ctr_load(cline(ra.qh, CBQ_ERR));
     __syncthreads();
-    if (s_err) {
-        for (int p = tid; p < ra.W; p += SMALL_NT) {
-            const int64_t at = (int64_t)ra.desc[p].idx * MARGIN_WORDS;
-            a.margin[at] = __builtin_nan("");
-            a.margin[at + 2] = MARGIN_HANDOFF_TIMEOUT;
-        }
-        for (int p = 0; p < ra.W; ++p) {
-            const int m = ra.desc[p].m;
-            int64_t *sel = a.sel + ra.desc[p].so;
-            for (int i = tid; i < m; i += SMALL_NT) sel[i] = -1;
-        }
-    }
+    if (s_err) collect_ragged_invalidate(ra, tid);
     __syncthreads();
-    // only word 0 of each line is ever written
-    for (int w = tid; w < ra.W * CB_LINES; w += SMALL_NT)
-        __hip_atomic_store(a.ctr + 32 * (int64_t)w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < CBQ_LINES)
-        __hip_atomic_store(ra.qh + 32 * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    collect_lines_reset(ra.s.ctr, ra.qh, ra.W, tid);
 }
 
 // Queue order and invariant are k_collect_small_ragged's: the lag-one pipeline
@@ -159,7 +103,7 @@ __device__ __forceinline__ void wide_ragged_last_out(const CollectWideRaggedArgs
 // M_p waits for F_S of problem p alone, raised by S items earlier in the queue;
 // S items wait for nothing and the leading run of them is held by blockIdx.
 template <typename T, int NB>
-__global__ __launch_bounds__(SMALL_NT) void k_collect_wide_ragged(CollectWideRaggedArgs ra) {
+__global__ __launch_bounds__(SMALL_NT) void k_collect_wide_ragged(CollectRaggedArgs ra) {
     __shared__ int s_item;
     __shared__ unsigned s_old;
     __shared__ __attribute__((aligned(16))) double gv[2 * 16 * NB];  // S: the Gram row, the diagonal
@@ -191,10 +135,10 @@ __global__ __launch_bounds__(SMALL_NT) void k_collect_wide_ragged(CollectWideRag
         // global item -> (problem p, k_collect_wide's item number it of that problem)
         int p = 0, it = 0;
         if (git < total) ragged_queue_decode(ra.seg, ra.W, a.C, git, p, it);
-        p = wuni(p);
-        it = wuni(it);
+        p = uni(p);
+        it = uni(it);
         SmallArgs b = a;
-        const int64_t oo = wide_ragged_view(b, ra.desc, p);
+        const int64_t oo = collect_ragged_view(b, ra.desc, p);
         asm volatile("" : "+s"(b.n), "+s"(b.f), "+s"(b.C), "+s"(b.d), "+s"(b.ld));
         int ot = tid;
         asm volatile("" : "+v"(ot));
@@ -224,30 +168,6 @@ __global__ __launch_bounds__(SMALL_NT) void k_collect_wide_ragged(CollectWideRag
     if (last_out) wide_ragged_last_out(ra, tid);
 }
 
-#define BK_WIDE_NB_SWITCH(KERNEL, ARGS)                                                          \
-    switch (NBv) {                                                                               \
-    case 1: hipLaunchKernelGGL((KERNEL<T, 1>), dim3(grid), dim3(SMALL_NT), 0, st, ARGS); break;  \
-    case 2: hipLaunchKernelGGL((KERNEL<T, 2>), dim3(grid), dim3(SMALL_NT), 0, st, ARGS); break;  \
-    case 3: hipLaunchKernelGGL((KERNEL<T, 3>), dim3(grid), dim3(SMALL_NT), 0, st, ARGS); break;  \
-    case 4: hipLaunchKernelGGL((KERNEL<T, 4>), dim3(grid), dim3(SMALL_NT), 0, st, ARGS); break;  \
-    case 5: hipLaunchKernelGGL((KERNEL<T, 5>), dim3(grid), dim3(SMALL_NT), 0, st, ARGS); break;  \
-    case 6: hipLaunchKernelGGL((KERNEL<T, 6>), dim3(grid), dim3(SMALL_NT), 0, st, ARGS); break;  \
-    case 7: hipLaunchKernelGGL((KERNEL<T, 7>), dim3(grid), dim3(SMALL_NT), 0, st, ARGS); break;  \
-    default: hipLaunchKernelGGL((KERNEL<T, 8>), dim3(grid), dim3(SMALL_NT), 0, st, ARGS); break; \
-    }
-
-template <typename T>
-static void launch_collect_wide_t(const CollectWideArgs &a, int NBv, int grid, hipStream_t st) {
-    BK_WIDE_NB_SWITCH(k_collect_wide, a)
-}
-
-template <typename T>
-static void launch_collect_wide_ragged_t(const CollectWideRaggedArgs &a, int NBv, int grid,
-                                         hipStream_t st) {
-    BK_WIDE_NB_SWITCH(k_collect_wide_ragged, a)
-}
-#undef BK_WIDE_NB_SWITCH
-
 // the wide M item loads whole 16-B vectors of 16-B aligned rows: the row
 // store's layout (bk_collect_begin pads ld and zeroes the pad columns)
 static bool wide_rows_ok(const void *store, int dtype, int64_t ld) {
@@ -262,37 +182,16 @@ hipError_t launch_collect_wide(const void *store, int dtype, int64_t ld, int n, 
                                int check_lines) {
     if (n < 1 || n > 128 || d < 1 || ld < d || !wide_rows_ok(store, dtype, ld))
         return hipErrorInvalidValue;
-    CollectWideArgs ca = {};
-    SmallArgs &a = ca.s;
-    a.X = store;
-    a.ld = ld;
-    a.d = d;
-    a.n = n;
-    a.f = f;
-    a.nS = n;
-    a.C = mean ? collect_wide_items(d) : 1;  // item 0 writes sel and the margin even without a mean
-    a.sm = 1;
-    a.scores = scores;
-    a.diag = diag;
-    a.mean = mean;
-    a.margin = margin;
-    a.scores_out = scores_out;
-    a.sel = sel;
-    a.ctr = ctr;
-    a.spin_max = spin_max;
-    a.check_lines = check_lines;
-    ca.G = G;
-    for (int i = 0; i < n; ++i) {
-        const int64_t o = order ? order[i] : i;
-        if (o < 0 || o > 0xFFFF) return hipErrorInvalidValue;
-        ca.order[i] = (uint16_t)o;
-    }
-    const int total = n + a.C;
+    CollectSmallArgs ca = {};
+    if (!collect_small_fill(ca, collect_wide_items(d), store, ld, n, d, f, G, order, scores, diag, sel,
+                            mean, margin, scores_out, ctr, spin_max, check_lines))
+        return hipErrorInvalidValue;
+    const int total = n + ca.s.C;
     const int grid = total < num_cu ? total : num_cu;
     if (dtype == 0)
-        launch_collect_wide_t<double>(ca, (n + 15) / 16, grid, st);
+        BK_NB_LAUNCH((n + 15) / 16, k_collect_wide, grid, st, ca, double)
     else
-        launch_collect_wide_t<float>(ca, (n + 15) / 16, grid, st);
+        BK_NB_LAUNCH((n + 15) / 16, k_collect_wide, grid, st, ca, float)
     return hipGetLastError();
 }
 
@@ -307,33 +206,14 @@ hipError_t launch_collect_wide_ragged(const void *store, int dtype, int64_t ld, 
         lead < 1 || lead >= total || !G || !desc || !seg || !orders || !scores || !diag || !sel ||
         !margin || !lines || !wide_rows_ok(store, dtype, ld))
         return hipErrorInvalidValue;
-    CollectWideRaggedArgs ra = {};
-    SmallArgs &a = ra.s;
-    a.X = store;
-    a.ld = ld;
-    a.d = d;
-    a.C = mean ? collect_wide_items(d) : 1;  // item 0 writes sel and the margin even without a mean
-    a.sm = 1;
-    a.scores = scores;
-    a.diag = diag;
-    a.mean = mean;
-    a.margin = margin;
-    a.sel = sel;
-    a.spin_max = spin_max;
-    ra.G = G;
-    ra.desc = desc;
-    ra.seg = seg;
-    ra.orders = orders;
-    ra.W = W;
-    ra.total = total;  // <= 1,024 x (128 + 512)
-    ra.lead = lead;
-    ra.qh = lines;
-    a.ctr = lines + CBQ_LINES * 32;
+    CollectRaggedArgs ra = {};
+    collect_ragged_fill(ra, collect_wide_items(d), store, ld, W, d, G, desc, seg, total, lead, orders,
+                        scores, diag, sel, mean, margin, lines, spin_max);
     const int grid = total < num_cu ? total : num_cu;
     if (dtype == 0)
-        launch_collect_wide_ragged_t<double>(ra, NB, grid, st);
+        BK_NB_LAUNCH(NB, k_collect_wide_ragged, grid, st, ra, double)
     else
-        launch_collect_wide_ragged_t<float>(ra, NB, grid, st);
+        BK_NB_LAUNCH(NB, k_collect_wide_ragged, grid, st, ra, float)
     return hipGetLastError();
 }
 

@@ -310,6 +310,13 @@ int stage_finish(bk_ctx *c, const double *U, const Plan &pl, const void *dX, int
 constexpr size_t HOUT_MPAD = 16;  // doubles kept for the record at the head of c->hout
 int ensure_hout(bk_ctx *c, size_t words);
 int ensure_small_queue(bk_ctx *c);
+// the polls a wait of the next one-launch kernel may spend: the test knob's
+// (BK_SMALL_SPIN_MAX=<polls>[,<launches>]) while it has launches left
+inline uint64_t next_spin(bk_ctx *c) {
+    const uint64_t spin = c->small_spin_left == 0 ? SMALL_SPIN_MAX : c->small_spin_max;
+    if (c->small_spin_left > 0) --c->small_spin_left;
+    return spin;
+}
 bool small_ok(const bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d, int64_t ld);
 int run_small(bk_ctx *c, const void *dX, int dtype, int64_t n, int64_t d, int64_t ld, int64_t f,
               int64_t *d_sel, double *d_scores, double *d_mean, double *margin_out = nullptr,

@@ -152,15 +152,9 @@ __global__ __launch_bounds__(SMALL_NT) void k_small(SmallArgs a) {
 // row from G, the M items' staged rows from the row store (s.X, s.ld).  The
 // order travels in the kernel arguments (slots < BK_MAX_N fit 16 bits), so
 // nothing is uploaded before the launch; entries past n are 0.
-struct CollectSmallArgs {
-    SmallArgs s;  // gn = 0, sm = 1; X = the row store; part, U, trace unused
-    const double *G;
-    uint16_t order[128];
-};
-
-// (collect_row, the S item's first half, is bk_small_items.h's: shared with
-// k_collect_small_batch, bk_collect_batch.hip)
-
+// (CollectSmallArgs and collect_row, the S item's first half, are
+// bk_small_items.h's: shared with the other collection finishes.)
+//
 // Items 0..n-1 are the S items (the first min(n, grid) of them held by
 // blockIdx: they wait for nothing), items n.. the M items (always dequeued;
 // they wait for F_S, raised by S items, all numbered before them).  Queue
@@ -227,20 +221,6 @@ __global__ __launch_bounds__(SMALL_NT) void k_collect_small(CollectSmallArgs ca)
 template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void k_tiny(SmallArgs a) {
     tiny_body<T, VEC>(a);
-}
-
-template <typename T, bool VEC>
-static void launch_small_t(const SmallArgs &a, int NBv, int grid, hipStream_t st) {
-    switch (NBv) {
-    case 1: hipLaunchKernelGGL((k_small<T, VEC, 1>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_small<T, VEC, 2>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_small<T, VEC, 3>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_small<T, VEC, 4>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 5: hipLaunchKernelGGL((k_small<T, VEC, 5>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 6: hipLaunchKernelGGL((k_small<T, VEC, 6>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 7: hipLaunchKernelGGL((k_small<T, VEC, 7>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    default: hipLaunchKernelGGL((k_small<T, VEC, 8>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    }
 }
 
 bool tiny_ok(int n, int64_t d) {
@@ -315,28 +295,14 @@ hipError_t launch_small(const void *X, int dtype, int64_t ld, int n, int64_t d, 
         return hipGetLastError();
     }
     if (dtype == 0 && vec)
-        launch_small_t<double, true>(a, p.nb16, grid, st);
+        BK_NB_LAUNCH(p.nb16, k_small, grid, st, a, double, true)
     else if (dtype == 0)
-        launch_small_t<double, false>(a, p.nb16, grid, st);
+        BK_NB_LAUNCH(p.nb16, k_small, grid, st, a, double, false)
     else if (vec)
-        launch_small_t<float, true>(a, p.nb16, grid, st);
+        BK_NB_LAUNCH(p.nb16, k_small, grid, st, a, float, true)
     else
-        launch_small_t<float, false>(a, p.nb16, grid, st);
+        BK_NB_LAUNCH(p.nb16, k_small, grid, st, a, float, false)
     return hipGetLastError();
-}
-
-template <typename T>
-static void launch_collect_small_t(const CollectSmallArgs &a, int NBv, int grid, hipStream_t st) {
-    switch (NBv) {
-    case 1: hipLaunchKernelGGL((k_collect_small<T, 1>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_collect_small<T, 2>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_collect_small<T, 3>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_collect_small<T, 4>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 5: hipLaunchKernelGGL((k_collect_small<T, 5>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 6: hipLaunchKernelGGL((k_collect_small<T, 6>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 7: hipLaunchKernelGGL((k_collect_small<T, 7>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    default: hipLaunchKernelGGL((k_collect_small<T, 8>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    }
 }
 
 hipError_t launch_collect_small(const void *store, int dtype, int64_t ld, int n, int64_t d, int f,
@@ -346,36 +312,15 @@ hipError_t launch_collect_small(const void *store, int dtype, int64_t ld, int n,
                                 uint64_t spin_max, int check_lines) {
     if (n < 1 || n > 128) return hipErrorInvalidValue;
     CollectSmallArgs ca = {};
-    SmallArgs &a = ca.s;
-    a.X = store;
-    a.ld = ld;
-    a.d = d;
-    a.n = n;
-    a.f = f;
-    a.nS = n;
-    a.C = mean ? (int)((d + 63) / 64) : 1;  // item 0 writes sel and the margin even without a mean
-    a.sm = 1;
-    a.scores = scores;
-    a.diag = diag;
-    a.mean = mean;
-    a.margin = margin;
-    a.scores_out = scores_out;
-    a.sel = sel;
-    a.ctr = ctr;
-    a.spin_max = spin_max;
-    a.check_lines = check_lines;
-    ca.G = G;
-    for (int i = 0; i < n; ++i) {
-        const int64_t o = order ? order[i] : i;
-        if (o < 0 || o > 0xFFFF) return hipErrorInvalidValue;
-        ca.order[i] = (uint16_t)o;
-    }
-    const int total = n + a.C;
+    if (!collect_small_fill(ca, (int)((d + 63) / 64), store, ld, n, d, f, G, order, scores, diag, sel,
+                            mean, margin, scores_out, ctr, spin_max, check_lines))
+        return hipErrorInvalidValue;
+    const int total = n + ca.s.C;
     const int grid = total < num_cu ? total : num_cu;
     if (dtype == 0)
-        launch_collect_small_t<double>(ca, (n + 15) / 16, grid, st);
+        BK_NB_LAUNCH((n + 15) / 16, k_collect_small, grid, st, ca, double)
     else
-        launch_collect_small_t<float>(ca, (n + 15) / 16, grid, st);
+        BK_NB_LAUNCH((n + 15) / 16, k_collect_small, grid, st, ca, float)
     return hipGetLastError();
 }
 

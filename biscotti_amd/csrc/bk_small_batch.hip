@@ -161,20 +161,6 @@ __global__ __launch_bounds__(256) void k_tiny_batch(BatchArgs ba) {
     tiny_body<T, VEC>(b);
 }
 
-template <typename T, bool VEC>
-static void launch_small_batch_t(const BatchArgs &a, int NBv, int grid, hipStream_t st) {
-    switch (NBv) {
-    case 1: hipLaunchKernelGGL((k_small_batch<T, VEC, 1>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_small_batch<T, VEC, 2>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_small_batch<T, VEC, 3>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_small_batch<T, VEC, 4>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 5: hipLaunchKernelGGL((k_small_batch<T, VEC, 5>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 6: hipLaunchKernelGGL((k_small_batch<T, VEC, 6>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    case 7: hipLaunchKernelGGL((k_small_batch<T, VEC, 7>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    default: hipLaunchKernelGGL((k_small_batch<T, VEC, 8>), dim3(grid), dim3(SMALL_NT), 0, st, a); break;
-    }
-}
-
 hipError_t launch_small_batch(const void *X, int dtype, int64_t ld, int64_t stride, int W, int n,
                               int64_t d, int f, const SmallPlan &p, double *part, int64_t part_stride,
                               double *scores, double *diag, int64_t *sel, double *mean,
@@ -231,13 +217,13 @@ hipError_t launch_small_batch(const void *X, int dtype, int64_t ld, int64_t stri
     if (total > (int64_t)1 << 30) return hipErrorInvalidValue;
     const int grid = total < num_cu ? (int)total : num_cu;
     if (dtype == 0 && vec)
-        launch_small_batch_t<double, true>(ba, p.nb16, grid, st);
+        BK_NB_LAUNCH(p.nb16, k_small_batch, grid, st, ba, double, true)
     else if (dtype == 0)
-        launch_small_batch_t<double, false>(ba, p.nb16, grid, st);
+        BK_NB_LAUNCH(p.nb16, k_small_batch, grid, st, ba, double, false)
     else if (vec)
-        launch_small_batch_t<float, true>(ba, p.nb16, grid, st);
+        BK_NB_LAUNCH(p.nb16, k_small_batch, grid, st, ba, float, true)
     else
-        launch_small_batch_t<float, false>(ba, p.nb16, grid, st);
+        BK_NB_LAUNCH(p.nb16, k_small_batch, grid, st, ba, float, false)
     return hipGetLastError();
 }
 

@@ -1,11 +1,14 @@
 // bk_small_items.h -- the work items of the one-launch small path, shared by
 // the kernels of bk_small.hip (k_small, k_collect_small, k_tiny), of
 // bk_small_batch.hip (k_small_batch, k_tiny_batch), of bk_collect_batch.hip
-// (k_collect_small_batch) and of bk_collect_ragged.hip (k_collect_small_ragged):
-// the queue words, the write-through hand-off (arrive / raise / wait), the G, S
-// and M item bodies, the last workgroup's reset and k_tiny's body.
-// bk_small.hip's header comment describes the queue.  Private to those four
-// files.
+// (k_collect_small_batch), of bk_collect_ragged.hip (k_collect_small_ragged)
+// and, through bk_wide_items.h, of bk_collect_wide.hip (k_collect_wide,
+// k_collect_wide_ragged): the queue words, the write-through hand-off (arrive /
+// raise / wait), the G, S and M item bodies, the last workgroup's reset,
+// k_tiny's body, and for the collection finishes their argument blocks, the
+// ragged view and reset, the launchers' NB dispatch (BK_NB_LAUNCH) and argument
+// fill.  bk_small.hip's header comment describes the queue.  Private to those
+// five files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -746,6 +749,183 @@ __device__ __forceinline__ void small_last_out(const SmallArgs &a, unsigned *ctr
     __syncthreads();
     // only word 0 of each line is ever written (checked under check_lines)
     if (tid < C_LINES) __hip_atomic_store(ctr + 32 * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- what the one-launch collection finishes share (k_collect_small,
+// k_collect_small_batch, k_collect_small_ragged, k_collect_wide,
+// k_collect_wide_ragged): argument blocks, the ragged problems' view, the last
+// workgroup's reset and the launchers' argument fill.  The kernels' item loops
+// are NOT here: each kernel keeps its own, written out.
+
+// k_collect_small and k_collect_wide: the order travels in the kernel
+// arguments (slots < BK_MAX_N fit 16 bits), so nothing is uploaded before the
+// launch; entries past n are 0
+struct CollectSmallArgs {
+    SmallArgs s;  // gn = 0, sm = 1; X = the row store; C = the M items; part, U, trace unused
+    const double *G;
+    uint16_t order[128];
+};
+
+// k_collect_small_ragged and k_collect_wide_ragged
+struct CollectRaggedArgs {
+    SmallArgs s;             // what the problems share (X = the row store, ld, d, C, spin_max) and
+                             // the bases of the caller-order outputs; ctr: problem 0's lines
+    const double *G;         // the collection's Gram by arrival slot, lower packed
+    const RaggedDesc *desc;  // W problems, in queue order
+    const int32_t *seg;      // W + 2 segment starts
+    const uint16_t *orders;  // the packed arrival slots (desc[p].ord)
+    int W, total, lead;      // problems; items (seg[W + 1]); the leading S items (S_0 and S_1)
+    unsigned *qh;            // the launch's own lines: CBQ_HEAD and CBQ_ERR
+};
+
+// a wave-uniform value into scalar registers.  The descriptors and the segment
+// starts are loaded by vector loads (the kernel stores to global memory, so the
+// compiler keeps such loads off the scalar path); every lane reads the same word
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t uni(int64_t v) {
+    return (int64_t)(((uint64_t)(uint32_t)uni((int)((uint64_t)v >> 32)) << 32) |
+                     (uint32_t)uni((int)v));
+}
+
+// problem p's view of the arguments (p wave-uniform): its descriptor, read once
+// per dequeued item.  Returns the offset of its order
+__device__ __forceinline__ int64_t collect_ragged_view(SmallArgs &b, const RaggedDesc *desc, int p) {
+    const RaggedDesc &r = desc[p];
+    const int idx = uni(r.idx);
+    const int64_t sc = uni(r.sc);
+    b.n = uni(r.n);
+    b.f = uni(r.f);
+    b.nS = b.n;
+    b.scores += sc;
+    b.diag += sc;
+    if (b.mean) b.mean += (int64_t)idx * b.d;
+    b.margin += (int64_t)idx * MARGIN_WORDS;
+    b.sel += uni(r.so);
+    b.ctr += (int64_t)p * (CB_LINES * 32);
+    return uni(r.ord);
+}
+
+// the last workgroup out of a batched or ragged launch: every problem's lines
+// (ctr: problem 0's) and the launch's own go back to zero
+__device__ __forceinline__ void collect_lines_reset(unsigned *ctr, unsigned *qh, int W, int tid) {
+    // only word 0 of each line is ever written
+    for (int w = tid; w < W * CB_LINES; w += SMALL_NT)
+        __hip_atomic_store(ctr + 32 * (int64_t)w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid < CBQ_LINES)
+        __hip_atomic_store(qh + 32 * tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a wait of a ragged launch gave up: every problem of the launch is invalid
+// (sel = -1, the record's time-out code: small_last_out)
+__device__ __forceinline__ void collect_ragged_invalidate(const CollectRaggedArgs &ra, int tid) {
+    const SmallArgs &a = ra.s;
+    for (int p = tid; p < ra.W; p += SMALL_NT) {
+        const int64_t at = (int64_t)ra.desc[p].idx * MARGIN_WORDS;
+        a.margin[at] = __builtin_nan("");
+        a.margin[at + 2] = MARGIN_HANDOFF_TIMEOUT;
+    }
+    for (int p = 0; p < ra.W; ++p) {
+        const int m = ra.desc[p].m;
+        int64_t *sel = a.sel + ra.desc[p].so;
+        for (int i = tid; i < m; i += SMALL_NT) sel[i] = -1;
+    }
+}
+
+// the last workgroup out of a ragged launch: a give-up in any wait marks every
+// problem invalid, then the lines are reset.  (k_collect_wide_ragged keeps
+// these six lines under a name of its own, wide_ragged_last_out: the compiler
+// places a kernel's LDS words by name, this s_err's includes the function's,
+// and the kernel's LDS offsets are held to what they were)
+__device__ __forceinline__ void collect_ragged_last_out(const CollectRaggedArgs &ra, int tid) {
+    __shared__ unsigned s_err;
+    if (tid == 0) s_err = ctr_load(cline(ra.qh, CBQ_ERR));
+    __syncthreads();
+    if (s_err) collect_ragged_invalidate(ra, tid);
+    __syncthreads();
+    collect_lines_reset(ra.s.ctr, ra.qh, ra.W, tid);
+}
+
+// The launchers' dispatch over NB = ceil(n / 16): KERNEL<..., NB> (the leading
+// template arguments follow ARGS) on GRID workgroups of SMALL_NT threads
+#define BK_NB_CASE(NB, KERNEL, GRID, ST, ARGS, ...) \
+    hipLaunchKernelGGL((KERNEL<__VA_ARGS__, NB>), dim3(GRID), dim3(SMALL_NT), 0, ST, ARGS)
+#define BK_NB_LAUNCH(NBV, KERNEL, GRID, ST, ARGS, ...)                      \
+    switch (NBV) {                                                          \
+    case 1: BK_NB_CASE(1, KERNEL, GRID, ST, ARGS, __VA_ARGS__); break;      \
+    case 2: BK_NB_CASE(2, KERNEL, GRID, ST, ARGS, __VA_ARGS__); break;      \
+    case 3: BK_NB_CASE(3, KERNEL, GRID, ST, ARGS, __VA_ARGS__); break;      \
+    case 4: BK_NB_CASE(4, KERNEL, GRID, ST, ARGS, __VA_ARGS__); break;      \
+    case 5: BK_NB_CASE(5, KERNEL, GRID, ST, ARGS, __VA_ARGS__); break;      \
+    case 6: BK_NB_CASE(6, KERNEL, GRID, ST, ARGS, __VA_ARGS__); break;      \
+    case 7: BK_NB_CASE(7, KERNEL, GRID, ST, ARGS, __VA_ARGS__); break;      \
+    default: BK_NB_CASE(8, KERNEL, GRID, ST, ARGS, __VA_ARGS__); break;     \
+    }
+
+// launch_collect_small's and launch_collect_wide's arguments, C M items (1
+// without a mean: item 0 writes sel and the margin even then); false when a
+// slot does not fit the 16-bit order
+static inline bool collect_small_fill(CollectSmallArgs &ca, int C, const void *store, int64_t ld,
+                                      int n, int64_t d, int f, const double *G,
+                                      const int64_t *order, double *scores, double *diag,
+                                      int64_t *sel, double *mean, double *margin,
+                                      double *scores_out, unsigned *ctr, uint64_t spin_max,
+                                      int check_lines) {
+    SmallArgs &a = ca.s;
+    a.X = store;
+    a.ld = ld;
+    a.d = d;
+    a.n = n;
+    a.f = f;
+    a.nS = n;
+    a.C = mean ? C : 1;
+    a.sm = 1;
+    a.scores = scores;
+    a.diag = diag;
+    a.mean = mean;
+    a.margin = margin;
+    a.scores_out = scores_out;
+    a.sel = sel;
+    a.ctr = ctr;
+    a.spin_max = spin_max;
+    a.check_lines = check_lines;
+    ca.G = G;
+    for (int i = 0; i < n; ++i) {
+        const int64_t o = order ? order[i] : i;
+        if (o < 0 || o > 0xFFFF) return false;
+        ca.order[i] = (uint16_t)o;
+    }
+    return true;
+}
+
+// launch_collect_small_ragged's and launch_collect_wide_ragged's arguments, C M
+// items per problem (1 without a mean)
+static inline void collect_ragged_fill(CollectRaggedArgs &ra, int C, const void *store, int64_t ld,
+                                       int W, int64_t d, const double *G, const RaggedDesc *desc,
+                                       const int32_t *seg, int total, int lead,
+                                       const uint16_t *orders, double *scores, double *diag,
+                                       int64_t *sel, double *mean, double *margin, unsigned *lines,
+                                       uint64_t spin_max) {
+    SmallArgs &a = ra.s;
+    a.X = store;
+    a.ld = ld;
+    a.d = d;
+    a.C = mean ? C : 1;
+    a.sm = 1;
+    a.scores = scores;
+    a.diag = diag;
+    a.mean = mean;
+    a.margin = margin;
+    a.sel = sel;
+    a.spin_max = spin_max;
+    ra.G = G;
+    ra.desc = desc;
+    ra.seg = seg;
+    ra.orders = orders;
+    ra.W = W;
+    ra.total = total;  // <= 1,024 x (128 + 512)
+    ra.lead = lead;
+    ra.qh = lines;
+    a.ctr = lines + CBQ_LINES * 32;
 }
 
 // k_tiny: the whole call in ONE workgroup for n <= 16, d <= 128 (config A,
