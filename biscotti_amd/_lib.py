@@ -14,6 +14,7 @@ BK_F64, BK_F32 = 0, 1
 BK_HOST, BK_HOST_PINNED, BK_DEVICE = 0, 1, 2
 BK_MAX_N = 16384
 BK_MAX_BATCH = 65536
+BK_COLLECT_NOISE_MAX_K = 64
 BK_UNIQUE_ID_BYTES = 128
 BK_SYNTH_FP32ROUND = 1
 BK_GROUP_ALLREDUCE, BK_GROUP_DETERMINISTIC, BK_GROUP_HOST_EXCHANGE = 0, 1, 2
@@ -98,6 +99,8 @@ SIGNATURES = {
     "bk_set_collect_wide": (_i, [_p, _i]),
     "bk_collect_begin": (_i, [_p, _i, _i64, _i64]),
     "bk_collect_add": (_i, [_p, _p, _i64, _i, _pi64]),
+    "bk_collect_add_noised": (_i, [_p, _p, _p, _i64, _i64, _i, _pi64]),
+    "bk_collect_read_rows": (_i, [_p, _p, _i64, _p]),
     "bk_collect_count": (_i, [_p, _pi64]),
     "bk_collect_finish": (_i, [_p, _p, _i64, _i64, _p, _p, _p, _p]),
     "bk_multikrum_batch_device": (_i, [_p, _p, _i, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p,

@@ -23,6 +23,10 @@
 // bk_set_collect_wide on, n <= 128 and 32,768 < d <= BK_COLLECT_WIDE_MAX_D take
 // one launch too: k_collect_wide, and k_collect_wide_ragged for the batched and
 // ragged entries (bk_collect_wide.hip).
+// bk_collect_add_noised takes an update as Delta and Noise: k_collect_noise
+// (bk_collect_noise.hip) adds the mean of the noise vectors to the arriving
+// rows in the store, one launch per group of up to BORDER_ROWS, before the
+// same border.
 // Every element of G is the same sum whatever the add's count and however many
 // rows are resident: chunk s covers the same columns, one wave sums a chunk's
 // products in lane order and the chunks are added in the same tree, so the
@@ -244,6 +248,10 @@ struct Collect {
     // every launch leaves them zero).  The records go to the context's batch
     // record store
     Buf b_order, b_horder, b_scores, b_diag, b_sel, b_mean, b_ctr;
+    // bk_collect_add_noised: the device staging of a launch's noise vectors
+    // (host rows) and the pointer table of a call's device rows with its pinned
+    // staging, grown on demand
+    Buf nstage, ntab, hntab;
     hipEvent_t ev_slot[RING_SLOTS] = {};
     bool slot_used[RING_SLOTS] = {};
     int ring_next = 0;
@@ -263,7 +271,7 @@ static void collect_batch_release(Collect *k) {
 void collect_destroy(Collect *k) {
     if (!k) return;
     for (Buf *b : {&k->store, &k->G, &k->P, &k->U, &k->sel, &k->slots, &k->scores, &k->mean,
-                   &k->mean_part, &k->order, &k->horder, &k->ring})
+                   &k->mean_part, &k->order, &k->horder, &k->ring, &k->nstage, &k->ntab, &k->hntab})
         if (b->p) (void)(b->pinned ? hipHostFree(b->p) : hipFree(b->p));
     collect_batch_release(k);
     for (hipEvent_t ev : k->ev_slot)
@@ -447,6 +455,144 @@ size_t wide_out_bytes() {
     return v > 0 && (size_t)v < dflt ? (size_t)v : dflt;
 }
 
+// the noise bytes one k_collect_noise launch may stage on the device:
+// BK_COLLECT_NOISE_STAGE_BYTES, read at the call; it may only lower the
+// default (256 MiB)
+size_t noise_stage_bytes() {
+    const size_t dflt = (size_t)256 << 20;
+    const char *e = getenv("BK_COLLECT_NOISE_STAGE_BYTES");
+    if (!e) return dflt;
+    const long long v = atoll(e);
+    return v > 0 && (size_t)v < dflt ? (size_t)v : dflt;
+}
+
+// bk_collect_add past its checks (the context mutex held): the rows copied into
+// the slots from count on, then their border
+int add_rows(bk_ctx *c, Collect *k, const void *const *rows, int64_t count, int where,
+             int64_t *first_slot) {
+    DeviceGuard dg(c->device);
+    const hipStream_t st = c->stream;
+    Drain drain{st};
+    const size_t es = esize(k->dtype), bytes = (size_t)k->d * es;
+    const int64_t j0 = k->count;
+    for (int64_t i = 0; i < count; ++i) {
+        char *dst = (char *)k->store.p + (size_t)(j0 + i) * (size_t)k->ld * es;
+        if (where == BK_HOST)
+            CHK(upload_pageable(k, dst, (const char *)rows[i], bytes, st));
+        else
+            HIPCHK(hipMemcpyAsync(dst, rows[i], bytes,
+                                  where == BK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                  st));
+    }
+    if (where != BK_HOST) HIPCHK(hipEventRecord(k->ev_up, st));
+    CHK(fold_border(k, j0, count, c->num_cu, st));
+    // pinned and device rows are read by the copies themselves: consumed once
+    // those are done (the border runs on)
+    if (where != BK_HOST) HIPCHK(hipEventSynchronize(k->ev_up));
+    drain.armed = false;
+    k->count = j0 + count;
+    if (first_slot) *first_slot = j0;
+    return BK_OK;
+}
+
+// bk_collect_add_noised past its checks, k >= 1 (fp64 collection, the context
+// mutex held).  Host rows: every delta goes to its store row as add_rows
+// uploads it, the noise vectors of a launch to the staging block, and
+// k_collect_noise adds them in place.  Device rows: the kernel reads the
+// caller's deltas and, through one uploaded pointer table, its noise vectors
+// where they are.  A launch covers up to BORDER_ROWS rows, as many as the
+// staging bound holds; a row whose k vectors exceed it is noised in consecutive
+// ranges of an even number of columns (every element is independent: the same
+// bits however the call is cut).  Then the border of the new slots
+int add_noised(bk_ctx *c, Collect *k, const double *const *deltas, const double *const *noises,
+               int64_t kn, int64_t count, int where, int64_t *first_slot) {
+    static_assert(COLLECT_NOISE_ROWS == BORDER_ROWS, "one noise launch per border group");
+    DeviceGuard dg(c->device);
+    const hipStream_t st = c->stream;
+    const int64_t j0 = k->count, d = k->d;
+    const size_t bytes = (size_t)d * sizeof(double);
+    const bool dev = where == BK_DEVICE;
+    // rows per launch and columns per range
+    int64_t fit = BORDER_ROWS, wcols = d;
+    if (dev) {
+        const size_t tb = (size_t)count * (size_t)kn * sizeof(double *);
+        // (a launch of an earlier add may still read the block about to be replaced)
+        if (tb > k->ntab.bytes) HIPCHK(hipStreamSynchronize(st));
+        CHK(grow_all({{&k->ntab, tb}, {&k->hntab, tb}}, "bk_collect_add_noised"));
+    } else {
+        const size_t bound = noise_stage_bytes();
+        const size_t row = (size_t)kn * (size_t)((d + 1) & ~(int64_t)1) * sizeof(double);
+        if (row <= bound) {
+            fit = (int64_t)(bound / row) < fit ? (int64_t)(bound / row) : fit;
+            if (fit > count) fit = count;
+        } else {
+            fit = 1;
+            wcols = (int64_t)(bound / ((size_t)kn * sizeof(double))) & ~(int64_t)1;
+            if (wcols < 2) wcols = 2;
+        }
+        const size_t need = (size_t)fit * (size_t)kn * (size_t)((wcols + 1) & ~(int64_t)1) * sizeof(double);
+        if (need > k->nstage.bytes) HIPCHK(hipStreamSynchronize(st));
+        CHK(grow_all({{&k->nstage, need}}, "bk_collect_add_noised"));
+    }
+    Drain drain{st};
+    double *store = (double *)k->store.p;
+    if (dev) {
+        const double **ht = (const double **)k->hntab.p;
+        for (int64_t q = 0; q < count * kn; ++q) ht[q] = noises[q];
+        HIPCHK(hipMemcpyAsync(k->ntab.p, ht, (size_t)count * (size_t)kn * sizeof(double *),
+                              hipMemcpyHostToDevice, st));
+    } else {
+        for (int64_t i = 0; i < count; ++i) {
+            char *dst = (char *)(store + (j0 + i) * k->ld);
+            if (where == BK_HOST)
+                CHK(upload_pageable(k, dst, (const char *)deltas[i], bytes, st));
+            else
+                HIPCHK(hipMemcpyAsync(dst, deltas[i], bytes, hipMemcpyHostToDevice, st));
+        }
+    }
+    for (int64_t r0 = 0; r0 < count; r0 += fit) {
+        const int nr = (int)(count - r0 < fit ? count - r0 : fit);
+        for (int64_t c0 = 0; c0 < d; c0 += wcols) {
+            const int64_t c1 = c0 + wcols < d ? c0 + wcols : d;
+            CollectNoiseArgs a = {};
+            a.sld = (c1 - c0 + 1) & ~(int64_t)1;
+            a.c0 = c0;
+            a.c1 = c1;
+            a.rows = nr;
+            a.k = (int)kn;
+            if (dev)
+                a.tab = (const double *const *)k->ntab.p + r0 * kn;
+            else
+                a.stage = (const double *)k->nstage.p;
+            for (int r = 0; r < nr; ++r) {
+                a.out[r] = store + (j0 + r0 + r) * k->ld;
+                a.delta[r] = dev ? deltas[r0 + r] : a.out[r];
+                for (int64_t j = 0; j < kn && !dev; ++j) {
+                    char *dst = (char *)(k->nstage.p) + (size_t)((r * kn + j) * a.sld) * sizeof(double);
+                    const char *src = (const char *)(noises[(r0 + r) * kn + j] + c0);
+                    const size_t len = (size_t)(c1 - c0) * sizeof(double);
+                    if (where == BK_HOST)
+                        CHK(upload_pageable(k, dst, src, len, st));
+                    else
+                        HIPCHK(hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, st));
+                }
+            }
+            // pinned rows are read by the copies: consumed with the last of them
+            if (where == BK_HOST_PINNED && r0 + nr == count && c1 == d)
+                HIPCHK(hipEventRecord(k->ev_up, st));
+            CHK(timed(c, BK_K_NOISE, [&] { return launch_collect_noise(a, c->num_cu, st); }));
+        }
+    }
+    // device rows are read by the kernel itself: consumed with the last launch
+    if (dev) HIPCHK(hipEventRecord(k->ev_up, st));
+    CHK(fold_border(k, j0, count, c->num_cu, st));
+    if (where != BK_HOST) HIPCHK(hipEventSynchronize(k->ev_up));  // (the border runs on)
+    drain.armed = false;
+    k->count = j0 + count;
+    if (first_slot) *first_slot = j0;
+    return BK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -466,7 +612,7 @@ int bk_collect_begin(bk_ctx *c, int dtype, int64_t n_cap, int64_t d) {
     if (!k) {
         k = new (std::nothrow) Collect();
         if (!k) return fail(BK_ENOMEM, "host allocation of the collection failed");
-        k->horder.pinned = k->ring.pinned = k->b_horder.pinned = true;
+        k->horder.pinned = k->ring.pinned = k->b_horder.pinned = k->hntab.pinned = true;
         hipError_t e = hipEventCreateWithFlags(&k->ev_up, hipEventDisableTiming);
         for (int s = 0; s < RING_SLOTS && e == hipSuccess; ++s)
             e = hipEventCreateWithFlags(&k->ev_slot[s], hipEventDisableTiming);
@@ -537,28 +683,65 @@ int bk_collect_add(bk_ctx *c, const void *const *rows, int64_t count, int where,
                     (long long)count, (long long)k->n_cap, (long long)k->count);
     for (int64_t i = 0; i < count; ++i)
         if (!rows[i]) return fail(BK_EINVAL, "null row %lld", (long long)i);
+    return add_rows(c, k, rows, count, where, first_slot);
+}
+
+int bk_collect_add_noised(bk_ctx *c, const double *const *deltas, const double *const *noises,
+                          int64_t kn, int64_t count, int where, int64_t *first_slot) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!deltas) return fail(BK_EINVAL, "null deltas");
+    if (count < 1) return fail(BK_EINVAL, "need count >= 1 (count=%lld)", (long long)count);
+    if (kn < 0) return fail(BK_EINVAL, "need k >= 0 (k=%lld)", (long long)kn);
+    if (!noises && kn > 0) return fail(BK_EINVAL, "null noises with k=%lld", (long long)kn);
+    if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
+        return fail(BK_EINVAL, "bad where %d", where);
+    if (kn > BK_COLLECT_NOISE_MAX_K)
+        return fail(BK_ENOTSUP, "k=%lld exceeds BK_COLLECT_NOISE_MAX_K=%d", (long long)kn,
+                    BK_COLLECT_NOISE_MAX_K);
+    std::lock_guard<std::mutex> lk(c->mu);
+    Collect *k = c->collect;
+    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_add_noised without bk_collect_begin");
+    if (k->dtype != BK_F64)
+        return fail(BK_EINVAL, "bk_collect_add_noised: the collection is BK_F32 (noise is fp64 only)");
+    if (count > k->n_cap - k->count)
+        return fail(BK_EINVAL, "bk_collect_add_noised: %lld rows past n_cap=%lld (%lld collected)",
+                    (long long)count, (long long)k->n_cap, (long long)k->count);
+    for (int64_t i = 0; i < count; ++i) {
+        if (!deltas[i]) return fail(BK_EINVAL, "null delta %lld", (long long)i);
+        for (int64_t j = 0; j < kn; ++j)
+            if (!noises[i * kn + j])
+                return fail(BK_EINVAL, "null noise vector (%lld, %lld)", (long long)i, (long long)j);
+    }
+    // no noisers: the row is the delta, bitwise (bk_multikrum_noised's rule)
+    if (kn == 0)
+        return add_rows(c, k, (const void *const *)deltas, count, where, first_slot);
+    return add_noised(c, k, deltas, noises, kn, count, where, first_slot);
+}
+
+int bk_collect_read_rows(bk_ctx *c, const int64_t *slots, int64_t count, double *const *out_rows) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!slots) return fail(BK_EINVAL, "null slots");
+    if (!out_rows) return fail(BK_EINVAL, "null out_rows");
+    if (count < 1) return fail(BK_EINVAL, "need count >= 1 (count=%lld)", (long long)count);
+    std::lock_guard<std::mutex> lk(c->mu);
+    Collect *k = c->collect;
+    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_read_rows without bk_collect_begin");
+    if (k->dtype != BK_F64)
+        return fail(BK_EINVAL, "bk_collect_read_rows: the collection is BK_F32 (fp64 rows only)");
+    for (int64_t i = 0; i < count; ++i)
+        if (slots[i] < 0 || slots[i] >= k->count)
+            return fail(BK_EINVAL, "slots[%lld] = %lld is no collected slot (0..%lld)", (long long)i,
+                        (long long)slots[i], (long long)k->count - 1);
+    for (int64_t i = 0; i < count; ++i)
+        if (!out_rows[i]) return fail(BK_EINVAL, "null output row %lld", (long long)i);
     DeviceGuard dg(c->device);
     const hipStream_t st = c->stream;
     Drain drain{st};
-    const size_t es = esize(k->dtype), bytes = (size_t)k->d * es;
-    const int64_t j0 = k->count;
-    for (int64_t i = 0; i < count; ++i) {
-        char *dst = (char *)k->store.p + (size_t)(j0 + i) * (size_t)k->ld * es;
-        if (where == BK_HOST)
-            CHK(upload_pageable(k, dst, (const char *)rows[i], bytes, st));
-        else
-            HIPCHK(hipMemcpyAsync(dst, rows[i], bytes,
-                                  where == BK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                  st));
-    }
-    if (where != BK_HOST) HIPCHK(hipEventRecord(k->ev_up, st));
-    CHK(fold_border(k, j0, count, c->num_cu, st));
-    // pinned and device rows are read by the copies themselves: consumed once
-    // those are done (the border runs on)
-    if (where != BK_HOST) HIPCHK(hipEventSynchronize(k->ev_up));
+    for (int64_t i = 0; i < count; ++i)
+        HIPCHK(hipMemcpyAsync(out_rows[i], (const double *)k->store.p + slots[i] * k->ld,
+                              (size_t)k->d * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     drain.armed = false;
-    k->count = j0 + count;
-    if (first_slot) *first_slot = j0;
     return BK_OK;
 }
 

@@ -424,6 +424,25 @@ hipError_t launch_collect_wide_ragged(const void *store, int dtype, int64_t ld, 
                                       uint64_t spin_max = SMALL_SPIN_MAX);
 hipError_t launch_synth(void *X, int dtype, int64_t ld, int64_t n, int64_t dl, int64_t c0,
                         const int64_t *perm, const SynthParams &P, hipStream_t st);
+// bk_collect_noise.hip, k_collect_noise (bk_collect_add_noised): one launch adds
+// the mean of its k noise vectors to each of `rows` arriving fp64 rows over the
+// columns [c0, c1) (c0 even; c1 even or d), K6's arithmetic: out[r][c] =
+// delta[r][c] + ((0 + v_0[c]) + ... + v_{k-1}[c]) / k, k >= 1.  delta[r] may be
+// out[r] (in place).  Row r's vector j is tab[r k + j] (tab in device memory:
+// the caller's device rows, 8-B aligned at least), or, with tab null, lies in
+// the staging block at stage + (r k + j) sld, its column c at [c - c0] (stage
+// 16-B aligned, sld even).  out[r] is 16-B aligned; only columns [c0, c1) of
+// it are written.  The tables travel in the kernel's arguments
+constexpr int COLLECT_NOISE_ROWS = 8;  // rows per launch: k_border's group (BORDER_ROWS)
+struct CollectNoiseArgs {
+    const double *delta[COLLECT_NOISE_ROWS];
+    double *out[COLLECT_NOISE_ROWS];
+    const double *const *tab;
+    const double *stage;
+    int64_t sld, c0, c1;
+    int rows, k;
+};
+hipError_t launch_collect_noise(const CollectNoiseArgs &a, int num_cu, hipStream_t st);
 
 // bk_collect.hip: the incremental collection of a context (bk_collect_*), which
 // owns its buffers; bk_destroy frees it (device selected, streams idle)

@@ -241,6 +241,57 @@ class Engine:
                                    ctypes.byref(first)))
         return first.value
 
+    def collect_add_noised(self, delta, noise=None):
+        """One noised update arrives as Delta and Noise (bk_collect_add_noised):
+        delta a 1-D float64 array of the collection's d; noise None (k = 0: the
+        row is delta), a vector of length d (k = 1) or a (k, d) array.  The
+        stored row is delta + (0 + v_0 + ... + v_{k-1}) / k, added on the
+        device.  Returns the arrival slot."""
+        if getattr(self, "_collect", None) is None:
+            raise ValueError("collect_add_noised without collect_begin")
+        dt, d = self._collect
+        if dt != np.float64:
+            raise ValueError("noise is float64 only: the collection is %s" % dt)
+        D = np.ascontiguousarray(delta, dtype=np.float64)
+        if D.ndim != 1 or D.shape[0] != d:
+            raise ValueError("delta must be a 1-D float64 array of length %d" % d)
+        if noise is None:
+            N = np.empty((0, d), dtype=np.float64)
+        else:
+            N = np.ascontiguousarray(noise, dtype=np.float64)
+            if N.ndim == 1:
+                N = N.reshape(1, -1)
+            if N.ndim != 2 or (N.shape[0] > 0 and N.shape[1] != d):
+                raise ValueError("noise must be None, a vector of length %d or a (k, %d) array"
+                                 % (d, d))
+        k = N.shape[0]
+        dp = (ctypes.c_void_p * 1)(D.ctypes.data)
+        nz = (ctypes.c_void_p * k)(*[N[j].ctypes.data for j in range(k)]) if k else None
+        return self.collect_add_noised_ptr(dp, nz, k, 1, _lib.BK_HOST)
+
+    def collect_add_noised_ptr(self, delta_ptrs, noise_ptrs, k, count, where):
+        """Raw pointers (ctypes c_void_p arrays): count deltas and count * k noise
+        vectors (vector j of update i at noise_ptrs[i * k + j]; None when k = 0),
+        all pageable, pinned or device rows."""
+        first = ctypes.c_int64(-1)
+        check(lib().bk_collect_add_noised(self._ctx, delta_ptrs, noise_ptrs, int(k), int(count),
+                                          int(where), ctypes.byref(first)))
+        return first.value
+
+    def collect_read_rows(self, slots):
+        """The stored rows of the named arrival slots (bk_collect_read_rows), a
+        (len(slots), d) float64 array: after a noised add, NoisedDelta."""
+        if getattr(self, "_collect", None) is None:
+            raise ValueError("collect_read_rows without collect_begin")
+        _, d = self._collect
+        slots = np.ascontiguousarray(np.atleast_1d(slots), dtype=np.int64)
+        if slots.ndim != 1 or len(slots) < 1:
+            raise ValueError("slots must list at least one arrival slot")
+        out = np.empty((len(slots), d), dtype=np.float64)
+        ptrs = (ctypes.c_void_p * len(slots))(*[out[i].ctypes.data for i in range(len(slots))])
+        check(lib().bk_collect_read_rows(self._ctx, slots.ctypes.data, len(slots), ptrs))
+        return out
+
     def collect_count(self):
         cnt = ctypes.c_int64(0)
         check(lib().bk_collect_count(self._ctx, ctypes.byref(cnt)))
@@ -721,13 +772,17 @@ class KRUMValidator:
     """DistSys/krum.go:22-29, with getTopKRUMIndex running on libbk."""
 
     def __init__(self, num_adversaries=0.5, engine: Optional[Engine] = None, device=0,
-                 collect=False, n_cap=128, wide=False):
+                 collect=False, n_cap=128, wide=False, noised=False):
         """collect=True (opt-in): add_update streams each update's NoisedDelta
         to the engine's collection as it arrives (bk_collect_add), and
         compute_scores only finishes (bk_collect_finish) in SourceID order;
         n_cap bounds the updates of one round (KRUM_UPDATETHRESH).  wide=True
         (with collect) turns the engine's wide one-launch finish on when the
-        round begins (Engine.set_collect_wide: the CNN models' d)."""
+        round begins (Engine.set_collect_wide: the CNN models' d).  noised=True
+        (with collect): add_update sends update.Delta and update.Noise through
+        the noised add (bk_collect_add_noised; k = 1 when Noise is present, k =
+        0 when it is absent, as the shim does), so NoisedDelta is never built on
+        the host; noised_delta(i) reads it back from the row store when asked."""
         self.UpdateList: List[Update] = []
         self.AcceptedList: List[int] = []
         self.NumAdversaries = num_adversaries  # fixed at 0.5 (main.go:783)
@@ -736,6 +791,9 @@ class KRUMValidator:
         self._collect = bool(collect)
         self._n_cap = int(n_cap)
         self._wide = bool(wide)
+        self._noised = bool(noised)
+        if self._noised and not self._collect:
+            raise ValueError("noised=True needs collect=True")
         self._slots: List[int] = []  # collect mode: arrival slot of UpdateList[i]
 
     def initialize(self):
@@ -755,13 +813,27 @@ class KRUMValidator:
         if self._collect:
             if self._engine is None:
                 self.initialize()
-            row = np.ascontiguousarray(update.NoisedDelta, dtype=np.float64)
+            row = np.ascontiguousarray(update.Delta if self._noised else update.NoisedDelta,
+                                       dtype=np.float64)
             if not self._slots:
                 if self._wide:
                     self._engine.set_collect_wide(True)
                 self._engine.collect_begin(self._n_cap, row.shape[0], np.float64)
-            self._slots.append(self._engine.collect_add(row))
+            if self._noised:
+                self._slots.append(self._engine.collect_add_noised(row, update.Noise))
+            else:
+                self._slots.append(self._engine.collect_add(row))
         self.UpdateList.append(update)
+
+    def noised_delta(self, i):
+        """noised mode: UpdateList[i].NoisedDelta, read back from the row store
+        on first use (bk_collect_read_rows) and kept on the update."""
+        if not self._noised:
+            raise ValueError("noised_delta needs KRUMValidator(collect=True, noised=True)")
+        u = self.UpdateList[i]
+        if u.NoisedDelta is None:
+            u.NoisedDelta = self._engine.collect_read_rows([self._slots[i]])[0]
+        return u.NoisedDelta
 
     def compute_scores(self):
         # krum.go:77-98

@@ -168,6 +168,51 @@ int bk_collect_begin(bk_ctx *ctx, int dtype, int64_t n_cap, int64_t d);
  * The resident rows are read once per group of up to 8 new rows. */
 int bk_collect_add(bk_ctx *ctx, const void *const *rows, int64_t count, int where,
                    int64_t *first_slot);
+/* count >= 1 NOISED updates arrive: Delta and Noise separately (update.go:13-22),
+ * as bk_multikrum_noised takes them, so the verifier never builds NoisedDelta on
+ * the host (main.go:1524-1537, 1606-1653).  deltas[i] points at d doubles,
+ * noises[i*k + j] at noise vector j of update i (d doubles; noises may be NULL
+ * only when k == 0); where applies to both: BK_HOST (pageable, any alignment),
+ * BK_HOST_PINNED, or BK_DEVICE (separately allocated device rows, 8-byte
+ * aligned, not necessarily 16).  Update i takes arrival slot *first_slot + i and
+ * the row stored there is, per element and in exactly this order (fp64, no
+ * contraction),
+ *     delta[c] + ((0 + v_0[c]) + v_1[c] + ... + v_{k-1}[c]) / (double)k
+ * -- the bits of bk_noise_apply_device.  k == 0 means no noisers: the stored row
+ * is delta bitwise (bk_multikrum_noised's rule, not the literal 0/0).
+ * One k_collect_noise launch noises up to 8 arriving rows whatever k is.  Device
+ * rows are read where they are, through a pointer table (no copy first).  Host
+ * deltas go to their store rows as bk_collect_add uploads them, the noise
+ * vectors to a device staging block owned by the collection (grown on demand,
+ * released with it), and the kernel adds them in place.  One launch stages at
+ * most BK_COLLECT_NOISE_STAGE_BYTES (environment, read at the call; it may lower
+ * the 256 MiB default): a launch covers as many rows as fit, and a row whose k
+ * vectors exceed the bound is noised in consecutive column ranges -- every
+ * element is independent, so any split gives the same bits.  Then the border of
+ * the new slots, as bk_collect_add's; the launches are timed under BK_K_NOISE.
+ * On return every input has been consumed and no pointer is retained (the cgo
+ * contract of bk_collect_add); the noise kernel and the border run on
+ * asynchronously on the context stream.  Plain and noised adds may be mixed
+ * freely within one collection.
+ * The checks, in this order, all before any copy, launch or state change (every
+ * error leaves the collection as it was): BK_EINVAL for a null ctx, null
+ * deltas, count < 1, k < 0, null noises with k > 0, a bad where; BK_ENOTSUP for
+ * k > BK_COLLECT_NOISE_MAX_K; then BK_EINVAL for a call without
+ * bk_collect_begin, a BK_F32 collection (noise is fp64 only, as
+ * bk_multikrum_noised), an add past n_cap, a null deltas[i] or noises[i*k + j]
+ * (the indices named).  The checks that need no collection need no GPU.
+ * Added without a change of BK_ABI_VERSION (14), as bk_set_collect_wide was. */
+#define BK_COLLECT_NOISE_MAX_K 64
+int bk_collect_add_noised(bk_ctx *ctx, const double *const *deltas,
+                          const double *const *noises, int64_t k, int64_t count,
+                          int where, int64_t *first_slot);
+/* The d stored doubles of each named arrival slot, copied to the host row
+ * out_rows[i] (count >= 1 of them); synchronous; fp64 collections only.  How the
+ * verifier gets NoisedDelta back for the block without recomputing it.
+ * BK_EINVAL: a null ctx, slots or out_rows; count < 1; a call without begin; a
+ * BK_F32 collection; a slot outside 0..collected-1 (named); a null output row. */
+int bk_collect_read_rows(bk_ctx *ctx, const int64_t *slots, int64_t count,
+                         double *const *out_rows);
 /* rows collected since the last begin (0 before any) */
 int bk_collect_count(bk_ctx *ctx, int64_t *count);
 /* Multi-Krum over n of the collected rows: order[i] = arrival slot of the caller's
@@ -712,7 +757,7 @@ enum bk_kernel_id {
     BK_K_D2H = 10,
     BK_K_AGGREGATE = 11, /* K4' block aggregation global += sum (bk_aggregate*) */
     BK_K_QSUM = 12,      /* K5  quantised int64 sum (bk_quantized_sum_device)  */
-    BK_K_NOISE = 13,     /* K6  noise application (bk_noise_apply_device)      */
+    BK_K_NOISE = 13,     /* K6  noise application (bk_noise_apply_device, bk_collect_add_noised) */
     BK_K_RONI = 14,      /* K7  RONI counts + scores (bk_roni*)                 */
     BK_K_SMALL = 15,     /* K1..K4 fused in one launch for n <= 128 (k_small)   */
     BK_K_SLICE = 16,     /* K1i8 digit slicing + error bound (BK_F32_I8)        */
