@@ -12,7 +12,7 @@
 //                 arrival order, divide by the float count) and :1524-1537.
 //
 // The plain block aggregation (GlobalW += sum of accepted Delta, in update
-// order, honest.go:361-375) is K4's ACCUM variant in bk_kernels.hip.
+// order, honest.go:361-375) is K4's ACCUM variant in bk_mean.hip.
 //
 // All three are one pass over HBM: 16 bytes per lane, columns across lanes,
 // rows (or noise vectors) as the sequential inner loop with 8 loads in flight.
@@ -33,7 +33,7 @@ __host__ __device__ __forceinline__ int64_t go_f64_to_i64(double y) {
     return INT64_MIN;
 }
 
-// used-once streaming reads: non-temporal (see ld2s in bk_kernels.hip)
+// used-once streaming reads: non-temporal (see ld2s in bk_device.h)
 template <typename T>
 __device__ __forceinline__ double ldv(const T *p) {
 #ifndef BK_NO_NT

@@ -1,15 +1,76 @@
-// bk_device.h -- device helpers shared by the kernels of libbk (bk_kernels.hip,
-// bk_small.hip): the total order of the row sort, the packed upper-tile
-// addressing, the register bitonic building blocks and the selection margin.
+// bk_device.h -- device helpers shared by the kernels of libbk (bk_gram.hip,
+// bk_scores.hip, bk_mean.hip, bk_small.hip): the vector types and row loads,
+// the workgroup and sub-tile index maps, the total order of the row sort, the
+// packed upper-tile addressing, the register bitonic building blocks and the
+// selection margin.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "bk_internal.h"
 
 namespace bk {
 
 typedef double d2v __attribute__((ext_vector_type(2)));
+typedef double d4v __attribute__((ext_vector_type(4)));
+typedef float f2v __attribute__((ext_vector_type(2)));
+typedef float f4v __attribute__((ext_vector_type(4)));
+
+// Bijective XCD remap (cdna_hip_programming.md T1): blocks b and b+8 share an
+// XCD, so give each XCD a contiguous range of logical workgroups.  Speed only.
+__device__ __forceinline__ int xcd_remap(int b, int nwg) {
+    const int q = nwg >> 3, r = nwg & 7, x = b & 7;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
+}
+
+// upper-triangle sub-tile u -> (bi, bj), bi <= bj, T blocks per side
+__device__ __forceinline__ void tri_decode(int u, int T, int &bi, int &bj) {
+    int i = 0, off = 0;
+    while (u >= off + (T - i)) { off += T - i; ++i; }
+    bi = i;
+    bj = i + (u - off);
+}
+
+template <typename T, bool VEC>
+__device__ __forceinline__ d2v ld2(const T *p) {
+    d2v r;
+    if constexpr (std::is_same<T, double>::value) {
+        if constexpr (VEC) {
+            r = *reinterpret_cast<const d2v *>(p);
+        } else {
+            r.x = p[0];
+            r.y = p[1];
+        }
+    } else {
+        if constexpr (VEC) {
+            const f2v v = *reinterpret_cast<const f2v *>(p);
+            r.x = (double)v.x;
+            r.y = (double)v.y;
+        } else {
+            r.x = (double)p[0];
+            r.y = (double)p[1];
+        }
+    }
+    return r;
+}
+
+// Streaming read of data used once (K4 and its aggregation variant): a
+// non-temporal load.  K4 at config D: 0.549 -> 0.495 ms (5.5 -> 6.1 TB/s,
+// profiles/r01/ab_mean_nt.log).  -DBK_NO_NT restores plain loads for A/B.
+template <typename T, bool VEC>
+__device__ __forceinline__ d2v ld2s(const T *p) {
+#ifndef BK_NO_NT
+    if constexpr (VEC && std::is_same<T, double>::value) {
+        return __builtin_nontemporal_load(reinterpret_cast<const d2v *>(p));
+    } else if constexpr (VEC) {
+        const f2v v = __builtin_nontemporal_load(reinterpret_cast<const f2v *>(p));
+        return d2v{(double)v.x, (double)v.y};
+    }
+#endif
+    return ld2<T, VEC>(p);
+}
 
 // total order on doubles for sorting / selection: ascending, +0 == -0, NaN last
 __device__ __forceinline__ uint64_t dkey(double v) {

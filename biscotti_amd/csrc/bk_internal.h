@@ -1,6 +1,7 @@
-// bk_internal.h -- what the kernel files (bk_kernels, bk_small, bk_small_batch, bk_i8,
-// bk_aggregate, bk_roni, bk_collect) and the planner (bk_plan) offer the files
-// that implement the C ABI: plans, layouts and launchers.  The context those
+// bk_internal.h -- what the kernel files (bk_gram, bk_scores, bk_mean, bk_small,
+// bk_small_batch, bk_i8, bk_aggregate, bk_roni, bk_collect) and the planner
+// (bk_plan) offer the files that implement the C ABI: plans, layouts and
+// launchers (and the launchers' shared row-type dispatch).  The context those
 // files share among themselves is bk_ctx.h, which the kernels never see.  Not
 // installed; the public surface is include/bk.h.
 #pragma once
@@ -8,6 +9,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "bk_synth.h"
@@ -178,7 +180,31 @@ bool plan3_pieces(const Plan3Host &H, int k, std::vector<int> &tile_end,
 // valid[b] whether a cut before block b is allowed; the pieces shrink
 // geometrically (x0.6) so the last exchange, the one left exposed, is small
 std::vector<int> piece_cuts(const std::vector<double> &w, const std::vector<char> &valid, int k);
-hipError_t configure_kernels();
+// the dynamic-LDS limits of the general chain's kernels, file by file
+// (bk_gram.hip, bk_scores.hip, bk_mean.hip)
+hipError_t configure_gram_kernels();
+hipError_t configure_scores_kernels();
+hipError_t configure_mean_kernels();
+inline hipError_t configure_kernels() {
+    hipError_t e = configure_gram_kernels();
+    if (e == hipSuccess) e = configure_scores_kernels();
+    if (e == hipSuccess) e = configure_mean_kernels();
+    return e;
+}
+// Rows of dtype (0: fp64, else fp32) that can be read as pairs of columns, one
+// 16-byte (fp64) or 8-byte (fp32) load each: an even ld and a base aligned to
+// a pair.  K1 v1 and K4 pick their VEC kernels by it
+inline bool rows_pair_aligned(const void *X, int dtype, int64_t ld) {
+    return (ld % 2) == 0 && ((uintptr_t)X % (dtype == 0 ? 16 : 8)) == 0;
+}
+// (dtype, vec) -> f(T(), std::bool_constant<VEC>()): T = double / float
+template <typename F>
+inline void with_row_type(int dtype, bool vec, F &&f) {
+    if (dtype == 0)
+        vec ? f(double(), std::true_type()) : f(double(), std::false_type());
+    else
+        vec ? f(float(), std::true_type()) : f(float(), std::false_type());
+}
 hipError_t launch_gram(const void *X, int dtype, int64_t ld, int n, int64_t d, const Plan &pl,
                        double *part, hipStream_t st);
 hipError_t launch_reduce(const double *part, const Plan &pl, double *U, hipStream_t st);
