@@ -7,6 +7,6 @@ driver (dist.py).
 """
 from . import _lib  # noqa: F401
 from .krum import (Engine, KRUMValidator, Update, default_engine, get_krum_scores,  # noqa: F401
-                   krum, krum_batch, krum_mean)
+                   krum, krum_batch, krum_mean, krum_ragged)
 
 __version__ = "0.1.0"

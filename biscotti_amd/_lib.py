@@ -108,6 +108,10 @@ SIGNATURES = {
     "bk_multikrum_batch": (_i, [_p, _p, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p,
                                 _p]),
     "bk_selection_margin_batch": (_i, [_p, _pd, _i64]),
+    "bk_multikrum_ragged_device": (_i, [_p, _p, _i, _i64, _p, _p, _i64, _i64, _p, _p, _p]),
+    "bk_multikrum_ragged": (_i, [_p, _p, _i, _i, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p]),
+    "bk_ragged_batch_queue_item": (_i, [_p, _i, _i, _i, _i64, ctypes.POINTER(_i),
+                                        ctypes.POINTER(_i)]),
     "bk_collect_finish_batch": (_i, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p]),
     "bk_collect_finish_ragged": (_i, [_p, _p, _p, _p, _i64, _p, _p, _p, _p]),
     "bk_ragged_queue_item": (_i, [_p, _i, _i, _i64, ctypes.POINTER(_i), ctypes.POINTER(_i)]),

@@ -218,9 +218,14 @@ void bk_destroy(bk_ctx *c) {
                           &c->mean_part, &c->status, &c->rmc_X, &c->rmc_y, &c->rmc_ws,
                       &c->rmc_xn, &c->rmc_idx, &c->rmc_nt, &c->i8ws, &c->sgather, &c->pcnt,
                           &c->batch_ctr, &c->batch_part, &c->batch_diag, &c->batch_scores,
-                          &c->batch_rec, &c->batch_X, &c->batch_sel, &c->batch_hsc, &c->batch_mean};
+                          &c->batch_rec, &c->batch_X, &c->batch_sel, &c->batch_hsc, &c->batch_mean,
+                          &c->batch_desc};
         if (c->hmargin) (void)hipHostFree(c->hmargin);
         if (c->hout) (void)hipHostFree(c->hout);
+        for (void *p : c->ragged_stage)
+            if (p) (void)hipHostFree(p);
+        for (hipEvent_t ev : c->ev_ragged)
+            if (ev) (void)hipEventDestroy(ev);
         if (c->copy) (void)hipStreamSynchronize(c->copy);
         for (DevBuf *b : bufs)
             if (b->p) (void)hipFree(b->p);

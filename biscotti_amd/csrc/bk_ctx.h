@@ -98,6 +98,18 @@ struct bk_ctx {
     // device copies of X and of the outputs
     DevBuf batch_ctr, batch_part, batch_diag, batch_scores, batch_rec;
     DevBuf batch_X, batch_sel, batch_hsc, batch_mean;
+    // bk_multikrum_ragged*: a call's descriptors and segment starts on the
+    // device, and the pinned ring they go up through -- a call fills the next
+    // slot and records the slot's event behind its copy, and the call that
+    // comes round to the slot again waits for that event before it writes, so
+    // calls queued back to back on the stream never share staging bytes
+    DevBuf batch_desc;
+    static constexpr int RAGGED_SLOTS = 4;
+    void *ragged_stage[RAGGED_SLOTS] = {};
+    size_t ragged_stage_bytes[RAGGED_SLOTS] = {};
+    hipEvent_t ev_ragged[RAGGED_SLOTS] = {};
+    bool ragged_used[RAGGED_SLOTS] = {};
+    int ragged_next = 0;
     // the records of the last batched call on the host (fetched by the first
     // reader once the stream is done) and the one bk_selection_margin* reports
     // (margin_host points at batch_pick while a batched call is the last finish)

@@ -1,5 +1,5 @@
 // bk_internal.h -- what the kernel files (bk_gram, bk_scores, bk_mean, bk_small,
-// bk_small_batch, bk_i8, bk_aggregate, bk_roni, bk_collect) and the planner
+// bk_small_batch, bk_small_ragged, bk_i8, bk_aggregate, bk_roni, bk_collect) and the planner
 // (bk_plan) offer the files that implement the C ABI: plans, layouts and
 // launchers (and the launchers' shared row-type dispatch).  The context those
 // files share among themselves is bk_ctx.h, which the kernels never see.  Not
@@ -354,6 +354,76 @@ hipError_t launch_small_batch(const void *X, int dtype, int64_t ld, int64_t stri
                               int64_t part_stride, double *scores, double *diag, int64_t *sel,
                               double *mean, double *margin, unsigned *lines, int num_cu,
                               hipStream_t st, uint64_t spin_max = SMALL_SPIN_MAX);
+// bk_small_ragged.hip, k_small_ragged / k_tiny_ragged: W problems in one launch,
+// each with its own n and f, all of one NB = ceil(n / 16) and one d (so one P,
+// one C, one partials' stride and the instantiation the single call picks: the
+// bitwise contract), packed in ONE row-major matrix X.  Problem p of the launch
+// is desc[p]: its rows from row `row` of X, its partials in slot `slot` of the
+// launch's (part + slot * part_stride), its scores and diag at scores / diag +
+// sc, its sel at sel + so, its mean (nullable) at mean + idx * d and its record
+// at margin + idx * MARGIN_WORDS -- the caller's positions, so the launches of
+// one call fill one set of arrays.  seg: the W + 2 segment starts of the queue
+// (ragged_batch_seg_build).  lines: as launch_small_batch's
+struct RaggedBatchDesc {
+    int32_t n, f, m, idx;  // rows, Byzantine bound, m = n - f; the problem's index in the caller's order
+    int64_t row, sc, so;   // offsets: the first row in X, scores / diag, sel
+    int32_t slot, pad;     // the problem's partials (and queue lines) in this launch
+};
+// The queue of k_small_ragged, k_small_batch's lag-one pipeline over W problems
+// of NGI G items, n[p] S items and C M items each:
+//   G_0 | G_1 S_0 M_0 | G_2 S_1 M_1 | ... | G_{W-1} S_{W-2} M_{W-2} | S_{W-1} M_{W-1}
+// segment 0 has NGI items, segment j (1 <= j < W) has NGI + n[j - 1] + C,
+// segment W has n[W - 1] + C; seg[0 .. W + 1] are the segments' starts and the
+// total.
+__host__ __device__ inline void ragged_batch_seg_build(const int32_t *n, int W, int NGI, int C,
+                                                       int32_t *seg) {
+    seg[0] = 0;
+    seg[1] = NGI;
+    for (int j = 1; j < W; ++j) seg[j + 1] = seg[j] + NGI + n[j - 1] + C;
+    seg[W + 1] = seg[W] + n[W - 1] + C;
+}
+// queue position item (0 <= item < seg[W + 1]) -> problem p and k_small's item
+// number it of that problem (it < NGI: G item it; it < NGI + n[p]: S item
+// it - NGI; else M item it - NGI - n[p]).  A binary search over the W + 1
+// segments: <= 11 steps at W = 1,024.  A segment's G items open it, and behind
+// them the S and M items of the problem before keep k_small's numbering, so no
+// n is needed here
+__host__ __device__ inline void ragged_batch_queue_decode(const int32_t *seg, int W, int NGI,
+                                                          int item, int &p, int &it) {
+    int lo = 0, hi = W + 1;  // seg[lo] <= item < seg[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (seg[mid] <= item)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const int q = item - seg[lo];
+    if (lo == W) {  // the last problem's S and M items
+        p = W - 1;
+        it = NGI + q;
+    } else if (lo == 0 || q < NGI) {  // a G item of the problem that opens the segment
+        p = lo;
+        it = q;
+    } else {  // an S or M item of the problem before
+        p = lo - 1;
+        it = q;
+    }
+}
+// (the descriptors are the caller's to validate: every n in 16 NB - 15 .. 16 NB,
+// 0 <= f < n, m = n - f, slot < W, the offsets inside the arrays; seg =
+// ragged_batch_seg_build of the n's with NGI = SMALL_SPLIT_ITEMS * p.P and C =
+// p.C (1 without a mean), total = seg[W + 1])
+hipError_t launch_small_ragged(const void *X, int dtype, int64_t ld, int W, int NB, int64_t d,
+                               const SmallPlan &p, const RaggedBatchDesc *desc, const int32_t *seg,
+                               int total, double *part, int64_t part_stride, double *scores,
+                               double *diag, int64_t *sel, double *mean, double *margin,
+                               unsigned *lines, int num_cu, hipStream_t st,
+                               uint64_t spin_max = SMALL_SPIN_MAX);
+// k_tiny_ragged: workgroup b is k_tiny on desc[b] (every n <= 16, d <= 128)
+hipError_t launch_tiny_ragged(const void *X, int dtype, int64_t ld, int W, int64_t d,
+                              const RaggedBatchDesc *desc, double *scores, double *diag,
+                              int64_t *sel, double *mean, double *margin, hipStream_t st);
 // bk_collect_batch.hip, k_collect_small_batch: W finishes of one shape (n, f)
 // over one collection in one launch (problem b's arrival slots at orders +
 // b * n).  Per problem: n scores, n diag, m = n - f sel, d mean (nullable),

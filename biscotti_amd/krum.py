@@ -505,6 +505,86 @@ class Engine:
                                               stride, f, _p(sel_ptr), _p(scores_ptr),
                                               _p(mean_ptr)))
 
+    # ---- ragged entries (bk_multikrum_ragged*): every problem its own n and f ----
+    def multikrum_ragged(self, problems, fs, want_scores=True, want_mean=True, pinned=False):
+        """problems: a sequence of 2-D arrays (n_b, d) that share d and dtype
+        (float64 / float32) -- B independent Multi-Krum problems; fs an int (the
+        same f for all) or a sequence of B of them.  Returns a list of (sel,
+        scores, mean) per problem (scores / mean None when not wanted); problem
+        b's are bitwise multikrum's on problems[b].  The problems go to the
+        library packed in one matrix: views of consecutive rows of one
+        C-contiguous array are passed as they lie (pinned: that array is in
+        pinned host memory, BK_HOST_PINNED), anything else is packed into a
+        pageable copy first."""
+        if isinstance(problems, np.ndarray) and problems.ndim < 3:
+            raise ValueError("problems must be a sequence of 2-D arrays, one per problem")
+        problems = [np.asarray(x) for x in problems]
+        if not problems:
+            raise ValueError("need at least one problem")
+        for b, x in enumerate(problems):
+            if x.ndim != 2:
+                raise ValueError("problems[%d] must be 2-D (n updates x d)" % b)
+        if any(x.dtype not in (np.float64, np.float32) for x in problems):
+            problems = [x.astype(np.float64) for x in problems]
+        dtype, d = problems[0].dtype, problems[0].shape[1]
+        for b, x in enumerate(problems):
+            if x.shape[1] != d:
+                raise ValueError("problems[%d] has d=%d, problems[0] has d=%d: the problems share d"
+                                 % (b, x.shape[1], d))
+            if x.dtype != dtype:
+                raise ValueError("problems[%d] is %s, problems[0] is %s: the problems share a dtype"
+                                 % (b, x.dtype, dtype))
+        B = len(problems)
+        if np.ndim(fs) == 0:
+            fs = [int(fs)] * B
+        fs = np.ascontiguousarray(fs, dtype=np.int64)
+        if fs.ndim != 1 or fs.shape[0] != B:
+            raise ValueError("fs must be an int or one f per problem (%d problems)" % B)
+        ns = np.array([x.shape[0] for x in problems], dtype=np.int64)
+        offsets = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(ns, out=offsets[1:])
+        it = dtype.itemsize
+        packed = all(x.flags.c_contiguous for x in problems) and all(
+            problems[b + 1].ctypes.data == problems[b].ctypes.data + int(ns[b]) * d * it
+            for b in range(B - 1))
+        if packed:
+            x_ptr = problems[0].ctypes.data
+        else:
+            X = np.concatenate(problems, axis=0) if offsets[B] else np.empty((0, d), dtype=dtype)
+            X = np.ascontiguousarray(X)
+            x_ptr, pinned = X.ctypes.data, False
+        # room for every problem even where a check below would refuse the call
+        ms = np.maximum(ns - fs, 0)
+        sel = np.empty(max(int(ms.sum()), 1), dtype=np.int64)
+        mo = np.zeros(B, dtype=np.int64)
+        sc = np.empty(max(int(offsets[B]), 1), dtype=np.float64) if want_scores else None
+        mean = np.empty((B, max(d, 1)), dtype=np.float64) if want_mean else None
+        dt = _lib.BK_F32 if dtype == np.float32 else _lib.BK_F64
+        check(lib().bk_multikrum_ragged(self._ctx, x_ptr,
+                                        _lib.BK_HOST_PINNED if pinned else _lib.BK_HOST, dt, B,
+                                        offsets.ctypes.data, fs.ctypes.data, d, d, sel.ctypes.data,
+                                        mo.ctypes.data,
+                                        sc.ctypes.data if sc is not None else None,
+                                        mean.ctypes.data if mean is not None else None))
+        assert np.array_equal(mo, ns - fs)
+        so = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(mo, out=so[1:])
+        return [(sel[so[b]:so[b + 1]].copy(),
+                 sc[offsets[b]:offsets[b + 1]].copy() if want_scores else None,
+                 mean[b].copy() if want_mean else None) for b in range(B)]
+
+    def multikrum_ragged_device_ptr(self, x_ptr, dtype, offsets, fs, d, ld, sel_ptr,
+                                    scores_ptr=None, mean_ptr=None):
+        """Raw device pointers; offsets (B + 1) and fs (B) are host integer
+        sequences, consumed before the call returns."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        fs = np.ascontiguousarray(fs, dtype=np.int64)
+        if offsets.ndim != 1 or fs.ndim != 1 or offsets.shape[0] != fs.shape[0] + 1:
+            raise ValueError("offsets must hold one entry more than fs (one f per problem)")
+        check(lib().bk_multikrum_ragged_device(self._ctx, _p(x_ptr), dtype, fs.shape[0],
+                                               offsets.ctypes.data, fs.ctypes.data, d, ld,
+                                               _p(sel_ptr), _p(scores_ptr), _p(mean_ptr)))
+
     def selection_margin_batch(self, batch):
         """The records of the last batched call, one dict per problem (the keys
         of selection_margin); batch: that call's problem count."""
@@ -729,6 +809,30 @@ def krum_batch(deltas, clip, engine: Optional[Engine] = None):
     sel, _, _ = (engine or default_engine()).multikrum_batch(X, clip, want_scores=False,
                                                              want_mean=False)
     return sel
+
+
+def krum_ragged(list_of_deltas, clips, engine: Optional[Engine] = None):
+    """[krum(deltas, clip) for deltas, clip in zip(list_of_deltas, clips)] in
+    one call: the batches may differ in their number of updates (they share d);
+    clips an int or one clip per batch.  A list of ascending index arrays.
+    Raises krum's ValueError for a clip outside [1, n) of its batch."""
+    Xs = [_as_matrix(deltas) for deltas in list_of_deltas]
+    if not Xs:
+        raise ValueError("need at least one batch of updates")
+    if np.ndim(clips) == 0:
+        clips = [clips] * len(Xs)
+    if len(clips) != len(Xs):
+        raise ValueError("clips must be an int or one clip per batch (%d batches)" % len(Xs))
+    for X, clip in zip(Xs, clips):
+        if X.ndim != 2:
+            raise ValueError("every batch must be n updates of d values")
+        if clip < 1 or clip >= len(X):
+            raise ValueError("kth(=%d) out of bounds (%d)" % (len(X) - clip, len(X)))
+    if len({X.dtype for X in Xs}) > 1:
+        Xs = [X.astype(np.float64) for X in Xs]
+    out = (engine or default_engine()).multikrum_ragged(Xs, [int(c) for c in clips],
+                                                        want_scores=False, want_mean=False)
+    return [sel for sel, _, _ in out]
 
 
 def krum_mean(deltas, clip, engine: Optional[Engine] = None):

@@ -279,6 +279,82 @@ int bk_multikrum_batch(bk_ctx *ctx, const void *X, int where, int dtype, int64_t
  * bk_selection_margin_record, one per problem); batch must be that call's */
 int bk_selection_margin_batch(bk_ctx *ctx, double *records, int64_t batch);
 
+/* ---- many small problems, each with its own n and f, in one call -------------
+ * bk_multikrum_batch with a row count n_b and an f_b PER PROBLEM: attack, f or
+ * seed sweeps whose batches differ in size (the reference fixes f = int(0.5 n),
+ * and n is what KRUM_UPDATETHRESH, the deadline or sampleUpdates left), the
+ * verdict stages at n = 28, 42, 56 and 70 side by side, several validators in
+ * one process -- one call, not one per distinct (n, f).  (Problems that share
+ * rows belong to bk_collect_finish_ragged, which computes their Gram once.)
+ * All problems share d, dtype and ld and lie packed in ONE row-major matrix of
+ * offsets[batch] rows: problem b is rows offsets[b] .. offsets[b+1]-1 (n_b =
+ * the difference, offsets[0] = 0) with f = fs[b].  The outputs are packed as
+ * bk_collect_finish_ragged packs them: problem b's m_b = n_b - f_b selected
+ * indices (its own rows 0..n_b-1, ascending) at d_sel_idx + sum_{c<b} m_c, its
+ * n_b scores at d_scores + offsets[b] (nullable), its mean at d_mean + b*d
+ * (nullable, batch x d).
+ * dX and the outputs are device pointers and the call is asynchronous on the
+ * context stream; offsets and fs are HOST arrays, consumed before the call
+ * returns (the descriptors built from them go up through a pinned ring of the
+ * context's, each slot guarded by an event, so calls queued back to back on the
+ * stream never share staging).
+ * Every output of problem b -- sel, scores, mean and all eight margin fields --
+ * is BITWISE what bk_multikrum_device gives on that problem alone under the
+ * same context settings.  Problems within the one-launch range (n_b <= 128, d
+ * <= 32,768, the small path on) are grouped by ceil(n_b / 16): the single call
+ * picks its kernel instantiation, its partial layout and its item counts by
+ * that number and by d, so only problems that agree in it share launches.  Each
+ * group of two or more runs as k_small_ragged launches of W problems -- k_small's
+ * work items behind a per-problem descriptor, every output written at the
+ * caller's position -- W bounded by 1,024 and by the launch's partial workspace
+ * (BK_BATCH_WS_BYTES, as bk_multikrum_batch); with d <= 128 the n_b <= 16 group
+ * runs as one k_tiny_ragged launch, one workgroup per problem.  A group's only
+ * problem, every problem outside the range, bk_set_small_path(ctx, 0) and
+ * batch = 1 run the single-problem device path in the same call (the f32 / f64
+ * modes and certification apply per problem there); a call may mix all three.
+ * The buffers are bk_multikrum_batch's, with their life-cycle: a single call, a
+ * batched call or a collection finish between two ragged calls is unaffected
+ * and affects nothing.  hipGraph replay does not apply.
+ * Measured (tools/batch_ragged_bench.py): ahead of a loop of single
+ * calls and of one bk_multikrum_batch_device per distinct (n, f) at every batch
+ * size tried, 2 included; where all problems share one (n, f),
+ * bk_multikrum_batch_device stays the faster call (the ragged one takes 1.08-
+ * 1.10 x its time at 100 x 7,850 from a batch of 16, 1.27 x at a batch of 2,
+ * and 1.2-2.0 x at 10 x 25: one descriptor copy per call, and a descriptor
+ * read and a segment search per item).
+ * A hand-off give-up in a launch invalidates the launch: every d_sel_idx entry
+ * of its problems is -1, their records carry the time-out code, and
+ * bk_synchronize (and the host entry) return BK_EHIP.
+ * Afterwards bk_selection_margin / _record follow bk_multikrum_batch's rule,
+ * and bk_selection_margin_batch(ctx, records, batch) gives the batch records in
+ * the caller's problem order.  Timed under BK_K_SMALL, BK_K_H2D and BK_K_D2H.
+ * The checks, in this order, all before any copy, launch or state change: a
+ * bad dtype; batch < 1 (BK_EINVAL), batch > BK_MAX_BATCH (BK_ENOTSUP), d < 1,
+ * ld < d (no GPU or context needed); then BK_EINVAL for a null ctx, X, offsets,
+ * fs or sel (each named); offsets[0] != 0 or an n_b < 1 (the problem named);
+ * then bk_check_args(n_b, d, f_b)'s status, its message behind "problem b: ";
+ * then, for the host entry, a bad `where`. */
+int bk_multikrum_ragged_device(bk_ctx *ctx, const void *dX, int dtype, int64_t batch,
+                               const int64_t *offsets /* HOST, batch + 1 */,
+                               const int64_t *fs /* HOST, batch */, int64_t d, int64_t ld,
+                               int64_t *d_sel_idx, double *d_scores, double *d_mean);
+/* X on the host (BK_HOST / BK_HOST_PINNED), host outputs (m_out nullable, batch
+ * entries: m_out[b] = m_b; scores and mean_out nullable), synchronous: one H2D
+ * copy of the (offsets[batch]-1)*ld + d elements, the device entry, the copies
+ * back, then the records' error codes, as bk_multikrum_batch. */
+int bk_multikrum_ragged(bk_ctx *ctx, const void *X, int where, int dtype, int64_t batch,
+                        const int64_t *offsets, const int64_t *fs, int64_t d, int64_t ld,
+                        int64_t *sel_idx, int64_t *m_out /* batch, nullable */, double *scores,
+                        double *mean_out);
+/* Host-side only; no context.  For W problems with n[] rows (1..128), NGI Gram
+ * items (4 per 128 columns: 4 * ceil(d / 128)) and C mean items (ceil(d / 64);
+ * 1 without a mean) each: the queue position `item` of k_small_ragged ->
+ * problem *p and k_small's item number *it of that problem (it < NGI: G item;
+ * it < NGI + n[p]: S item it - NGI; else M item it - NGI - n[p]).  The kernel
+ * decodes with the same function.  BK_EINVAL outside the queue. */
+int bk_ragged_batch_queue_item(const int32_t *n, int W, int NGI, int C, int64_t item, int *p,
+                               int *it);
+
 /* ---- many finishes over one collection in one call --------------------------
  * `batch` finishes over ONE collection in one call: problem b is Multi-Krum
  * over the n collected rows orders[b*n .. b*n+n) (arrival slots; a subset and
