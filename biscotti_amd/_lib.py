@@ -25,7 +25,11 @@ BK_F64_EXACT, BK_F64_I8, BK_F64_I8_CERTIFIED, BK_F64_I8X2, BK_F64_I8X2_CERTIFIED
 KERNELS = ["k_gram", "k_reduce", "k_transpose", "k_scores", "k_rank", "k_compact", "k_mean",
            "allreduce", "k_synth", "h2d", "d2h", "k_aggregate", "k_qsum", "k_noise", "k_roni",
            "k_small", "k_slice", "score_gather", "exchange_exposed"]
-K = {name: i for i, name in enumerate(KERNELS)}
+# the ids past the first 19: a RONI round's score launches (bk.h BK_K_RONI_ROUND*)
+ROUND_KERNELS = ["k_roni_round", "k_roni_round_sm"]
+ALL_KERNELS = KERNELS + ROUND_KERNELS
+K = {name: i for i, name in enumerate(ALL_KERNELS)}
+BK_RONI_ROUND_G = 8
 
 # every symbol include/bk.h declares: name -> (restype, argtypes)
 _i = ctypes.c_int
@@ -85,6 +89,10 @@ SIGNATURES = {
     "bk_roni_softmax_set_validation": (_i, [_p, _p, _i64, _i64, _i64, _p, _i64]),
     "bk_roni_softmax": (_i, [_p, _p, _p, _i64, _i64, _p, _p]),
     "bk_roni_softmax_batches": (_i, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _p]),
+    "bk_roni_round_begin": (_i, [_p, _p, _i64, _i]),
+    "bk_roni_round_score": (_i, [_p, _p, _i64, _i, _p]),
+    "bk_roni_softmax_round_begin": (_i, [_p, _p, _i]),
+    "bk_roni_softmax_round_score": (_i, [_p, _p, _i64, _i, _p, _p]),
     "bk_group_create": (_i, [ctypes.POINTER(_p), _i, _p, _i]),
     "bk_group_destroy": (None, [_p]),
     "bk_group_size": (_i, [_p]),

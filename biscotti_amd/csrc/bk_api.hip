@@ -40,7 +40,7 @@ const char *kKernelNames[BK_NUM_KERNELS] = {"k_gram",    "k_reduce",  "k_transpo
                                             "k_synth",   "h2d",       "d2h",
                                             "k_aggregate", "k_qsum",  "k_noise",
                                             "k_roni", "k_small", "k_slice", "score_gather",
-                                            "exchange_exposed"};
+                                            "exchange_exposed", "k_roni_round", "k_roni_round_sm"};
 
 int ensure(DevBuf &b, size_t bytes) {
     if (bytes <= b.bytes) return BK_OK;
@@ -217,11 +217,15 @@ void bk_destroy(bk_ctx *c) {
                           &c->noise, &c->diag, &c->bnd, &c->Ut, &c->small_ctr, &c->small_part,
                           &c->mean_part, &c->status, &c->rmc_X, &c->rmc_y, &c->rmc_ws,
                       &c->rmc_xn, &c->rmc_idx, &c->rmc_nt, &c->i8ws, &c->sgather, &c->pcnt,
+                          &c->rr_w, &c->rr_base, &c->rr_ws, &c->rs_w, &c->rs_base, &c->rs_ws,
+                          &c->round_rows, &c->round_cnt,
                           &c->batch_ctr, &c->batch_part, &c->batch_diag, &c->batch_scores,
                           &c->batch_rec, &c->batch_X, &c->batch_sel, &c->batch_hsc, &c->batch_mean,
                           &c->batch_desc};
         if (c->hmargin) (void)hipHostFree(c->hmargin);
         if (c->hout) (void)hipHostFree(c->hout);
+        if (c->round_out) (void)hipHostFree(c->round_out);
+        if (c->ev_round) (void)hipEventDestroy(c->ev_round);
         for (void *p : c->ragged_stage)
             if (p) (void)hipHostFree(p);
         for (hipEvent_t ev : c->ev_ragged)

@@ -152,6 +152,21 @@ struct bk_ctx {
     // labels; bk_roni_softmax_set_validation) and the prepared models
     DevBuf rmc_X, rmc_y, rmc_ws, rmc_xn, rmc_idx, rmc_nt;
     int64_t rmc_nv = 0, rmc_din = 0, rmc_C = 0;
+    // RONI rounds (bk_roni*_round_*): the iteration's model, its evaluation's
+    // counts (logistic: mismatches; softmax: correct, near ties) and the begin's
+    // prepared columns (softmax: the widened fp32 weights and their norms), kept
+    // until the next begin or set_validation; buffers of their own, so batched
+    // calls in between leave a round intact
+    DevBuf rr_w, rr_base, rr_ws, rs_w, rs_base, rs_ws;
+    int rr_live = 0, rs_live = 0;
+    // a score call's scratch: host rows staged on the device, the groups'
+    // counters, and the mapped pinned block the kernel writes the scores (and
+    // near-tie counts) into: no device-to-host copy
+    DevBuf round_rows, round_cnt;
+    void *round_out = nullptr;
+    void *round_out_dev = nullptr;
+    size_t round_out_bytes = 0;
+    hipEvent_t ev_round = nullptr;  // begin: ww has been consumed
     // bk_multikrum_noised: a 2-slot ring of noise chunks, filled on a copy
     // stream while K6 consumes the previous chunk on `stream` (created lazily)
     DevBuf noise;

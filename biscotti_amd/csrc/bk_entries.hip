@@ -2,6 +2,7 @@
 // quantised sum, the noise application and both RONI variants (the kernels:
 // bk_aggregate.hip, bk_roni.hip).
 #include <hip/hip_runtime.h>
+#include <string.h>
 
 #include <mutex>
 #include <vector>
@@ -155,6 +156,7 @@ int bk_roni_set_validation(bk_ctx *c, const double *Xv, int64_t nv, int64_t d, i
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard dg(c->device);
     c->roni_nv = 0;  // invalid until the new set has landed
+    c->rr_live = 0;  // a round was evaluated on the old set
     HostDrain drain{c};
     CHK(ensure(c->roni_X, (size_t)nv * d * sizeof(double)));
     CHK(ensure(c->roni_y, (size_t)nv * sizeof(double)));
@@ -275,6 +277,7 @@ int bk_roni_softmax_set_validation(bk_ctx *c, const float *Xv, int64_t nv, int64
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard dg(c->device);
     c->rmc_nv = 0;  // invalid until the new set has landed
+    c->rs_live = 0;  // a round was evaluated on the old set
     HostDrain drain{c};
     CHK(ensure(c->rmc_X, (size_t)nv * d_in * sizeof(float)));
     CHK(ensure(c->rmc_y, (size_t)nv * sizeof(int32_t)));
@@ -362,6 +365,196 @@ static int roni_softmax_host(bk_ctx *c, const double *ww, const double *deltas, 
     HIPCHK(hipStreamSynchronize(c->stream));
     drain.armed = false;
     return BK_OK;
+}
+
+// ---- RONI rounds: the model of one iteration held with its evaluation done --
+static int check_where(int where) {
+    if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
+        return fail(BK_EINVAL, "bad where=%d", where);
+    return BK_OK;
+}
+
+// a begin's upload: ww is consumed on return, the evaluation behind it runs on
+static int round_upload_ww(bk_ctx *c, DevBuf &w, const double *ww, int64_t d, int where) {
+    CHK(ensure(w, (size_t)d * sizeof(double)));
+    if (!c->ev_round) HIPCHK(hipEventCreateWithFlags(&c->ev_round, hipEventDisableTiming));
+    CHK(timed(c, BK_K_H2D, [&] {
+        return hipMemcpyAsync(w.p, ww, (size_t)d * sizeof(double),
+                              where == BK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                              c->stream);
+    }));
+    HIPCHK(hipEventRecord(c->ev_round, c->stream));
+    HIPCHK(hipEventSynchronize(c->ev_round));
+    return BK_OK;
+}
+
+// the mapped pinned block a score call's kernels write: count scores, then
+// 1 + count near-tie counts
+static int ensure_round_out(bk_ctx *c, int64_t count) {
+    const size_t bytes = (size_t)count * sizeof(double) + (size_t)(count + 1) * sizeof(int32_t);
+    if (bytes <= c->round_out_bytes) return BK_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->round_out) (void)hipHostFree(c->round_out);
+    c->round_out = c->round_out_dev = nullptr;
+    c->round_out_bytes = 0;
+    const size_t want = bytes < 4096 ? 4096 : bytes;
+    HIPCHK(hipHostMalloc(&c->round_out, want,
+                         hipHostMallocPortable | hipHostMallocMapped | hipHostMallocNonCoherent));
+    HIPCHK(hipHostGetDevicePointer(&c->round_out_dev, c->round_out, 0));
+    c->round_out_bytes = want;
+    return BK_OK;
+}
+
+// A score call past its checks (the context mutex held): host rows staged on
+// the device (device rows are read where they are), the groups' counters
+// zeroed, one launch per group of up to RONI_ROUND_G rows, one wait, then host
+// memcpys out of the mapped block.  launch(rows, g, cnt, scores, near, first)
+template <typename F>
+static int round_score(bk_ctx *c, int kid, const double *const *deltas, int64_t count, int where,
+                       int64_t d, double *scores, int32_t *near_ties, F &&launch) {
+    DeviceGuard dg(c->device);
+    HostDrain drain{c};  // error returns: queued copies and launches may still read the rows
+    const int64_t groups = (count + RONI_ROUND_G - 1) / RONI_ROUND_G;
+    const size_t cbytes = (size_t)groups * ROUND_CNT_WORDS * sizeof(unsigned int);
+    CHK(ensure(c->round_cnt, cbytes));
+    CHK(ensure_round_out(c, count));
+    const double *staged = nullptr;
+    if (where != BK_DEVICE) {
+        CHK(ensure(c->round_rows, (size_t)count * d * sizeof(double)));
+        double *dst = (double *)c->round_rows.p;
+        CHK(timed(c, BK_K_H2D, [&] {
+            hipError_t e = hipSuccess;
+            for (int64_t i = 0; i < count && e == hipSuccess; ++i)
+                e = hipMemcpyAsync(dst + i * d, deltas[i], (size_t)d * sizeof(double),
+                                   hipMemcpyHostToDevice, c->stream);
+            return e;
+        }));
+        staged = dst;
+    }
+    HIPCHK(hipMemsetAsync(c->round_cnt.p, 0, cbytes, c->stream));
+    double *dsc = (double *)c->round_out_dev;
+    int32_t *dnt = near_ties ? (int32_t *)(dsc + count) : nullptr;
+    for (int64_t q0 = 0; q0 < count; q0 += RONI_ROUND_G) {
+        const int g = (int)(count - q0 < RONI_ROUND_G ? count - q0 : RONI_ROUND_G);
+        RoundRows rows = {};
+        for (int q = 0; q < g; ++q) rows.p[q] = staged ? staged + (q0 + q) * d : deltas[q0 + q];
+        unsigned int *cnt = (unsigned int *)c->round_cnt.p + q0 / RONI_ROUND_G * ROUND_CNT_WORDS;
+        CHK(timed(c, kid, [&] {
+            return launch(rows, g, cnt, dsc + q0, dnt ? dnt + q0 : nullptr, q0 == 0 ? 1 : 0);
+        }));
+    }
+    HIPCHK(wait_stream(c));
+    drain.armed = false;
+    const char *h = (const char *)c->round_out;
+    memcpy(scores, h, (size_t)count * sizeof(double));
+    if (near_ties) memcpy(near_ties, h + (size_t)count * sizeof(double), (size_t)(count + 1) * sizeof(int32_t));
+    return BK_OK;
+}
+
+static int check_round_rows(const double *const *deltas, int64_t count, const double *scores) {
+    if (!deltas || !scores) return fail(BK_EINVAL, "null pointer argument");
+    for (int64_t i = 0; i < count; ++i)
+        if (!deltas[i]) return fail(BK_EINVAL, "null row deltas[%lld]", (long long)i);
+    return BK_OK;
+}
+
+int bk_roni_round_begin(bk_ctx *c, const double *ww, int64_t d, int where) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->roni_nv < 1) return fail(BK_EINVAL, "no validation set: call bk_roni_set_validation");
+    if (d != c->roni_dim)
+        return fail(BK_EINVAL, "d=%lld != validation set's %lld", (long long)d, (long long)c->roni_dim);
+    CHK(check_roni(c->roni_nv, d, d, 0, d));
+    if (!ww) return fail(BK_EINVAL, "null pointer argument");
+    CHK(check_where(where));
+    DeviceGuard dg(c->device);
+    HostDrain drain{c};
+    c->rr_live = 0;  // no round until the new one's evaluation is queued
+    CHK(ensure(c->rr_base, sizeof(unsigned int)));
+    CHK(ensure(c->rr_ws, roni_ws(0, d)));
+    CHK(round_upload_ww(c, c->rr_w, ww, d, where));
+    // K7 with no new model: model 0's count, bitwise the batched call's
+    const double *dw = (const double *)c->rr_w.p;
+    CHK(timed(c, BK_K_RONI, [&] {
+        return launch_roni((const double *)c->roni_X.p, c->roni_nv, d, d, (const double *)c->roni_y.p,
+                           dw, dw, 0, d, (double *)c->rr_ws.p, (unsigned int *)c->rr_base.p, nullptr,
+                           c->stream);
+    }));
+    drain.armed = false;
+    c->rr_live = 1;
+    return BK_OK;
+}
+
+int bk_roni_round_score(bk_ctx *c, const double *const *deltas, int64_t count, int where,
+                        double *scores) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->roni_nv < 1) return fail(BK_EINVAL, "no validation set: call bk_roni_set_validation");
+    if (!c->rr_live) return fail(BK_EINVAL, "no round: call bk_roni_round_begin");
+    if (count < 1) return fail(BK_EINVAL, "count=%lld < 1", (long long)count);
+    const int64_t nv = c->roni_nv, d = c->roni_dim;
+    CHK(check_roni(nv, d, d, count, d));
+    CHK(check_round_rows(deltas, count, scores));
+    CHK(check_where(where));
+    return round_score(c, BK_K_RONI_ROUND, deltas, count, where, d, scores, nullptr,
+                       [&](const RoundRows &rows, int g, unsigned int *cnt, double *sc, int32_t *,
+                           int) {
+                           return launch_roni_round((const double *)c->roni_X.p, nv, d, d,
+                                                    (const double *)c->roni_y.p,
+                                                    (const double *)c->rr_w.p, rows, g, cnt,
+                                                    (const unsigned int *)c->rr_base.p, sc,
+                                                    c->stream);
+                       });
+}
+
+int bk_roni_softmax_round_begin(bk_ctx *c, const double *ww, int where) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->rmc_nv < 1) return fail(BK_EINVAL, "no validation set: call bk_roni_softmax_set_validation");
+    const int64_t nv = c->rmc_nv, din = c->rmc_din, C = c->rmc_C, d = C * (din + 1);
+    CHK(check_roni_softmax(nv, din, din, C, 0, 0));
+    if (!ww) return fail(BK_EINVAL, "null pointer argument");
+    CHK(check_where(where));
+    DeviceGuard dg(c->device);
+    HostDrain drain{c};
+    c->rs_live = 0;
+    CHK(ensure(c->rs_base, 2 * sizeof(unsigned int)));
+    CHK(ensure(c->rs_ws, roni_softmax_ws(0, din, nv, (int)C)));
+    CHK(round_upload_ww(c, c->rs_w, ww, d, where));
+    // K8 with no new model: model 0's correct and near-tie counts, bitwise the
+    // batched call's; its widened columns and their norms stay in rs_ws
+    const double *dw = (const double *)c->rs_w.p;
+    CHK(timed(c, BK_K_RONI, [&] {
+        return launch_roni_softmax((const float *)c->rmc_X.p, nv, din, din, (const int32_t *)c->rmc_y.p,
+                                   (int)C, dw, dw, 0, d, (double *)c->rs_ws.p,
+                                   (const double *)c->rmc_xn.p, (unsigned int *)c->rs_base.p, nullptr,
+                                   nullptr, c->stream);
+    }));
+    drain.armed = false;
+    c->rs_live = 1;
+    return BK_OK;
+}
+
+int bk_roni_softmax_round_score(bk_ctx *c, const double *const *deltas, int64_t count, int where,
+                                double *scores, int32_t *near_ties) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->rmc_nv < 1) return fail(BK_EINVAL, "no validation set: call bk_roni_softmax_set_validation");
+    if (!c->rs_live) return fail(BK_EINVAL, "no round: call bk_roni_softmax_round_begin");
+    if (count < 1) return fail(BK_EINVAL, "count=%lld < 1", (long long)count);
+    const int64_t nv = c->rmc_nv, din = c->rmc_din, C = c->rmc_C, d = C * (din + 1);
+    CHK(check_roni_softmax(nv, din, din, C, count, d));
+    CHK(check_round_rows(deltas, count, scores));
+    CHK(check_where(where));
+    return round_score(c, BK_K_RONI_ROUND_SM, deltas, count, where, d, scores, near_ties,
+                       [&](const RoundRows &rows, int g, unsigned int *cnt, double *sc, int32_t *nt,
+                           int first) {
+                           return launch_roni_softmax_round(
+                               (const float *)c->rmc_X.p, nv, din, din, (const int32_t *)c->rmc_y.p,
+                               (int)C, (const double *)c->rs_w.p, rows, g,
+                               (const double *)c->rmc_xn.p, cnt, (const unsigned int *)c->rs_base.p,
+                               sc, nt, first, c->stream);
+                       });
 }
 
 int bk_roni_softmax(bk_ctx *c, const double *ww, const double *deltas, int64_t n, int64_t ld,

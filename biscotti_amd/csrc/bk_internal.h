@@ -282,6 +282,25 @@ hipError_t launch_roni_softmax_batches(const float *Xv, int64_t nv, int64_t din,
                                        const double *deltas, int64_t n, int64_t ld,
                                        const int64_t *idx, int64_t nb, double *scores,
                                        int32_t *near_out, hipStream_t st);
+// RONI rounds: with n = 0 launch_roni / launch_roni_softmax evaluate ww alone
+// (cnt[0]; good[0] and good[1], its near ties) and write no score.  A score
+// launch takes up to RONI_ROUND_G new models (rows.p[0..g), d doubles each)
+// through one pass over the validation set; cnt: ROUND_CNT_WORDS zeroed words
+// of its own; base: the begin's counts; scores (g) and near (softmax, nullable:
+// near[0] the base when `first`, near[1 + i] model i) are written by the last
+// workgroup out
+constexpr int RONI_ROUND_G = 8, ROUND_CNT_WORDS = 32;
+struct RoundRows {
+    const double *p[RONI_ROUND_G];
+};
+hipError_t launch_roni_round(const double *Xv, int64_t nv, int64_t d, int64_t ldv, const double *yv,
+                             const double *ww, const RoundRows &rows, int g, unsigned int *cnt,
+                             const unsigned int *base, double *scores, hipStream_t st);
+hipError_t launch_roni_softmax_round(const float *Xv, int64_t nv, int64_t din, int64_t ldv,
+                                     const int32_t *yv, int C, const double *ww,
+                                     const RoundRows &rows, int g, const double *xn,
+                                     unsigned int *cnt, const unsigned int *base, double *scores,
+                                     int32_t *near, int first, hipStream_t st);
 // bk_i8.hip: K1i8, the Gram of fp32 rows from exact int8 digit slices
 // (BK_F32_I8): column ranges (one per XCD), digit planes [3][npad][dp] int8
 struct I8Layout {

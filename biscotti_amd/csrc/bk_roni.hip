@@ -16,6 +16,9 @@
 //   K8  the torch-path (softmax) verifier: k_roni_mm_prep<true> +
 //       k_roni_logits over a whole sample set, or k_roni_batch over the last
 //       mini-batches the reference actually scores (below)
+//   K7r / K8r k_roni_round_sign, k_roni_round_logits: a round's score launches
+//       (r15): up to 8 new models against a model evaluated once per iteration,
+//       on per-lane FMA chains, the score in the launch's tail (at the end)
 //
 // Built with -ffp-contract=off: ww + delta rounds exactly like numpy; every dot
 // is a plain fp64 FMA chain over k ascending (the MFMA chains round alike,
@@ -698,9 +701,11 @@ hipError_t launch_roni_softmax(const float *Xv, int64_t nv, int64_t din, int64_t
                        yv, C, Wt, bt, ldl, nmod, nx, ny % 8 == 0 ? 1 : 0, good, xn, wn,
                        roni_softmax_g(din), near);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_roni_mc_score, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, good,
-                       n, nv, scores);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (n > 0) {  // (n = 0: a round's begin wants ww's counts only)
+        hipLaunchKernelGGL(k_roni_mc_score, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, good,
+                           n, nv, scores);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     if (near_out)
         e = hipMemcpyAsync(near_out, near, (size_t)nmod * sizeof(int32_t), hipMemcpyDeviceToDevice,
                            st);
@@ -971,8 +976,343 @@ hipError_t launch_roni(const double *Xv, int64_t nv, int64_t d, int64_t ldv, con
                        ws, ldl, nmod, nx, (int)per, cnt);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (n == 0) return hipSuccess;  // a round's begin wants ww's count only
     hipLaunchKernelGGL(k_roni_score, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cnt, n,
                        nv, scores);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// RONI rounds (r15).  The verifier scores ONE update per RPC against the
+// iteration's model (Peer.VerifyUpdateRONI, main.go:191-233): the round's begin
+// has evaluated ww (the batched kernels above with no new model), a score call
+// brings g <= G new models ww + delta_q.  On K7 / K8 one model fills 2 (20) of a
+// tile's 128 columns between a prep, a reset and a score launch; here a launch
+// is one pass over the validation set on per-lane fp64 FMA chains over k
+// ascending from +0.0 -- the chain the MFMA kernels round like, so
+// the counts are theirs bit for bit -- with the score in its tail.
+//
+// The tail, both kernels: the workgroup's counts are summed in LDS; thread 0
+// adds them to the launch's counters (agent-scope atomics), drains them
+// (vmcnt 0) and adds 1 to the exit counter; the workgroup whose add returns
+// gridDim.x - 1 reads the totals (atomic loads) and writes the scores.  Nobody
+// waits for anybody.  cnt: [0, G) the models' counts, [G, 2 G) the softmax near
+// ties, [2 G] the exit counter; zeroed by the host before every launch.
+constexpr int ROUND_EXIT = 2 * RONI_ROUND_G;
+static_assert(ROUND_EXIT < ROUND_CNT_WORDS, "the exit counter lies in the block");
+
+__device__ inline unsigned int round_load(const unsigned int *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// thread 0 of every workgroup, after the barrier behind the LDS counts: true
+// for the last workgroup out, which may then read every workgroup's adds
+template <int NC>
+__device__ inline bool round_exit(const unsigned int (&s_cnt)[NC], const int (&slot)[NC],
+                                  unsigned int *cnt) {
+#pragma unroll
+    for (int q = 0; q < NC; ++q)
+        if (s_cnt[q])
+            __hip_atomic_fetch_add(cnt + slot[q], s_cnt[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    return __hip_atomic_fetch_add(cnt + ROUND_EXIT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
+           gridDim.x - 1u;
+}
+
+// k_roni_round_sign: a workgroup takes 256 samples, thread t sample t.  The
+// samples go through LDS in chunks of 32 features (the global loads run along
+// k, 256 B per row and chunk; [sample][k] row stride 33 doubles: a lane's row
+// reads and the staging writes are conflict-free), the next chunk's loads in
+// flight under this chunk's chains; d <= 32 (creditcard: 25) is one chunk.  The
+// G models' weights ww + delta_q (numpy's fp64 add) are formed once per
+// workgroup and chunk in LDS and read as broadcasts: they are wave-uniform, and
+// 8 models x 32 features would be 512 registers per lane.
+// Bound: HBM / L2 -- Xv is read once per launch.
+constexpr int RR_TS = 256, RR_KC = 32;
+
+template <int G>
+__global__ __launch_bounds__(256) void k_roni_round_sign(const double *__restrict__ Xv, int64_t nv,
+                                                         int64_t din, int64_t ldv,
+                                                         const double *__restrict__ yv,
+                                                         const double *__restrict__ ww,
+                                                         const RoundRows rows, int g,
+                                                         unsigned int *__restrict__ cnt,
+                                                         const unsigned int *__restrict__ base,
+                                                         double *__restrict__ scores) {
+    static_assert(G * RR_KC <= 256 && G <= RONI_ROUND_G, "one weight per thread and chunk");
+    __shared__ double xs[RR_TS][RR_KC + 1];
+    __shared__ double wsm[G][RR_KC];
+    __shared__ unsigned int s_cnt[G];
+    const int tid = threadIdx.x, l = tid & 63;
+    const int64_t s0 = (int64_t)blockIdx.x * RR_TS;
+    if (tid < G) s_cnt[tid] = 0;
+    // staging: thread t moves feature t & 31 of samples (t >> 5) + 8 u, and the
+    // weight of model t >> 5, feature t & 31
+    const int xk = tid & 31, xr = tid >> 5;
+    const double *dq = nullptr;
+#pragma unroll
+    for (int q = 0; q < G; ++q)
+        if (xr == q && q < g) dq = rows.p[q];
+    double xv[RR_KC], wv = 0.0;
+    auto load = [&](int64_t k0) {  // clamped addresses, every load in flight
+        int64_t k = k0 + xk;
+        k = k < din ? k : din - 1;
+#pragma unroll
+        for (int u = 0; u < RR_KC; ++u) {
+            int64_t s = s0 + xr + 8 * u;
+            s = s < nv ? s : nv - 1;
+            xv[u] = Xv[s * ldv + k];
+        }
+        if (dq) wv = ww[k] + dq[k];
+    };
+    double acc[G];
+#pragma unroll
+    for (int q = 0; q < G; ++q) acc[q] = 0.0;
+    load(0);
+    for (int64_t k0 = 0; k0 < din; k0 += RR_KC) {
+        __syncthreads();  // the previous chunk has been consumed
+#pragma unroll
+        for (int u = 0; u < RR_KC; ++u) xs[xr + 8 * u][xk] = xv[u];
+        if (xr < G) wsm[xr][xk] = dq ? wv : 0.0;
+        __syncthreads();
+        if (k0 + RR_KC < din) load(k0 + RR_KC);
+        const int kn = (int)(din - k0 < RR_KC ? din - k0 : RR_KC);
+        for (int kk = 0; kk < kn; ++kk) {
+            const double x = xs[tid][kk];
+#pragma unroll
+            for (int q = 0; q < G; ++q) acc[q] = __builtin_fma(x, wsm[q][kk], acc[q]);
+        }
+    }
+    const int64_t s = s0 + tid;
+    const double y = yv[s < nv ? s : nv - 1];
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+        const double v = acc[q];  // np.sign: 0 -> 0, NaN -> NaN
+        const double yh = v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : (v == 0.0 ? 0.0 : v));
+        const unsigned int mis = (unsigned int)__popcll(__ballot(s < nv && !(yh == y)));
+        if (l == 0 && mis && q < g) atomicAdd(&s_cnt[q], mis);
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    unsigned int mine[G];
+    int slot[G];
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+        mine[q] = s_cnt[q];
+        slot[q] = q;
+    }
+    if (!round_exit(mine, slot, cnt)) return;
+    const double dn = (double)nv;
+    const double g_err = (double)base[0] / dn;
+    for (int q = 0; q < g; ++q) {  // k_roni_score's expression
+        const double new_err = (double)round_load(cnt + q) / dn;
+        scores[q] = new_err - g_err;
+    }
+}
+
+// k_roni_round_logits: a workgroup takes 16 samples, thread (s, c) = (t >> 4,
+// t & 15) the logit of class c of sample s for each of the G models, as
+// k_roni_batch's threads do: the samples and the models' fp32 weights (ww +
+// delta_q rounded after the fp64 add, as k_roni_mm_prep<true> rounds them) go
+// through LDS in chunks of 64 features (row stride 68 floats: the 16-B reads of
+// 16 class rows cover all 64 banks), the next chunk's loads in flight under
+// this chunk's chains; 16 features at a time are read as float4s, then their 16
+// FMAs per model run in k order.  Threads (0, c) add |w_c|^2 of every model in
+// the same order (k_roni_wnorm's sequential sum: each square is exact).  Then
+// logit = fp32(acc + b), and thread (q, s) takes np.argmax, the label compare
+// and softmax_near_tie -- K8's epilogue -- for model q and sample s.
+// Bound: L2 -- every workgroup reads the g deltas; Xv is read once.
+constexpr int RQ_ST = 16, RQ_KC = 64, RQ_KP = RQ_KC + 4;
+constexpr int RQ_XPT = RQ_ST * RQ_KC / 256;  // sample elements per thread
+
+template <int G>
+__global__ __launch_bounds__(256) void k_roni_round_logits(
+    const float *__restrict__ Xv, int64_t nv, int64_t din, int64_t ldv,
+    const int32_t *__restrict__ yv, int C, const double *__restrict__ ww, const RoundRows rows,
+    int g, const double *__restrict__ xn, double gam, unsigned int *__restrict__ cnt,
+    const unsigned int *__restrict__ base, double *__restrict__ scores,
+    int32_t *__restrict__ near_out, int first) {
+    static_assert(G * RQ_ST <= 256 && G <= RONI_ROUND_G, "one epilogue thread per (model, sample)");
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    __shared__ __attribute__((aligned(16))) float xs[RQ_ST][RQ_KP];
+    __shared__ __attribute__((aligned(16))) float wsm[G][16][RQ_KP];
+    __shared__ float lgs[G][RQ_ST][16];
+    __shared__ double wnl[G][16], bl[G][16];
+    __shared__ unsigned int s_cnt[2 * G];
+    const int tid = threadIdx.x;
+    const int ls = tid >> 4, lc = tid & 15;
+    const int64_t s0 = (int64_t)blockIdx.x * RQ_ST;
+    if (tid < 2 * G) s_cnt[tid] = 0;
+    if (tid < 16 * G) {  // the models' fp32 biases
+        const int q = tid >> 4;
+        const double *dq = nullptr;
+#pragma unroll
+        for (int p = 0; p < G; ++p)
+            if (q == p && p < g) dq = rows.p[p];
+        const int64_t bi = (int64_t)C * din + lc;
+        bl[q][lc] = dq && lc < C ? (double)(float)(ww[bi] + dq[bi]) : 0.0;
+    }
+    // staging: thread t moves feature t & 63 of samples / classes (t >> 6) + 4 u
+    const int xk = tid & 63, xr = tid >> 6;
+    float wv[G][4], xv[RQ_XPT];
+    auto load = [&](int64_t k0) {  // every load in flight
+        const int64_t k = k0 + xk;
+        const bool kin = k < din;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = xr + 4 * u;
+            const bool on = kin && c < C;
+            const int64_t wi = on ? (int64_t)c * din + k : 0;
+            const double w0 = on ? ww[wi] : 0.0;
+#pragma unroll
+            for (int q = 0; q < G; ++q) wv[q][u] = on && q < g ? (float)(w0 + rows.p[q][wi]) : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < RQ_XPT; ++u) {
+            int64_t s = s0 + xr + 4 * u;
+            s = s < nv ? s : nv - 1;
+            xv[u] = kin ? Xv[s * ldv + k] : 0.0f;
+        }
+    };
+    double acc[G], wna[G];
+#pragma unroll
+    for (int q = 0; q < G; ++q) acc[q] = wna[q] = 0.0;
+    const bool lt = lc < C, wn = ls == 0;
+    load(0);
+    for (int64_t k0 = 0; k0 < din; k0 += RQ_KC) {
+        __syncthreads();  // the previous chunk has been consumed
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int q = 0; q < G; ++q) wsm[q][xr + 4 * u][xk] = wv[q][u];
+        }
+#pragma unroll
+        for (int u = 0; u < RQ_XPT; ++u) xs[xr + 4 * u][xk] = xv[u];
+        __syncthreads();
+        if (k0 + RQ_KC < din) load(k0 + RQ_KC);
+        if (!lt) continue;
+        const int kn = (int)(din - k0 < RQ_KC ? din - k0 : RQ_KC);
+        const float *xrow = xs[ls];
+        int kk = 0;
+        for (; kk + 16 <= kn; kk += 16) {
+            f4 xq[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) xq[p] = *reinterpret_cast<const f4 *>(xrow + kk + 4 * p);
+#pragma unroll
+            for (int q = 0; q < G; ++q) {
+                f4 wq[4];
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+                    wq[p] = *reinterpret_cast<const f4 *>(&wsm[q][lc][kk + 4 * p]);
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    const double x = (double)xq[u >> 2][u & 3], w = (double)wq[u >> 2][u & 3];
+                    acc[q] = __builtin_fma(x, w, acc[q]);
+                    if (wn) wna[q] += w * w;
+                }
+            }
+        }
+        for (; kk < kn; ++kk) {
+            const double x = (double)xrow[kk];
+#pragma unroll
+            for (int q = 0; q < G; ++q) {
+                const double w = (double)wsm[q][lc][kk];
+                acc[q] = __builtin_fma(x, w, acc[q]);
+                if (wn) wna[q] += w * w;
+            }
+        }
+    }
+    if (lt) {
+#pragma unroll
+        for (int q = 0; q < G; ++q) {
+            lgs[q][ls][lc] = (float)(acc[q] + bl[q][lc]);
+            if (wn) wnl[q][lc] = __builtin_sqrt(wna[q]);
+        }
+    }
+    __syncthreads();
+    if (tid < G * RQ_ST) {
+        const int q = tid >> 4;  // RQ_ST == 16
+        const int64_t s = s0 + lc;
+        if (q < g && s < nv) {
+            // np.argmax: the first maximum, a NaN wins at its first place
+            const float *lg = lgs[q][lc];
+            int best = 0;
+            float b0 = lg[0];
+            for (int c = 1; c < C; ++c) {
+                const float v = lg[c];
+                if (!(b0 != b0) && (v != v || v > b0)) {
+                    best = c;
+                    b0 = v;
+                }
+            }
+            if (best == yv[s]) atomicAdd(&s_cnt[q], 1u);
+            if (softmax_near_tie(lg, C, best, xn[s], wnl[q], bl[q], gam)) atomicAdd(&s_cnt[G + q], 1u);
+        }
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    unsigned int mine[2 * G];
+    int slot[2 * G];
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+        mine[q] = s_cnt[q];
+        mine[G + q] = s_cnt[G + q];
+        slot[q] = q;
+        slot[G + q] = RONI_ROUND_G + q;
+    }
+    if (!round_exit(mine, slot, cnt)) return;
+    const double dn = (double)nv;
+    const double orig = 1.0 - (double)base[0] / dn;  // k_roni_mc_score's expression
+    for (int q = 0; q < g; ++q) {
+        const double after = 1.0 - (double)round_load(cnt + q) / dn;
+        scores[q] = after - orig;
+        if (near_out) near_out[1 + q] = (int32_t)round_load(cnt + RONI_ROUND_G + q);
+    }
+    if (near_out && first) near_out[0] = (int32_t)base[1];
+}
+
+// the smallest instantiation that holds the group's g models
+hipError_t launch_roni_round(const double *Xv, int64_t nv, int64_t d, int64_t ldv, const double *yv,
+                             const double *ww, const RoundRows &rows, int g, unsigned int *cnt,
+                             const unsigned int *base, double *scores, hipStream_t st) {
+    const int64_t nwg = (nv + RR_TS - 1) / RR_TS;
+    if (g < 1 || g > RONI_ROUND_G || nwg > 0x7fffffff) return hipErrorInvalidConfiguration;
+    const dim3 grid((unsigned)nwg), blk(256);
+#define BK_ROUND_SIGN(G_)                                                                        \
+    hipLaunchKernelGGL(k_roni_round_sign<G_>, grid, blk, 0, st, Xv, nv, d, ldv, yv, ww, rows, g, \
+                       cnt, base, scores)
+    if (g == 1)
+        BK_ROUND_SIGN(1);
+    else if (g == 2)
+        BK_ROUND_SIGN(2);
+    else if (g <= 4)
+        BK_ROUND_SIGN(4);
+    else
+        BK_ROUND_SIGN(8);
+#undef BK_ROUND_SIGN
+    return hipGetLastError();
+}
+
+hipError_t launch_roni_softmax_round(const float *Xv, int64_t nv, int64_t din, int64_t ldv,
+                                     const int32_t *yv, int C, const double *ww,
+                                     const RoundRows &rows, int g, const double *xn,
+                                     unsigned int *cnt, const unsigned int *base, double *scores,
+                                     int32_t *near, int first, hipStream_t st) {
+    const int64_t nwg = (nv + RQ_ST - 1) / RQ_ST;
+    if (g < 1 || g > RONI_ROUND_G || nwg > 0x7fffffff) return hipErrorInvalidConfiguration;
+    const dim3 grid((unsigned)nwg), blk(256);
+    const double gam = roni_softmax_g(din);
+#define BK_ROUND_LOGITS(G_)                                                                       \
+    hipLaunchKernelGGL(k_roni_round_logits<G_>, grid, blk, 0, st, Xv, nv, din, ldv, yv, C, ww, rows, \
+                       g, xn, gam, cnt, base, scores, near, first)
+    if (g == 1)
+        BK_ROUND_LOGITS(1);
+    else if (g == 2)
+        BK_ROUND_LOGITS(2);
+    else if (g <= 4)
+        BK_ROUND_LOGITS(4);
+    else
+        BK_ROUND_LOGITS(8);
+#undef BK_ROUND_LOGITS
     return hipGetLastError();
 }
 

@@ -730,7 +730,7 @@ class Engine:
         check(lib().bk_graph_enable(self._ctx, 1 if on else 0))
 
     def timing_select(self, kernels):
-        """Time only these kernels (names from _lib.KERNELS)."""
+        """Time only these kernels (names from _lib.ALL_KERNELS)."""
         mask = 0
         for k in kernels:
             mask |= 1 << _lib.K[k]
@@ -742,7 +742,7 @@ class Engine:
 
     def timing_read(self):
         out = {}
-        for i, name in enumerate(_lib.KERNELS):
+        for i, name in enumerate(_lib.ALL_KERNELS):
             ms = ctypes.c_double(0)
             cnt = ctypes.c_int64(0)
             check(lib().bk_timing_read(self._ctx, i, ctypes.byref(ms), ctypes.byref(cnt)))

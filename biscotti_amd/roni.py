@@ -8,15 +8,21 @@
     .verify_update(update)        Peer.VerifyUpdateRONI, DistSys/main.go:191-233:
                                   accept iff PRIV_PROB > 0 or score <= 0.02
     .scores(ww, deltas)           the batched form (one launch for n updates)
+    .begin_round(ww)              the deployed form: the iteration's model held
+    .score_round(deltas)          on the GPU with its evaluation done, each
+                                  update scored on its own (bk_roni_round_*);
+                                  verify_update(..., round=True) drives it
 
 Everything runs through libbk.so on the GPU (bk_roni_set_validation / bk_roni);
 there is no CPU path.
 """
 from typing import Optional, Sequence
 
+import ctypes
+
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import BK_HOST, check, lib
 from .krum import Engine, Update, default_engine
 
 __all__ = ["RONI_THRESHOLD", "RONIValidator", "SoftmaxRONIValidator", "set_validation", "roni"]
@@ -51,9 +57,58 @@ class RONIValidator:
     def roni(self, ww, delta) -> float:
         return float(self.scores(ww, np.asarray(delta)[None])[0])
 
-    def verify_update(self, update: Update, latest_gradient) -> bool:
-        """True = accept (sign), False = reject (updateError)."""
-        score = self.roni(latest_gradient, update.NoisedDelta)
+    # ---- rounds: bc.getLatestGradient() is the same model for every update
+    #      of an iteration (honest.go:598-629), so it is evaluated once ------
+    _round_ww = None   # the held model's host copy
+    rounds_begun = 0   # begin_round calls (verify_update(round=True): one per distinct model)
+    last_score = None  # the score behind the last verify_update verdict
+
+    def _begin(self, ww):
+        check(lib().bk_roni_round_begin(self._engine.ctx, ww.ctypes.data, self.d, BK_HOST))
+
+    def _score(self, rows, out):
+        check(lib().bk_roni_round_score(self._engine.ctx, rows, len(rows), BK_HOST,
+                                        out.ctypes.data))
+
+    def begin_round(self, ww):
+        """Hold ww on the GPU with its evaluation done (bk_roni*_round_begin)."""
+        ww = np.array(ww, dtype=np.float64, order="C")  # the validator's own copy
+        if ww.shape != (self.d,):
+            raise ValueError("ww must be (d,) with d = %d" % self.d)
+        self._round_ww = None
+        self._begin(ww)
+        self._round_ww = ww
+        self.rounds_begun += 1
+
+    def score_round(self, deltas) -> np.ndarray:
+        """Scores of separately allocated updates against the held model,
+        bitwise scores(ww, deltas)'s (bk_roni*_round_score)."""
+        if self._round_ww is None:
+            raise ValueError("no round: call begin_round(ww) first")
+        rows = [np.ascontiguousarray(r, dtype=np.float64) for r in deltas]
+        if not rows or any(r.shape != (self.d,) for r in rows):
+            raise ValueError("deltas must be a non-empty sequence of (d,) rows with d = %d" % self.d)
+        out = np.empty(len(rows), dtype=np.float64)
+        self._score((ctypes.c_void_p * len(rows))(*[r.ctypes.data for r in rows]), out)
+        return out
+
+    def _round_score_one(self, latest_gradient, delta) -> float:
+        held = self._round_ww
+        if held is None or not (latest_gradient is held or
+                                np.array_equal(held, latest_gradient, equal_nan=True)):
+            self.begin_round(latest_gradient)
+        return float(self.score_round([delta])[0])
+
+    def verify_update(self, update: Update, latest_gradient, round: bool = False) -> bool:
+        """True = accept (sign), False = reject (updateError).  round=True
+        begins a round when latest_gradient differs from the held model, then
+        scores the one update against it: the same score, without evaluating
+        the model again."""
+        if round:
+            score = self._round_score_one(latest_gradient, update.NoisedDelta)
+        else:
+            score = self.roni(latest_gradient, update.NoisedDelta)
+        self.last_score = score
         if self.priv_prob > 0:
             return True
         return not (score > RONI_THRESHOLD)
@@ -109,6 +164,28 @@ class SoftmaxRONIValidator(RONIValidator):
         check(lib().bk_roni_softmax_set_validation(self._engine.ctx, X.ctypes.data, self.nv,
                                                    self.d_in, self.d_in, y.ctypes.data,
                                                    self.n_classes))
+
+    def _begin(self, ww):
+        check(lib().bk_roni_softmax_round_begin(self._engine.ctx, ww.ctypes.data, BK_HOST))
+
+    def _score(self, rows, out):
+        nt = np.empty(len(rows) + 1, dtype=np.int32)
+        check(lib().bk_roni_softmax_round_score(self._engine.ctx, rows, len(rows), BK_HOST,
+                                                out.ctypes.data, nt.ctypes.data))
+        self.last_near_ties = nt
+        self.last_idx = None
+
+    def begin_round(self, ww):
+        if self.batch_size is not None:
+            raise ValueError("rounds score over the whole set: build the validator with "
+                             "batch_size=None (each update's `original` is drawn on its own "
+                             "random mini-batch, so nothing is shared)")
+        super().begin_round(ww)
+
+    def verify_update(self, update: Update, latest_gradient, round: bool = False) -> bool:
+        if round and self.batch_size is not None:
+            raise ValueError("round=True needs batch_size=None")
+        return super().verify_update(update, latest_gradient, round)
 
     def last_batch(self) -> np.ndarray:
         """One shuffled pass's last mini-batch (DataLoader(shuffle=True))."""

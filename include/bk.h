@@ -818,6 +818,41 @@ int bk_roni_softmax_batches(bk_ctx *ctx, const double *ww, const double *deltas,
                             int64_t ld, const int64_t *idx, int64_t nb, double *scores,
                             int32_t *near_ties);
 
+/* RONI rounds: the verifier's deployed sequence.  Peer.VerifyUpdateRONI
+ * (DistSys/main.go:191-233) scores ONE update per RPC against
+ * bc.getLatestGradient(), the same model for every update of an iteration
+ * (verifyUpdate, honest.go:598-629).  A round holds that model on the device
+ * with its evaluation done, so a score call does the new models' work only.
+ *   *_round_begin  needs the matching *_set_validation.  ww (d weights; the
+ *                  softmax form's d is the validation set's n_classes *
+ *                  (d_in + 1)) is at `where` (BK_HOST, BK_HOST_PINNED or
+ *                  BK_DEVICE) and is consumed on return; its evaluation (the
+ *                  logistic mismatch count; the softmax correct and near-tie
+ *                  counts) runs on asynchronously on the context stream.  The
+ *                  round lives until the next begin of its kind or the next
+ *                  *_set_validation, which invalidates it.
+ *   *_round_score  count >= 1 separately allocated rows of d doubles at `where`
+ *                  (bk_collect_add's pointer-table contract: 8-byte aligned, no
+ *                  pointer retained on return).  Writes scores[i], and for the
+ *                  softmax form near_ties (nullable, 1 + count: the base model,
+ *                  then update i at 1 + i).  Synchronous.  Every score and
+ *                  near-tie count is bitwise what one bk_roni / bk_roni_softmax
+ *                  call on the same ww and rows returns.  Groups of up to
+ *                  BK_RONI_ROUND_G updates share one launch (one pass over the
+ *                  validation set); a larger count is split into groups.
+ * BK_EINVAL: a null pointer, count < 1, a bad where, no validation set, d other
+ * than the validation set's, or a score without a live round; BK_ENOTSUP: count
+ * beyond bk_roni's / bk_roni_softmax's n.  A refused call leaves the round as it
+ * was.  Added without a change of BK_ABI_VERSION (14), as bk_collect_add_noised
+ * was. */
+#define BK_RONI_ROUND_G 8
+int bk_roni_round_begin(bk_ctx *ctx, const double *ww, int64_t d, int where);
+int bk_roni_round_score(bk_ctx *ctx, const double *const *deltas, int64_t count, int where,
+                        double *scores);
+int bk_roni_softmax_round_begin(bk_ctx *ctx, const double *ww, int where);
+int bk_roni_softmax_round_score(bk_ctx *ctx, const double *const *deltas, int64_t count, int where,
+                                double *scores, int32_t *near_ties);
+
 /* ---- measurement: per-kernel HIP-event timing on the context stream ------- */
 enum bk_kernel_id {
     BK_K_GRAM = 0,     /* K1  fp64-MFMA split-K upper-triangle Gram partials */
@@ -842,7 +877,9 @@ enum bk_kernel_id {
      * the last all-reduce -- the exchange time the overlap left exposed
      * (BK_K_ALLREDUCE is then the span from the first all-reduce's start) */
     BK_K_EXCHANGE_EXPOSED = 18,
-    BK_NUM_KERNELS = 19
+    BK_K_RONI_ROUND = 19,    /* k_roni_round_sign: a round's score launches (bk_roni_round_score) */
+    BK_K_RONI_ROUND_SM = 20, /* k_roni_round_logits (bk_roni_softmax_round_score)  */
+    BK_NUM_KERNELS = 21
 };
 int bk_timing_enable(bk_ctx *ctx, int on);   /* all kernels; clears accumulated timings */
 /* Time only the kernels whose bit (1u << kernel_id) is set: every timed kernel
