@@ -93,6 +93,7 @@ SIGNATURES = {
     "bk_roni_round_score": (_i, [_p, _p, _i64, _i, _p]),
     "bk_roni_softmax_round_begin": (_i, [_p, _p, _i]),
     "bk_roni_softmax_round_score": (_i, [_p, _p, _i64, _i, _p, _p]),
+    "bk_roni_softmax_round_score_batches": (_i, [_p, _p, _i64, _i, _p, _i64, _p, _p]),
     "bk_group_create": (_i, [ctypes.POINTER(_p), _i, _p, _i]),
     "bk_group_destroy": (None, [_p]),
     "bk_group_size": (_i, [_p]),

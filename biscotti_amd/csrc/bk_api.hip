@@ -218,7 +218,7 @@ void bk_destroy(bk_ctx *c) {
                           &c->mean_part, &c->status, &c->rmc_X, &c->rmc_y, &c->rmc_ws,
                       &c->rmc_xn, &c->rmc_idx, &c->rmc_nt, &c->i8ws, &c->sgather, &c->pcnt,
                           &c->rr_w, &c->rr_base, &c->rr_ws, &c->rs_w, &c->rs_base, &c->rs_ws,
-                          &c->round_rows, &c->round_cnt,
+                          &c->round_rows, &c->round_cnt, &c->round_idx,
                           &c->batch_ctr, &c->batch_part, &c->batch_diag, &c->batch_scores,
                           &c->batch_rec, &c->batch_X, &c->batch_sel, &c->batch_hsc, &c->batch_mean,
                           &c->batch_desc};

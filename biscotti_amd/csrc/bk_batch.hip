@@ -17,6 +17,32 @@
 
 namespace bk {
 
+// the next slot of the pinned ring, `bytes` large, free to write: the call
+// that used it last has had its copy run (its event).  Shared with the RONI
+// rounds' batch indices (bk_entries.hip)
+int ragged_stage_slot(bk_ctx *c, size_t bytes, int *slot) {
+    const int s = c->ragged_next;
+    c->ragged_next = (s + 1) % bk_ctx::RAGGED_SLOTS;
+    if (!c->ev_ragged[s])
+        HIPCHK(hipEventCreateWithFlags(&c->ev_ragged[s], hipEventDisableTiming));
+    if (c->ragged_used[s]) HIPCHK(hipEventSynchronize(c->ev_ragged[s]));
+    c->ragged_used[s] = false;
+    if (c->ragged_stage_bytes[s] < bytes) {
+        if (c->ragged_stage[s]) (void)hipHostFree(c->ragged_stage[s]);
+        c->ragged_stage[s] = nullptr;
+        c->ragged_stage_bytes[s] = 0;
+        const size_t want = bytes < 4096 ? 4096 : bytes;
+        const hipError_t e = hipHostMalloc(&c->ragged_stage[s], want, hipHostMallocPortable);
+        if (e != hipSuccess) {
+            c->ragged_stage[s] = nullptr;
+            return fail(BK_ENOMEM, "hipHostMalloc(%zu bytes): %s", want, hipGetErrorString(e));
+        }
+        c->ragged_stage_bytes[s] = want;
+    }
+    *slot = s;
+    return BK_OK;
+}
+
 namespace {
 
 // the partials of one launch: BK_BATCH_WS_BYTES, read at the call; it may only
@@ -186,31 +212,6 @@ int check_ragged(bk_ctx *c, const void *X, int dtype, int64_t batch, const int64
 }
 
 constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// the next slot of the pinned ring, `bytes` large, free to write: the call
-// that used it last has had its copy run (its event)
-int ragged_stage_slot(bk_ctx *c, size_t bytes, int *slot) {
-    const int s = c->ragged_next;
-    c->ragged_next = (s + 1) % bk_ctx::RAGGED_SLOTS;
-    if (!c->ev_ragged[s])
-        HIPCHK(hipEventCreateWithFlags(&c->ev_ragged[s], hipEventDisableTiming));
-    if (c->ragged_used[s]) HIPCHK(hipEventSynchronize(c->ev_ragged[s]));
-    c->ragged_used[s] = false;
-    if (c->ragged_stage_bytes[s] < bytes) {
-        if (c->ragged_stage[s]) (void)hipHostFree(c->ragged_stage[s]);
-        c->ragged_stage[s] = nullptr;
-        c->ragged_stage_bytes[s] = 0;
-        const size_t want = bytes < 4096 ? 4096 : bytes;
-        const hipError_t e = hipHostMalloc(&c->ragged_stage[s], want, hipHostMallocPortable);
-        if (e != hipSuccess) {
-            c->ragged_stage[s] = nullptr;
-            return fail(BK_ENOMEM, "hipHostMalloc(%zu bytes): %s", want, hipGetErrorString(e));
-        }
-        c->ragged_stage_bytes[s] = want;
-    }
-    *slot = s;
-    return BK_OK;
-}
 
 // bk_multikrum_ragged_device past its checks.  The problems within k_small's
 // range go by NB = ceil(n_b / 16) into buckets: small_plan depends on n only

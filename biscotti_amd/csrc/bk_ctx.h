@@ -161,8 +161,10 @@ struct bk_ctx {
     int rr_live = 0, rs_live = 0;
     // a score call's scratch: host rows staged on the device, the groups'
     // counters, and the mapped pinned block the kernel writes the scores (and
-    // near-tie counts) into: no device-to-host copy
-    DevBuf round_rows, round_cnt;
+    // near-tie counts) into: no device-to-host copy; round_idx: the mini-batch
+    // form's sample indices when a group has too many for the kernel's
+    // arguments (they go up through the ragged calls' pinned ring)
+    DevBuf round_rows, round_cnt, round_idx;
     void *round_out = nullptr;
     void *round_out_dev = nullptr;
     size_t round_out_bytes = 0;
@@ -355,6 +357,7 @@ int margin_status(const double *mg);
 int read_margin(bk_ctx *c, double (&mg)[MARGIN_WORDS]);
 int check_margin_readback(bk_ctx *c);
 // bk_batch.hip
+int ragged_stage_slot(bk_ctx *c, size_t bytes, int *slot);
 int batch_fetch(bk_ctx *c);
 void batch_pick_record(bk_ctx *c);
 // bk_host.hip

@@ -389,9 +389,9 @@ static int round_upload_ww(bk_ctx *c, DevBuf &w, const double *ww, int64_t d, in
 }
 
 // the mapped pinned block a score call's kernels write: count scores, then
-// 1 + count near-tie counts
-static int ensure_round_out(bk_ctx *c, int64_t count) {
-    const size_t bytes = (size_t)count * sizeof(double) + (size_t)(count + 1) * sizeof(int32_t);
+// nnt near-tie counts (1 + count; the mini-batch form: 2 count)
+static int ensure_round_out(bk_ctx *c, int64_t count, int64_t nnt) {
+    const size_t bytes = (size_t)count * sizeof(double) + (size_t)nnt * sizeof(int32_t);
     if (bytes <= c->round_out_bytes) return BK_OK;
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->round_out) (void)hipHostFree(c->round_out);
@@ -407,17 +407,20 @@ static int ensure_round_out(bk_ctx *c, int64_t count) {
 
 // A score call past its checks (the context mutex held): host rows staged on
 // the device (device rows are read where they are), the groups' counters
-// zeroed, one launch per group of up to RONI_ROUND_G rows, one wait, then host
-// memcpys out of the mapped block.  launch(rows, g, cnt, scores, near, first)
+// zeroed (cnt_words each), one launch per group of up to RONI_ROUND_G rows, one
+// wait, then host memcpys out of the mapped block (count scores, nnt near-tie
+// counts).  launch(rows, g, q0, cnt, scores, near): the group of rows q0 ..
+// q0 + g, its counters, and the block's score and near-tie (nullable) arrays
 template <typename F>
 static int round_score(bk_ctx *c, int kid, const double *const *deltas, int64_t count, int where,
-                       int64_t d, double *scores, int32_t *near_ties, F &&launch) {
+                       int64_t d, double *scores, int32_t *near_ties, int64_t nnt, int cnt_words,
+                       F &&launch) {
     DeviceGuard dg(c->device);
     HostDrain drain{c};  // error returns: queued copies and launches may still read the rows
     const int64_t groups = (count + RONI_ROUND_G - 1) / RONI_ROUND_G;
-    const size_t cbytes = (size_t)groups * ROUND_CNT_WORDS * sizeof(unsigned int);
+    const size_t cbytes = (size_t)groups * cnt_words * sizeof(unsigned int);
     CHK(ensure(c->round_cnt, cbytes));
-    CHK(ensure_round_out(c, count));
+    CHK(ensure_round_out(c, count, nnt));
     const double *staged = nullptr;
     if (where != BK_DEVICE) {
         CHK(ensure(c->round_rows, (size_t)count * d * sizeof(double)));
@@ -438,16 +441,14 @@ static int round_score(bk_ctx *c, int kid, const double *const *deltas, int64_t 
         const int g = (int)(count - q0 < RONI_ROUND_G ? count - q0 : RONI_ROUND_G);
         RoundRows rows = {};
         for (int q = 0; q < g; ++q) rows.p[q] = staged ? staged + (q0 + q) * d : deltas[q0 + q];
-        unsigned int *cnt = (unsigned int *)c->round_cnt.p + q0 / RONI_ROUND_G * ROUND_CNT_WORDS;
-        CHK(timed(c, kid, [&] {
-            return launch(rows, g, cnt, dsc + q0, dnt ? dnt + q0 : nullptr, q0 == 0 ? 1 : 0);
-        }));
+        unsigned int *cnt = (unsigned int *)c->round_cnt.p + q0 / RONI_ROUND_G * cnt_words;
+        CHK(timed(c, kid, [&] { return launch(rows, g, q0, cnt, dsc, dnt); }));
     }
     HIPCHK(wait_stream(c));
     drain.armed = false;
     const char *h = (const char *)c->round_out;
     memcpy(scores, h, (size_t)count * sizeof(double));
-    if (near_ties) memcpy(near_ties, h + (size_t)count * sizeof(double), (size_t)(count + 1) * sizeof(int32_t));
+    if (near_ties) memcpy(near_ties, h + (size_t)count * sizeof(double), (size_t)nnt * sizeof(int32_t));
     return BK_OK;
 }
 
@@ -496,13 +497,14 @@ int bk_roni_round_score(bk_ctx *c, const double *const *deltas, int64_t count, i
     CHK(check_roni(nv, d, d, count, d));
     CHK(check_round_rows(deltas, count, scores));
     CHK(check_where(where));
-    return round_score(c, BK_K_RONI_ROUND, deltas, count, where, d, scores, nullptr,
-                       [&](const RoundRows &rows, int g, unsigned int *cnt, double *sc, int32_t *,
-                           int) {
+    return round_score(c, BK_K_RONI_ROUND, deltas, count, where, d, scores, nullptr, 0,
+                       ROUND_CNT_WORDS,
+                       [&](const RoundRows &rows, int g, int64_t q0, unsigned int *cnt, double *sc,
+                           int32_t *) {
                            return launch_roni_round((const double *)c->roni_X.p, nv, d, d,
                                                     (const double *)c->roni_y.p,
                                                     (const double *)c->rr_w.p, rows, g, cnt,
-                                                    (const unsigned int *)c->rr_base.p, sc,
+                                                    (const unsigned int *)c->rr_base.p, sc + q0,
                                                     c->stream);
                        });
 }
@@ -546,14 +548,80 @@ int bk_roni_softmax_round_score(bk_ctx *c, const double *const *deltas, int64_t 
     CHK(check_roni_softmax(nv, din, din, C, count, d));
     CHK(check_round_rows(deltas, count, scores));
     CHK(check_where(where));
-    return round_score(c, BK_K_RONI_ROUND_SM, deltas, count, where, d, scores, near_ties,
-                       [&](const RoundRows &rows, int g, unsigned int *cnt, double *sc, int32_t *nt,
-                           int first) {
+    return round_score(c, BK_K_RONI_ROUND_SM, deltas, count, where, d, scores, near_ties, count + 1,
+                       ROUND_CNT_WORDS,
+                       [&](const RoundRows &rows, int g, int64_t q0, unsigned int *cnt, double *sc,
+                           int32_t *nt) {
                            return launch_roni_softmax_round(
                                (const float *)c->rmc_X.p, nv, din, din, (const int32_t *)c->rmc_y.p,
                                (int)C, (const double *)c->rs_w.p, rows, g,
                                (const double *)c->rmc_xn.p, cnt, (const unsigned int *)c->rs_base.p,
-                               sc, nt, first, c->stream);
+                               sc + q0, nt ? nt + q0 : nullptr, q0 == 0 ? 1 : 0, c->stream);
+                       });
+}
+
+// The mini-batch form on the same round (bk_roni_softmax_batches' semantics):
+// every check before any copy, launch or state change.  A group's indices ride
+// in its launch's arguments when there are at most ROUND_IDX_ARGS of them (the
+// verifier's 2 x 10); else all of the call's go up once, as int32, through the
+// ragged calls' pinned ring (its slot's event guards the staging bytes)
+int bk_roni_softmax_round_score_batches(bk_ctx *c, const double *const *deltas, int64_t count,
+                                        int where, const int64_t *idx, int64_t nb, double *scores,
+                                        int32_t *near_ties) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!deltas || !idx || !scores) return fail(BK_EINVAL, "null pointer argument");
+    if (count < 1) return fail(BK_EINVAL, "count=%lld < 1", (long long)count);
+    if (nb < 1) return fail(BK_EINVAL, "need a batch of nb >= 1 samples (nb=%lld)", (long long)nb);
+    CHK(check_where(where));
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->rmc_nv < 1) return fail(BK_EINVAL, "no validation set: call bk_roni_softmax_set_validation");
+    if (!c->rs_live) return fail(BK_EINVAL, "no round: call bk_roni_softmax_round_begin");
+    const int64_t nv = c->rmc_nv, din = c->rmc_din, C = c->rmc_C, d = C * (din + 1);
+    CHK(check_roni_softmax(nv, din, din, C, count, d));
+    CHK(check_round_rows(deltas, count, scores));
+    for (int64_t j = 0; j < count; ++j)
+        for (int e = 0; e < 2; ++e)
+            for (int64_t s = 0; s < nb; ++s) {
+                const int64_t v = idx[(2 * j + e) * nb + s];
+                if (v < 0 || v >= nv)
+                    return fail(BK_EINVAL,
+                                "batch index %lld outside [0, %lld): update %lld, evaluation %d "
+                                "(%s), position %lld",
+                                (long long)v, (long long)nv, (long long)j, e,
+                                e ? "after" : "original", (long long)s);
+            }
+    DeviceGuard dg(c->device);
+    const int64_t g0 = count < RONI_ROUND_G ? count : RONI_ROUND_G;  // the largest group
+    const int32_t *didx = nullptr;
+    if (2 * g0 * nb > ROUND_IDX_ARGS) {
+        const int64_t total = 2 * count * nb;
+        const size_t bytes = (size_t)total * sizeof(int32_t);
+        CHK(ensure(c->round_idx, bytes));
+        int slot = 0;
+        CHK(ragged_stage_slot(c, bytes, &slot));
+        int32_t *hs = (int32_t *)c->ragged_stage[slot];
+        for (int64_t i = 0; i < total; ++i) hs[i] = (int32_t)idx[i];
+        CHK(timed(c, BK_K_H2D, [&] {
+            return hipMemcpyAsync(c->round_idx.p, hs, bytes, hipMemcpyHostToDevice, c->stream);
+        }));
+        HIPCHK(hipEventRecord(c->ev_ragged[slot], c->stream));
+        c->ragged_used[slot] = true;
+        didx = (const int32_t *)c->round_idx.p;
+    }
+    return round_score(c, BK_K_RONI_ROUND_SM, deltas, count, where, d, scores, near_ties, 2 * count,
+                       ROUND_BATCH_CNT_WORDS,
+                       [&](const RoundRows &rows, int g, int64_t q0, unsigned int *cnt, double *sc,
+                           int32_t *nt) {
+                           RoundIdx ia = {};
+                           const bool in_args = 2 * g * nb <= ROUND_IDX_ARGS;
+                           if (in_args)
+                               for (int64_t i = 0; i < 2 * g * nb; ++i)
+                                   ia.v[i] = (int32_t)idx[2 * q0 * nb + i];
+                           return launch_roni_softmax_round_batch(
+                               (const float *)c->rmc_X.p, nv, din, din, (const int32_t *)c->rmc_y.p,
+                               (int)C, (const double *)c->rs_w.p, rows, g,
+                               in_args ? nullptr : didx + 2 * q0 * nb, ia, nb, cnt, sc + q0,
+                               nt ? nt + 2 * q0 : nullptr, c->stream);
                        });
 }
 

@@ -301,6 +301,22 @@ hipError_t launch_roni_softmax_round(const float *Xv, int64_t nv, int64_t din, i
                                      const RoundRows &rows, int g, const double *xn,
                                      unsigned int *cnt, const unsigned int *base, double *scores,
                                      int32_t *near, int first, hipStream_t st);
+// The mini-batch form of a softmax round's score launch (k_roni_round_batch):
+// up to RONI_ROUND_G updates, each scored as k_roni_batch scores it, on batches
+// idx (2 g nb sample indices, range-checked int32: update q's `original` at
+// (2 q) nb, its `after` at (2 q + 1) nb) -- idx_dev on the device, or null and
+// the indices in idx_arg when there are at most ROUND_IDX_ARGS of them.  cnt:
+// ROUND_BATCH_CNT_WORDS zeroed words; scores (g) and near (nullable, 2 g) are
+// written by the last workgroup out
+constexpr int ROUND_BATCH_CNT_WORDS = 48, ROUND_IDX_ARGS = 256;
+struct RoundIdx {
+    int32_t v[ROUND_IDX_ARGS];
+};
+hipError_t launch_roni_softmax_round_batch(const float *Xv, int64_t nv, int64_t din, int64_t ldv,
+                                           const int32_t *yv, int C, const double *ww,
+                                           const RoundRows &rows, int g, const int32_t *idx_dev,
+                                           const RoundIdx &idx_arg, int64_t nb, unsigned int *cnt,
+                                           double *scores, int32_t *near, hipStream_t st);
 // bk_i8.hip: K1i8, the Gram of fp32 rows from exact int8 digit slices
 // (BK_F32_I8): column ranges (one per XCD), digit planes [3][npad][dp] int8
 struct I8Layout {

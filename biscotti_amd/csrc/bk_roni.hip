@@ -19,6 +19,9 @@
 //   K7r / K8r k_roni_round_sign, k_roni_round_logits: a round's score launches
 //       (r15): up to 8 new models against a model evaluated once per iteration,
 //       on per-lane FMA chains, the score in the launch's tail (at the end)
+//   K8r' k_roni_round_batch: the softmax round's score launch on the last
+//       mini-batches (r16): k_roni_batch's arithmetic, a workgroup per (update,
+//       evaluation, tile of 16 samples), against the model the round holds
 //
 // Built with -ffp-contract=off: ww + delta rounds exactly like numpy; every dot
 // is a plain fp64 FMA chain over k ascending (the MFMA chains round alike,
@@ -1008,13 +1011,13 @@ __device__ inline unsigned int round_load(const unsigned int *p) {
 // for the last workgroup out, which may then read every workgroup's adds
 template <int NC>
 __device__ inline bool round_exit(const unsigned int (&s_cnt)[NC], const int (&slot)[NC],
-                                  unsigned int *cnt) {
+                                  unsigned int *cnt, int exit_slot = ROUND_EXIT) {
 #pragma unroll
     for (int q = 0; q < NC; ++q)
         if (s_cnt[q])
             __hip_atomic_fetch_add(cnt + slot[q], s_cnt[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    return __hip_atomic_fetch_add(cnt + ROUND_EXIT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
+    return __hip_atomic_fetch_add(cnt + exit_slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
            gridDim.x - 1u;
 }
 
@@ -1313,6 +1316,203 @@ hipError_t launch_roni_softmax_round(const float *Xv, int64_t nv, int64_t din, i
     else
         BK_ROUND_LOGITS(8);
 #undef BK_ROUND_LOGITS
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// K8r' k_roni_round_batch (r16): a round's score launch with the reference's
+// last-mini-batch semantics (k_roni_batch's, above) -- the deployed mnist
+// verifier.  k_roni_batch runs an update's two evaluations in ONE workgroup; at
+// count = 1 that is the whole launch.  Here a workgroup is one (update q,
+// evaluation e, tile t of 16 samples): 2 g ceil(nb / 16) workgroups, evaluation
+// 0 reading the held model only (never a delta), evaluation 1 forming
+// fp32(ww + delta_q) (the fp64 add, one rounding).  The tile's gathered samples
+// and the model's 16 class rows go through LDS in chunks of 128 features (row
+// stride 132 floats: the 16-B reads of 16 rows cover all 64 banks), the next
+// chunk's loads in flight under this chunk's chains.
+// A thread is ONE chain over k ascending from +0.0, acc = fma(a_k, b_k, acc),
+// 16 features at a time read as float4s: threads [0, 16 C) the logits (s, c) =
+// (i / C, i % C) with a = x_s, b = w_c, as k_roni_batch's threads run them; the
+// next 16 threads |x_s|^2 (a = b = x_s), the next C |w_c|^2 (a = b = w_c).  A
+// square of a widened fp32 is exact in fp64, so fma(v, v, acc) is k_roni_batch's
+// `acc += v * v` bit for bit: its own sequential sums, NOT k_roni_xnorm's /
+// k_roni_wnorm's held values (the near-tie counts are k_roni_batch's; every
+// tile recomputes |w_c|, the same sum each time).  The first form of this
+// kernel added the squares beside the logit chain in the same lanes as
+// k_roni_batch does: 7 fp64-rate instructions per feature and wave (two
+// converts, the FMA, two multiplies, two adds) where this one issues 3 (DESIGN
+// §5m).  16 C + 16 + C chains are 4 waves up to C = 14 and 5 beyond.  Then
+// logit = fp32(acc + b), and wave 0's lane s takes np.argmax, the label compare
+// and softmax_near_tie; two ballots count them.
+// The tail is the round kernels': lane 0 adds the workgroup's two counts to the
+// group's block (cnt: [0, G) good of evaluation 0, [G, 2 G) of evaluation 1,
+// [2 G, 4 G) the near ties alike, [4 G] the exit counter; zeroed by the host
+// before every launch), and the last workgroup out writes every update's score
+// -- k_roni_batch's fp64 expression -- and near-tie pair.
+// The indices (int32 after the host's range check) come in the kernel's
+// arguments when the group has at most ROUND_IDX_ARGS of them (the verifier's 20),
+// else from a staged device copy; a row outside [0, nv) is read as row 0.
+// Bound: latency -- one load round trip, then din dependent fp64 FMAs per lane.
+constexpr int RBR_ST = 16, RBR_KC = 128, RBR_NT = 320;  // 16 x 16 + 16 + 16 chains at most
+static_assert(RBR_KC % 16 == 0 && 256 % RBR_KC == 0, "whole float4 groups, whole staging passes");
+constexpr int RBR_GOOD = 0, RBR_NEAR = 2 * RONI_ROUND_G, RBR_EXIT = 4 * RONI_ROUND_G;
+static_assert(RBR_EXIT < ROUND_BATCH_CNT_WORDS, "the exit counter lies in the block");
+
+__device__ inline int64_t rbr_idx(const int32_t *p, int64_t i) { return p[i]; }
+__device__ inline int64_t rbr_idx(const RoundIdx &a, int64_t i) { return a.v[i]; }
+
+// threads of a workgroup: the chains in whole waves, at least the 256 that stage
+static inline int rbr_threads(int C) {
+    const int chains = RBR_ST * C + RBR_ST + C;
+    return chains <= 256 ? 256 : (chains + 63) / 64 * 64;
+}
+
+template <typename IDX>
+__global__ __launch_bounds__(RBR_NT) void k_roni_round_batch(
+    const float *__restrict__ Xv, int64_t nv, int64_t din, int64_t ldv,
+    const int32_t *__restrict__ yv, int C, const double *__restrict__ ww, const RoundRows rows,
+    int g, const IDX idx, int64_t nb, int tiles, double gam, unsigned int *__restrict__ cnt,
+    double *__restrict__ scores, int32_t *__restrict__ near_out) {
+    constexpr int KC = RBR_KC, KP = KC + 4, PT = RBR_ST * KC / 256, RS = 256 / KC;  // RS rows per staging pass
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    __shared__ __attribute__((aligned(16))) float xs[RBR_ST][KP];
+    __shared__ __attribute__((aligned(16))) float wsm[16][KP];
+    __shared__ float lgs[RBR_ST][16];
+    __shared__ double xnl[RBR_ST], wnl[16], bl[16];
+    __shared__ int64_t srow[RBR_ST];
+    const int tid = threadIdx.x;
+    // this thread's chain: a logit (ls, lc), |x_ls|^2, |w_lc|^2, or none
+    const int nlog = RBR_ST * C;
+    const bool is_log = tid < nlog, is_xn = !is_log && tid < nlog + RBR_ST,
+               is_wn = tid >= nlog + RBR_ST && tid < nlog + RBR_ST + C;
+    const int ls = is_log ? tid / C : is_xn ? tid - nlog : 0;
+    const int lc = is_log ? tid - ls * C : is_wn ? tid - nlog - RBR_ST : 0;
+    const float *arow = is_wn ? wsm[lc] : xs[ls], *brow = is_xn ? xs[ls] : wsm[lc];
+    const bool chain = is_log || is_xn || is_wn, stager = tid < 256;
+    // workgroup (q, e, t), the tile fastest
+    const int t = (int)(blockIdx.x % (unsigned)tiles), qe = (int)(blockIdx.x / (unsigned)tiles);
+    const int e = qe & 1, q = qe >> 1;
+    const double *dq = nullptr;  // evaluation 0: the held model alone
+#pragma unroll
+    for (int p = 0; p < RONI_ROUND_G; ++p)
+        if (e == 1 && q == p) dq = rows.p[p];
+    const int64_t st0 = (int64_t)t * RBR_ST;
+    const int ns = (int)(nb - st0 < RBR_ST ? nb - st0 : RBR_ST);
+    if (tid < RBR_ST) {  // the tile's sample rows (padding repeats its first sample, never counted)
+        int64_t row = rbr_idx(idx, (int64_t)(2 * q + e) * nb + st0 + (tid < ns ? tid : 0));
+        if (row < 0 || row >= nv) row = 0;  // the host has range-checked: never read out of range
+        srow[tid] = row;
+    }
+    if (tid < 16) {  // the model's fp32 biases
+        const int64_t bi = (int64_t)C * din + tid;
+        double b = 0.0;
+        if (tid < C) b = (double)(float)(dq ? ww[bi] + dq[bi] : ww[bi]);
+        bl[tid] = b;
+    }
+    // staging (the first 256 threads): thread t moves feature t % KC of samples
+    // / classes t / KC + RS u
+    const int xk = tid % KC, xr = (tid & 255) / KC;
+    double wa[PT], wb[PT];
+    float xv[PT];
+    auto load = [&](int64_t k0) {  // every load in flight
+        const int64_t k = k0 + xk;
+        const bool kin = k < din;
+#pragma unroll
+        for (int u = 0; u < PT; ++u) {
+            const int c = xr + RS * u;
+            const bool on = kin && c < C;
+            const int64_t wi = on ? (int64_t)c * din + k : 0;
+            wa[u] = on ? ww[wi] : 0.0;
+            wb[u] = on && dq ? dq[wi] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < PT; ++u) xv[u] = kin ? Xv[srow[xr + RS * u] * ldv + k] : 0.0f;
+    };
+    double acc = 0.0;
+    __syncthreads();  // srow is written
+    if (stager) load(0);
+    for (int64_t k0 = 0; k0 < din; k0 += KC) {
+        __syncthreads();  // the previous chunk has been consumed
+        if (stager) {
+#pragma unroll
+            for (int u = 0; u < PT; ++u) {
+                wsm[xr + RS * u][xk] = dq ? (float)(wa[u] + wb[u]) : (float)wa[u];
+                xs[xr + RS * u][xk] = xv[u];
+            }
+        }
+        __syncthreads();
+        if (stager && k0 + KC < din) load(k0 + KC);
+        if (!chain) continue;
+        const int kn = (int)(din - k0 < KC ? din - k0 : KC);
+        int kk = 0;
+        for (; kk + 16 <= kn; kk += 16) {
+            f4 aq[4], bq[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                aq[p] = *reinterpret_cast<const f4 *>(arow + kk + 4 * p);
+                bq[p] = *reinterpret_cast<const f4 *>(brow + kk + 4 * p);
+            }
+#pragma unroll
+            for (int u = 0; u < 16; ++u)
+                acc = __builtin_fma((double)aq[u >> 2][u & 3], (double)bq[u >> 2][u & 3], acc);
+        }
+        for (; kk < kn; ++kk) acc = __builtin_fma((double)arow[kk], (double)brow[kk], acc);
+    }
+    if (is_log) lgs[ls][lc] = (float)(acc + bl[lc]);
+    if (is_xn) xnl[ls] = __builtin_sqrt(acc);
+    if (is_wn) wnl[lc] = __builtin_sqrt(acc);
+    __syncthreads();
+    if (tid >= 64) return;  // wave 0: lane s takes sample s (no barrier below)
+    bool ok = false, nt = false;
+    if (tid < ns) {
+        // np.argmax: the first maximum, a NaN wins at its first place
+        const float *lg = lgs[tid];
+        int best = 0;
+        float b0 = lg[0];
+        for (int c = 1; c < C; ++c) {
+            const float v = lg[c];
+            if (!(b0 != b0) && (v != v || v > b0)) {
+                best = c;
+                b0 = v;
+            }
+        }
+        ok = best == yv[srow[tid]];
+        nt = softmax_near_tie(lg, C, best, xnl[tid], wnl, bl, gam);
+    }
+    const unsigned int mine[2] = {(unsigned int)__popcll(__ballot(ok)),
+                                  (unsigned int)__popcll(__ballot(nt))};
+    if (tid != 0) return;
+    const int slot[2] = {RBR_GOOD + e * RONI_ROUND_G + q, RBR_NEAR + e * RONI_ROUND_G + q};
+    if (!round_exit(mine, slot, cnt, RBR_EXIT)) return;
+    const double dn = (double)nb;
+    for (int p = 0; p < g; ++p) {  // k_roni_batch's expression
+        const double orig = 1.0 - (double)round_load(cnt + RBR_GOOD + p) / dn;
+        const double after = 1.0 - (double)round_load(cnt + RBR_GOOD + RONI_ROUND_G + p) / dn;
+        scores[p] = after - orig;
+        if (near_out) {
+            near_out[2 * p] = (int32_t)round_load(cnt + RBR_NEAR + p);
+            near_out[2 * p + 1] = (int32_t)round_load(cnt + RBR_NEAR + RONI_ROUND_G + p);
+        }
+    }
+}
+
+// idx_dev: the group's 2 g nb staged indices, or null: idx_arg carries them
+hipError_t launch_roni_softmax_round_batch(const float *Xv, int64_t nv, int64_t din, int64_t ldv,
+                                           const int32_t *yv, int C, const double *ww,
+                                           const RoundRows &rows, int g, const int32_t *idx_dev,
+                                           const RoundIdx &idx_arg, int64_t nb, unsigned int *cnt,
+                                           double *scores, int32_t *near, hipStream_t st) {
+    const int64_t tiles = (nb + RBR_ST - 1) / RBR_ST, nwg = 2 * (int64_t)g * tiles;
+    if (g < 1 || g > RONI_ROUND_G || nb < 1 || nwg > 0x7fffffff) return hipErrorInvalidConfiguration;
+    if (C < 2 || C > 16) return hipErrorInvalidConfiguration;
+    const dim3 grid((unsigned)nwg), blk((unsigned)rbr_threads(C));
+    const double gam = roni_softmax_g(din);
+    if (idx_dev)
+        hipLaunchKernelGGL(k_roni_round_batch<const int32_t *>, grid, blk, 0, st, Xv, nv, din, ldv,
+                           yv, C, ww, rows, g, idx_dev, nb, (int)tiles, gam, cnt, scores, near);
+    else
+        hipLaunchKernelGGL(k_roni_round_batch<RoundIdx>, grid, blk, 0, st, Xv, nv, din, ldv, yv, C,
+                           ww, rows, g, idx_arg, nb, (int)tiles, gam, cnt, scores, near);
     return hipGetLastError();
 }
 

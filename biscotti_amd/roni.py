@@ -142,11 +142,20 @@ class SoftmaxRONIValidator(RONIValidator):
     the (n, 2, nb) sample indices it scored (None for whole-set scores): the
     reference's scores are random draws (client.py:136-144), so a decision is
     reproduced by passing last_idx back as idx, or by a fixed seed.  A
-    validator built with seed=None draws from fresh OS entropy each run."""
+    validator built with seed=None draws from fresh OS entropy each run.
+
+    Rounds: with batch_size=None, begin_round / score_round /
+    verify_update(round=True) score over the whole set.  round_batches=True
+    (opt-in) gives a mini-batch validator rounds too: the model is held once
+    per iteration and each update is scored on its own two freshly drawn last
+    batches (bk_roni_softmax_round_score_batches), bitwise what scores() of a
+    same-seed validator returns."""
 
     def __init__(self, Xvalid, yvalid, n_classes, engine: Optional[Engine] = None,
-                 priv_prob: float = 0.0, batch_size: Optional[int] = 10, seed=None):
+                 priv_prob: float = 0.0, batch_size: Optional[int] = 10, seed=None,
+                 round_batches: bool = False):
         self._engine = engine if engine is not None else default_engine(0)
+        self.round_batches = bool(round_batches)
         X = np.ascontiguousarray(Xvalid, dtype=np.float32)
         y = np.ascontiguousarray(yvalid, dtype=np.int32)
         if X.ndim != 2 or y.shape != (X.shape[0],):
@@ -175,16 +184,48 @@ class SoftmaxRONIValidator(RONIValidator):
         self.last_near_ties = nt
         self.last_idx = None
 
+    def _mini_batch_rounds(self) -> bool:
+        return self.round_batches and self.batch_size is not None
+
     def begin_round(self, ww):
-        if self.batch_size is not None:
+        if self.batch_size is not None and not self.round_batches:
             raise ValueError("rounds score over the whole set: build the validator with "
-                             "batch_size=None (each update's `original` is drawn on its own "
-                             "random mini-batch, so nothing is shared)")
+                             "batch_size=None, or with round_batches=True for rounds that "
+                             "score each update on its own two last mini-batches")
         super().begin_round(ww)
 
+    def score_round(self, deltas, idx=None) -> np.ndarray:
+        """Whole-set rounds: RONIValidator.score_round.  With round_batches=True
+        and a mini-batch batch_size: each update's two last batches are drawn as
+        scores() draws them (original, then after; or taken from idx, (n, 2,
+        nb)), and scored against the held model
+        (bk_roni_softmax_round_score_batches): bitwise scores(ww, deltas, idx)."""
+        if not self._mini_batch_rounds():
+            if idx is not None:
+                raise ValueError("idx needs round_batches=True and a mini-batch batch_size")
+            return super().score_round(deltas)
+        if self._round_ww is None:
+            raise ValueError("no round: call begin_round(ww) first")
+        rows = [np.ascontiguousarray(r, dtype=np.float64) for r in deltas]
+        n = len(rows)
+        if not rows or any(r.shape != (self.d,) for r in rows):
+            raise ValueError("deltas must be a non-empty sequence of (d,) rows with d = %d" % self.d)
+        idx = self.draw_batches(n) if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        if idx.ndim != 3 or idx.shape[:2] != (n, 2) or idx.shape[2] < 1:
+            raise ValueError("idx must be (n, 2, nb)")
+        out = np.empty(n, dtype=np.float64)
+        nt = np.empty((n, 2), dtype=np.int32)
+        table = (ctypes.c_void_p * n)(*[r.ctypes.data for r in rows])
+        check(lib().bk_roni_softmax_round_score_batches(self._engine.ctx, table, n, BK_HOST,
+                                                        idx.ctypes.data, idx.shape[2],
+                                                        out.ctypes.data, nt.ctypes.data))
+        self.last_idx = idx
+        self.last_near_ties = nt
+        return out
+
     def verify_update(self, update: Update, latest_gradient, round: bool = False) -> bool:
-        if round and self.batch_size is not None:
-            raise ValueError("round=True needs batch_size=None")
+        if round and self.batch_size is not None and not self.round_batches:
+            raise ValueError("round=True needs batch_size=None or round_batches=True")
         return super().verify_update(update, latest_gradient, round)
 
     def last_batch(self) -> np.ndarray:

@@ -852,6 +852,33 @@ int bk_roni_round_score(bk_ctx *ctx, const double *const *deltas, int64_t count,
 int bk_roni_softmax_round_begin(bk_ctx *ctx, const double *ww, int where);
 int bk_roni_softmax_round_score(bk_ctx *ctx, const double *const *deltas, int64_t count, int where,
                                 double *scores, int32_t *near_ties);
+/* The softmax round in the form the reference scores (r16): client_obj.roni
+ * measures `original` and `after` on the shuffled loader's LAST mini-batch each
+ * (bk_roni_softmax_batches' semantics; 10 samples in Biscotti), so the deployed
+ * mnist verifier's call is this one.
+ *   *_round_score_batches  scores against the round begun by
+ *                  bk_roni_softmax_round_begin; one live round serves this entry
+ *                  and bk_roni_softmax_round_score, in any order.  Rows as for
+ *                  *_round_score.  idx is a HOST array in
+ *                  bk_roni_softmax_batches' layout, count x 2 x nb: update j
+ *                  scores `original` on idx[(2 j) nb ..] and `after` on
+ *                  idx[(2 j + 1) nb ..]; any nb >= 1.  Writes scores[j] and
+ *                  near_ties (nullable, 2 count: update j's original, after).
+ *                  Synchronous.  Every score and near-tie count is bitwise what
+ *                  one bk_roni_softmax_batches call on the same ww, rows and idx
+ *                  returns.  Only the rows go up (the held model is not uploaded
+ *                  or prepared again); groups of up to BK_RONI_ROUND_G updates
+ *                  share one launch of 2 ceil(nb / 16) workgroups per update.
+ * Checked in this order, before any copy, launch or state change (a refused
+ * call leaves the round as it was): BK_EINVAL for a null ctx, deltas, idx or
+ * scores, count < 1, nb < 1 or a bad where; BK_EINVAL for no validation set or
+ * no live round; BK_ENOTSUP for a count beyond bk_roni_softmax's n; BK_EINVAL
+ * for a null row (named); BK_EINVAL for an index outside [0, nv) (the update,
+ * the evaluation and the position named).  Added without a change of
+ * BK_ABI_VERSION (14). */
+int bk_roni_softmax_round_score_batches(bk_ctx *ctx, const double *const *deltas, int64_t count,
+                                        int where, const int64_t *idx, int64_t nb, double *scores,
+                                        int32_t *near_ties);
 
 /* ---- measurement: per-kernel HIP-event timing on the context stream ------- */
 enum bk_kernel_id {
