@@ -27,6 +27,10 @@
 // (bk_collect_noise.hip) adds the mean of the noise vectors to the arriving
 // rows in the store, one launch per group of up to BORDER_ROWS, before the
 // same border.
+// bk_collect_add_finish is the add of one row and the finish in one call; in
+// k_collect_small's range with at most 128 rows collected it is the row's copy
+// and ONE launch, k_collect_arrive (bk_collect_arrive.hip): that row's border,
+// bit for bit k_border + k_border_reduce's, in front of k_collect_small's items.
 // Every element of G is the same sum whatever the add's count and however many
 // rows are resident: chunk s covers the same columns, one wave sums a chunk's
 // products in lane order and the chunks are added in the same tree, so the
@@ -47,8 +51,15 @@ namespace {
 constexpr int BORDER_ROWS = 8;            // new rows per k_border launch (their chunks in LDS)
 constexpr int BORDER_CHUNK_BYTES = 8192;  // of one row per workgroup: 64 lanes x 8 loads x 16 B
 constexpr int BORDER_VPL = BORDER_CHUNK_BYTES / 16 / 64;  // 16-B loads per lane per row
+static_assert(BORDER_CHUNK_BYTES == COLLECT_BORDER_CHUNK_BYTES,
+              "k_collect_arrive's B items sum the chunks k_border does");
 constexpr size_t RING_SLOT_BYTES = (size_t)1 << 20;
 constexpr int RING_SLOTS = 8;
+// bk_collect_add_finish: a pageable row longer than this takes the add and the
+// finish inside the call, not the fused launch -- at 62,800 B (100 x 7,850) the
+// fused call measured no faster than the sequence from pageable memory, at
+// 200 B it did; nothing was measured in between
+constexpr size_t ARRIVE_HOST_MAX_BYTES = 32768;
 
 typedef double cd2 __attribute__((ext_vector_type(2)));
 typedef float cf4 __attribute__((ext_vector_type(4)));
@@ -238,6 +249,9 @@ struct Collect {
     int dtype = BK_F64;
     int64_t n_cap = 0, d = 0, ld = 0, count = 0;
     int S = 0;  // chunks of a row: ceil(d es / BORDER_CHUNK_BYTES)
+    // bk_collect_stats, since the begin: k_border launches, k_border_reduce
+    // launches, one-launch finishes, fused arrive launches
+    int64_t stats[4] = {0, 0, 0, 0};
     Buf store, G, P, U, sel, slots, scores, mean, mean_part, order, horder, ring;
     // bk_collect_finish_batch and bk_collect_finish_ragged: buffers of their
     // own (a single finish or any bk_multikrum* between two such finishes
@@ -339,6 +353,7 @@ int fold_border(Collect *k, int64_t j0, int64_t cnt, int num_cu, hipStream_t st)
                            : launch_border_t((const float *)k->store.p, k->ld, k->d, (int)g0, gc,
                                              k->S, rpb, RB, (double *)k->P.p, st);
         if (e != hipSuccess) return fail(BK_EHIP, "k_border launch: %s", hipGetErrorString(e));
+        ++k->stats[0];
         const int64_t items = (int64_t)gc * jend;
         hipLaunchKernelGGL(k_border_reduce, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st,
                            (const double *)k->P.p, k->S, border_c(gc), (int)g0, jend,
@@ -346,13 +361,18 @@ int fold_border(Collect *k, int64_t j0, int64_t cnt, int num_cu, hipStream_t st)
         e = hipGetLastError();
         if (e != hipSuccess)
             return fail(BK_EHIP, "k_border_reduce launch: %s", hipGetErrorString(e));
+        ++k->stats[1];
     }
     return BK_OK;
 }
 
 // one pageable row through the pinned ring: the host copy of a piece overlaps
-// the DMA of the one before; on return the row is in the ring or on the device
-int upload_pageable(Collect *k, char *dst, const char *src, size_t bytes, hipStream_t st) {
+// the DMA of the one before; on return the row is in the ring or on the device.
+// record = false (bk_collect_add_finish's fused path, which waits for the
+// stream before it returns or fails): no event behind the copy, the slot is
+// free again once that wait is over
+int upload_pageable(Collect *k, char *dst, const char *src, size_t bytes, hipStream_t st,
+                    bool record = true) {
     for (size_t off = 0; off < bytes; off += RING_SLOT_BYTES) {
         const size_t len = bytes - off < RING_SLOT_BYTES ? bytes - off : RING_SLOT_BYTES;
         const int s = k->ring_next;
@@ -361,8 +381,8 @@ int upload_pageable(Collect *k, char *dst, const char *src, size_t bytes, hipStr
         char *slot = (char *)k->ring.p + (size_t)s * RING_SLOT_BYTES;
         memcpy(slot, src + off, len);
         HIPCHK(hipMemcpyAsync(dst + off, slot, len, hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(k->ev_slot[s], st));
-        k->slot_used[s] = true;
+        if (record) HIPCHK(hipEventRecord(k->ev_slot[s], st));
+        k->slot_used[s] = record;
     }
     return BK_OK;
 }
@@ -399,10 +419,14 @@ int check_order(const int64_t *order, int64_t n, int64_t count, std::vector<int6
 // the row store through the order in its own arguments and writes {margin,
 // sel, scores, mean} into the context's mapped output block, so nothing is
 // uploaded before it and nothing copied after it -- one launch, one wait, then
-// host memcpys.  The arguments are validated by the caller.
-int finish_one_launch(bk_ctx *c, Collect *k, decltype(&launch_collect_small) launch,
-                      const int64_t *order, int64_t n, int64_t f, int64_t *sel_idx, int64_t *m_out,
-                      double *scores, double *mean_out) {
+// host memcpys.  bk_collect_add_finish's fused launch (k_collect_arrive) goes
+// the same way behind the new row's copy.  `launch` takes launch_collect_small's
+// arguments; stat: the launch's counter in bk_collect_stats.  The arguments are
+// validated by the caller.
+template <typename L>
+int finish_one_launch(bk_ctx *c, Collect *k, L launch, int stat, const int64_t *order, int64_t n,
+                      int64_t f, int64_t *sel_idx, int64_t *m_out, double *scores,
+                      double *mean_out) {
     static_assert(BK_MAX_N <= 65536, "arrival slots travel as 16-bit kernel arguments");
     const int64_t m = n - f, d = k->d;
     constexpr size_t MPAD = HOUT_MPAD;
@@ -418,6 +442,7 @@ int finish_one_launch(bk_ctx *c, Collect *k, decltype(&launch_collect_small) lau
                       scores ? blk + MPAD + n : nullptr, (unsigned *)c->small_ctr.p, c->num_cu,
                       c->stream, spin, c->small_check_lines);
     }));
+    ++k->stats[stat];
     c->margin_valid = 1;
     c->margin_host = c->hout_host_margin;
     c->margin_unchecked = 1;
@@ -492,6 +517,44 @@ int add_rows(bk_ctx *c, Collect *k, const void *const *rows, int64_t count, int 
     drain.armed = false;
     k->count = j0 + count;
     if (first_slot) *first_slot = j0;
+    return BK_OK;
+}
+
+// bk_collect_add_finish's fused path past its checks (the context mutex held,
+// the device selected; count + 1 <= 128 and the finish small_ok): the row goes
+// to slot `count` as add_rows copies it, then ONE launch -- k_collect_arrive,
+// the border of that slot in front of k_collect_small's items -- and the one
+// wait of finish_one_launch, behind which the row has been consumed.  The
+// collection counts the row only when all of it succeeded: after a failure the
+// next add rewrites the slot and its Gram run
+int add_finish_fused(bk_ctx *c, Collect *k, const void *row, int where, const int64_t *order,
+                     int64_t n, int64_t f, int64_t *first_slot, int64_t *sel_idx, int64_t *m_out,
+                     double *scores, double *mean_out) {
+    const hipStream_t st = c->stream;
+    Drain drain{st};
+    const size_t es = esize(k->dtype), bytes = (size_t)k->d * es;
+    const int64_t j = k->count;
+    char *dst = (char *)k->store.p + (size_t)j * (size_t)k->ld * es;
+    // (a row of the fused range is one ring slot: d <= 32,768; the stream is
+    // waited for below, or drained on a failure, before any later add)
+    if (where == BK_HOST)
+        CHK(upload_pageable(k, dst, (const char *)row, bytes, st, false));
+    else
+        HIPCHK(hipMemcpyAsync(dst, row, bytes,
+                              where == BK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                              st));
+    const auto launch = [j](const void *store, int dtype, int64_t ld, int n_, int64_t d, int f_,
+                            const double *G, const int64_t *ord, double *sc, double *diag,
+                            int64_t *sel, double *mean, double *margin, double *sc_out,
+                            unsigned *ctr, int num_cu, hipStream_t s, uint64_t spin, int lines) {
+        return launch_collect_arrive(store, dtype, ld, (int)j, n_, d, f_, const_cast<double *>(G),
+                                     ord, sc, diag, sel, mean, margin, sc_out, ctr, num_cu, s, spin,
+                                     lines);
+    };
+    CHK(finish_one_launch(c, k, launch, 3, order, n, f, sel_idx, m_out, scores, mean_out));
+    drain.armed = false;
+    k->count = j + 1;
+    if (first_slot) *first_slot = j;
     return BK_OK;
 }
 
@@ -665,6 +728,7 @@ int bk_collect_begin(bk_ctx *c, int dtype, int64_t n_cap, int64_t d) {
     k->ld = ld;
     k->S = S;
     k->count = 0;
+    for (int64_t &v : k->stats) v = 0;
     return BK_OK;
 }
 
@@ -777,6 +841,55 @@ int bk_collect_finish(bk_ctx *c, const int64_t *order, int64_t n, int64_t f, int
     return finish_checked(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
 }
 
+int bk_collect_add_finish(bk_ctx *c, const void *row, int where, const int64_t *order, int64_t n,
+                          int64_t f, int64_t *first_slot, int64_t *sel_idx, int64_t *m_out,
+                          double *scores, double *mean_out) {
+    // bk_collect_add's checks, then bk_collect_finish's on count + 1 rows
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!row) return fail(BK_EINVAL, "null row 0");
+    if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
+        return fail(BK_EINVAL, "bad where %d", where);
+    if (!sel_idx) return fail(BK_EINVAL, "null sel_idx");
+    std::lock_guard<std::mutex> lk(c->mu);
+    Collect *k = c->collect;
+    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_add without bk_collect_begin");
+    if (1 > k->n_cap - k->count)
+        return fail(BK_EINVAL, "bk_collect_add: %lld rows past n_cap=%lld (%lld collected)", 1LL,
+                    (long long)k->n_cap, (long long)k->count);
+    const int64_t after = k->count + 1;
+    if (n < 1 || n > after)
+        return fail(BK_EINVAL, "bk_collect_finish: n=%lld, %lld rows collected", (long long)n,
+                    (long long)after);
+    if (!order && n != after)
+        return fail(BK_EINVAL, "bk_collect_finish: a null order needs n = %lld, the rows "
+                               "collected (n=%lld)",
+                    (long long)after, (long long)n);
+    CHK(bk_check_args(n, k->d, f));
+    if (order) {
+        std::vector<int64_t> seen((size_t)after, 0);
+        CHK(check_order(order, n, after, seen, -1));
+    }
+    DeviceGuard dg(c->device);
+    // the fused launch: the finish in k_collect_small's range, a border of at
+    // most 128 rows and no long pageable row; everything else is the two
+    // entries' own paths
+    const bool long_host = where == BK_HOST && (size_t)k->d * esize(k->dtype) > ARRIVE_HOST_MAX_BYTES;
+    if (after <= 128 && !long_host && small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
+        return add_finish_fused(c, k, row, where, order, n, f, first_slot, sel_idx, m_out, scores,
+                                mean_out);
+    CHK(add_rows(c, k, &row, 1, where, first_slot));
+    return finish_checked(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
+}
+
+int bk_collect_stats(bk_ctx *c, int64_t out[4]) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!out) return fail(BK_EINVAL, "null out");
+    std::lock_guard<std::mutex> lk(c->mu);
+    const Collect *k = c->collect;
+    for (int i = 0; i < 4; ++i) out[i] = k && k->begun ? k->stats[i] : 0;
+    return BK_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -785,10 +898,10 @@ namespace {
 int finish_checked(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
                    int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
     if (small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
-        return finish_one_launch(c, k, launch_collect_small, order, n, f, sel_idx, m_out, scores,
+        return finish_one_launch(c, k, launch_collect_small, 2, order, n, f, sel_idx, m_out, scores,
                                  mean_out);
     if (wide_ok(c, n, k->d, mean_out != nullptr))
-        return finish_one_launch(c, k, launch_collect_wide, order, n, f, sel_idx, m_out, scores,
+        return finish_one_launch(c, k, launch_collect_wide, 2, order, n, f, sel_idx, m_out, scores,
                                  mean_out);
     const hipStream_t st = c->stream;
     Drain drain{st};

@@ -377,6 +377,18 @@ hipError_t launch_collect_small(const void *store, int dtype, int64_t ld, int n,
                                 double *diag, int64_t *sel, double *mean, double *margin,
                                 double *scores_out, unsigned *ctr, int num_cu, hipStream_t st,
                                 uint64_t spin_max = SMALL_SPIN_MAX, int check_lines = 0);
+// bk_collect_arrive.hip, k_collect_arrive (bk_collect_add_finish): the border
+// of the one new row at arrival slot j <= 127 (already copied into the row
+// store; its Gram run is written into G) and k_collect_small's finish behind
+// it, in one launch; d <= 32,768 (small_ok).  Every Gram element is the bits
+// of k_border + k_border_reduce (bk_collect.hip), whose chunk this is; the
+// other arguments are launch_collect_small's
+constexpr int COLLECT_BORDER_CHUNK_BYTES = 8192;
+hipError_t launch_collect_arrive(const void *store, int dtype, int64_t ld, int j, int n, int64_t d,
+                                 int f, double *G, const int64_t *order, double *scores,
+                                 double *diag, int64_t *sel, double *mean, double *margin,
+                                 double *scores_out, unsigned *ctr, int num_cu, hipStream_t st,
+                                 uint64_t spin_max = SMALL_SPIN_MAX, int check_lines = 0);
 // bk_small_batch.hip, k_small_batch / k_tiny_batch: W problems of one shape in one launch (problem
 // b's rows at X + b * stride elements).  Per problem: part_stride doubles of
 // partials, n scores, n diag, m = n - f sel, d mean (nullable), MARGIN_WORDS of

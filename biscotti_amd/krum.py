@@ -328,6 +328,64 @@ class Engine:
         assert mo.value == m
         return sel, sc, mean
 
+    def collect_add_finish(self, row, order=None, n=None, f=None, want_scores=True,
+                           want_mean=True, where=_lib.BK_HOST):
+        """The last arrival and the verdict in one call (bk_collect_add_finish):
+        collect_add(row) followed by collect_finish(order, n, f), bitwise, in
+        one launch at the deployed shapes.  order may name the new slot (the
+        count before the call); None: every row, the new one included.  where:
+        BK_HOST_PINNED when row is a view of pinned memory (a pageable row of
+        more than 32 KiB takes the two calls inside the entry: no faster fused).
+        Returns (slot, sel, scores, mean)."""
+        if getattr(self, "_collect", None) is None:
+            raise ValueError("collect_add_finish without collect_begin")
+        dt, d = self._collect
+        a = np.asarray(row)
+        if a.dtype != dt or a.ndim != 1 or a.shape[0] != d:
+            raise ValueError("the row must be a 1-D %s array of length %d" % (dt, d))
+        if not a.flags.c_contiguous:
+            a = np.ascontiguousarray(a)
+        if f is None:
+            raise ValueError("f is required")
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.int64)
+            if n is None:
+                n = len(order)
+            if order.ndim != 1 or len(order) < n:
+                raise ValueError("order must list n arrival slots")
+        elif n is None:
+            n = self.collect_count() + 1
+        n, f = int(n), int(f)
+        check(lib().bk_check_args(n, d, f))
+        m = n - f
+        sel = np.empty(m, dtype=np.int64)
+        sc = np.empty(n, dtype=np.float64) if want_scores else None
+        mean = np.empty(d, dtype=np.float64) if want_mean else None
+        slot, mo = self.collect_add_finish_ptr(
+            a.ctypes.data, where, order.ctypes.data if order is not None else None, n, f,
+            sel.ctypes.data, sc.ctypes.data if sc is not None else None,
+            mean.ctypes.data if mean is not None else None)
+        assert mo == m
+        return slot, sel, sc, mean
+
+    def collect_add_finish_ptr(self, row_ptr, where, order_ptr, n, f, sel_ptr, scores_ptr=None,
+                               mean_ptr=None):
+        """Raw pointers: the row pageable, pinned or device; order (nullable) and
+        the outputs host.  Returns (slot, m)."""
+        first, mo = ctypes.c_int64(-1), ctypes.c_int64(0)
+        check(lib().bk_collect_add_finish(self._ctx, _p(row_ptr), int(where), _p(order_ptr),
+                                          int(n), int(f), ctypes.byref(first), _p(sel_ptr),
+                                          ctypes.addressof(mo), _p(scores_ptr), _p(mean_ptr)))
+        return first.value, mo.value
+
+    def collect_stats(self):
+        """The collection's launches since collect_begin (bk_collect_stats): which
+        path the adds and finishes took."""
+        out = (ctypes.c_int64 * 4)()
+        check(lib().bk_collect_stats(self._ctx, out))
+        return {"border": out[0], "border_reduce": out[1], "one_launch_finishes": out[2],
+                "fused_arrivals": out[3]}
+
     def collect_finish_batch(self, orders, f, want_scores=True, want_mean=True):
         """B finishes over the one collection in one call (bk_collect_finish_batch):
         orders is a (B, n) integer array, row b the arrival slots of problem
@@ -911,9 +969,32 @@ class KRUMValidator:
         # global is never set, main.go:843 declares a local)
         return any(self.UpdateList[i].SourceID == peer_id for i in self.AcceptedList)
 
-    def add_update(self, update):
+    def add_update(self, update, last=False):
         """VerifyUpdateKRUM's append (krum.go:291).  In collect mode the update's
-        NoisedDelta is uploaded and folded into the Gram now."""
+        NoisedDelta is uploaded and folded into the Gram now.  last=True is the
+        threshold-th arrival (krum.go:291-314): the append, the sort by SourceID
+        and Krum in one engine call (bk_collect_add_finish), AcceptedList set on
+        return; outside plain collect mode it is add_update, then
+        compute_scores."""
+        if last and self._collect and not self._noised and self._slots:
+            row = np.ascontiguousarray(update.NoisedDelta, dtype=np.float64)
+            ups = self.UpdateList + [update]
+            slots = self._slots + [len(self._slots)]  # the new slot: the rows collected so far
+            by_id = sorted(range(len(ups)), key=lambda i: ups[i].SourceID)
+            order = [slots[i] for i in by_id]
+            n = len(ups)
+            clip = int(self.NumAdversaries * float(n))
+            slot, sel, _, _ = self._engine.collect_add_finish(row, order=order, n=n, f=clip,
+                                                              want_scores=False, want_mean=False)
+            assert slot == slots[-1]
+            self.UpdateList = [ups[i] for i in by_id]
+            self._slots = order
+            self.AcceptedList = [int(i) for i in sel]
+            return
+        if last:
+            self.add_update(update)
+            self.compute_scores()
+            return
         if self._collect:
             if self._engine is None:
                 self.initialize()

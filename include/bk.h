@@ -229,6 +229,48 @@ int bk_collect_count(bk_ctx *ctx, int64_t *count);
  * BK_COLLECT_WIDE_MAX_D, with the same bits. */
 int bk_collect_finish(bk_ctx *ctx, const int64_t *order, int64_t n, int64_t f,
                       int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out);
+/* The threshold-th update arrives and Krum runs in the same critical section
+ * (krum.go:291-314): exactly bk_collect_add(ctx, &row, 1, where, first_slot)
+ * followed by bk_collect_finish(ctx, order, n, f, ...), in one call.  row points
+ * at d elements (where as bk_collect_add's) and takes the next arrival slot, the
+ * collection's count before the call; order may name that slot, may leave it
+ * out, and may be NULL (all count + 1 slots in arrival order, n = count + 1).
+ * Outputs, nullable arguments and the margin record (bk_selection_margin*) are
+ * the finish's; synchronous, the row consumed on return.  The collection is not
+ * consumed: the row is in the store and its Gram run written, so any later add
+ * or finish (batched and ragged ones included) sees the bits the two calls
+ * would have left.
+ * Every output -- sel, scores, mean and the margin record -- is BITWISE the
+ * two-call sequence's on the same collection under the same context settings.
+ * With the small path on, a finish of n <= 128, d <= 32,768 and at most 128
+ * rows collected after the add, the row's copy is followed by ONE launch:
+ * k_collect_arrive, the border of the new row (every Gram element the bits of
+ * bk_collect_add's) in front of the one-launch finish's work items, timed under
+ * BK_K_SMALL; then one wait.  Everything else (bk_set_small_path(ctx, 0), n >
+ * 128, more than 128 rows collected, d > 32,768 with or without
+ * bk_set_collect_wide, and a BK_HOST row of more than 32 KiB, where the fused
+ * call measured no faster) runs the add and then the finish inside the call.
+ * The checks, in this order, all before any copy, launch or state change (a
+ * refused call leaves the collection as it was), with the messages of the two
+ * entries: BK_EINVAL for a null ctx, a null row, a bad where, a null sel_idx;
+ * a call without bk_collect_begin; an add past n_cap; then the finish's on
+ * count + 1 collected rows: n outside 1..count + 1; a null order with n !=
+ * count + 1; f outside bk_check_args (n = 1 included: a first-ever arrival
+ * cannot finish); an out-of-range or repeated slot in order.  If the launch's
+ * hand-off time-out (BK_EHIP) or a HIP error hits after the copy was queued, the
+ * row does not count: the next add rewrites the slot and its Gram run.
+ * Added without a change of BK_ABI_VERSION (14), as bk_collect_add_noised was. */
+int bk_collect_add_finish(bk_ctx *ctx, const void *row, int where,
+                          const int64_t *order, int64_t n, int64_t f,
+                          int64_t *first_slot /* nullable */,
+                          int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out);
+/* The launches of this collection since the last bk_collect_begin: out[0]
+ * k_border, out[1] k_border_reduce (one each per group of up to 8 added rows),
+ * out[2] one-launch finishes (bk_collect_finish's k_collect_small or
+ * k_collect_wide), out[3] fused arrive launches (bk_collect_add_finish's
+ * k_collect_arrive).  All 0 before any begin.  No kernel id of its own: the path
+ * a call took, for tests and benches.  BK_EINVAL: a null ctx or out. */
+int bk_collect_stats(bk_ctx *ctx, int64_t out[4]);
 
 /* Device-resident, asynchronous on the context stream.  All pointers are
  * device pointers; d_sel_idx gets m = n-f ascending indices; d_scores (n) and
