@@ -31,6 +31,10 @@
 // k_collect_small's range with at most 128 rows collected it is the row's copy
 // and ONE launch, k_collect_arrive (bk_collect_arrive.hip): that row's border,
 // bit for bit k_border + k_border_reduce's, in front of k_collect_small's items.
+// bk_collect_add_noised_finish is that for an update that arrives as Delta and
+// Noise: the copies and ONE launch, k_collect_arrive_noised
+// (bk_collect_arrive_noised.hip), which noises the new row in front of the
+// border.
 // Every element of G is the same sum whatever the add's count and however many
 // rows are resident: chunk s covers the same columns, one wave sums a chunk's
 // products in lane order and the chunks are added in the same tree, so the
@@ -60,6 +64,14 @@ constexpr int RING_SLOTS = 8;
 // fused call measured no faster than the sequence from pageable memory, at
 // 200 B it did; nothing was measured in between
 constexpr size_t ARRIVE_HOST_MAX_BYTES = 32768;
+// bk_collect_add_noised_finish: host rows longer than this take the noised add
+// and the finish inside the call, not the fused launch, but for pinned rows with
+// k = 1.  At 62,800 B (100 x 7,850) the fused call's runs were all below the
+// sequence's only there and from pageable memory with k = 2; pinned k = 2 and
+// pageable k = 1 overlapped by one run each.  At 200 B every setting was ahead
+// (DESIGN 5o); nothing was measured in between.  Device rows are fused at
+// every d of the range
+constexpr size_t ARRIVE_NOISED_HOST_MAX_BYTES = 32768;
 
 typedef double cd2 __attribute__((ext_vector_type(2)));
 typedef float cf4 __attribute__((ext_vector_type(4)));
@@ -656,6 +668,106 @@ int add_noised(bk_ctx *c, Collect *k, const double *const *deltas, const double 
     return BK_OK;
 }
 
+// bk_collect_finish's checks on the count + 1 rows a fused arrival leaves
+// (bk_collect_add_finish, bk_collect_add_noised_finish; the context mutex held)
+int check_finish_after(const Collect *k, const int64_t *order, int64_t n, int64_t f) {
+    const int64_t after = k->count + 1;
+    if (n < 1 || n > after)
+        return fail(BK_EINVAL, "bk_collect_finish: n=%lld, %lld rows collected", (long long)n,
+                    (long long)after);
+    if (!order && n != after)
+        return fail(BK_EINVAL, "bk_collect_finish: a null order needs n = %lld, the rows "
+                               "collected (n=%lld)",
+                    (long long)after, (long long)n);
+    CHK(bk_check_args(n, k->d, f));
+    if (order) {
+        std::vector<int64_t> seen((size_t)after, 0);
+        CHK(check_order(order, n, after, seen, -1));
+    }
+    return BK_OK;
+}
+
+// bk_collect_add_finish past its checks (the context mutex held, the device
+// selected)
+int add_finish_checked(bk_ctx *c, Collect *k, const void *row, int where, const int64_t *order,
+                       int64_t n, int64_t f, int64_t *first_slot, int64_t *sel_idx, int64_t *m_out,
+                       double *scores, double *mean_out) {
+    // the fused launch: the finish in k_collect_small's range, a border of at
+    // most 128 rows and no long pageable row; everything else is the two
+    // entries' own paths
+    const bool long_host = where == BK_HOST && (size_t)k->d * esize(k->dtype) > ARRIVE_HOST_MAX_BYTES;
+    if (k->count + 1 <= 128 && !long_host && small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
+        return add_finish_fused(c, k, row, where, order, n, f, first_slot, sel_idx, m_out, scores,
+                                mean_out);
+    CHK(add_rows(c, k, &row, 1, where, first_slot));
+    return finish_checked(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
+}
+
+// bk_collect_add_noised_finish's fused path past its checks, k >= 1 (fp64
+// collection, the context mutex held, the device selected; count + 1 <= 128 and
+// the finish small_ok).  Host rows: the delta goes to slot `count` as add_rows
+// copies it and the k noise vectors to the staging block; device rows are read
+// where they are and nothing is copied.  Then ONE launch -- k_collect_arrive_noised:
+// the noise of that slot, its border and k_collect_small's items -- and the one
+// wait of finish_one_launch, behind which every input has been consumed.  The
+// k vectors' pointers travel in the launch arguments: no table upload.  The
+// collection counts the row only when all of it succeeded (add_finish_fused)
+int add_noised_finish_fused(bk_ctx *c, Collect *k, const double *delta,
+                            const double *const *noises, int64_t kn, int where,
+                            const int64_t *order, int64_t n, int64_t f, int64_t *first_slot,
+                            int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
+    static_assert(BK_COLLECT_NOISE_MAX_K == COLLECT_ARRIVE_NOISE_MAX_K, "the launch's vector table");
+    const hipStream_t st = c->stream;
+    const int64_t j = k->count, d = k->d;
+    const size_t bytes = (size_t)d * sizeof(double);
+    const int64_t sld = (d + 1) & ~(int64_t)1;
+    const bool dev = where == BK_DEVICE;
+    if (!dev) {
+        const size_t need = (size_t)kn * (size_t)sld * sizeof(double);
+        // (a launch of an earlier add may still read the block about to be replaced)
+        if (need > k->nstage.bytes) HIPCHK(hipStreamSynchronize(st));
+        CHK(grow_all({{&k->nstage, need}}, "bk_collect_add_noised"));
+    }
+    Drain drain{st};
+    double *rowj = (double *)k->store.p + j * k->ld;
+    const double *vecs[BK_COLLECT_NOISE_MAX_K];
+    // (a row of the fused range is one ring slot: d <= 32,768.  The stream is
+    // waited for below, or drained on a failure, before any later add; up to
+    // RING_SLOTS copies need no event behind them, more of them reuse a slot
+    // within the call and take upload_pageable's events)
+    const bool record = 1 + kn > RING_SLOTS;
+    if (dev) {
+        for (int64_t q = 0; q < kn; ++q) vecs[q] = noises[q];
+    } else {
+        if (where == BK_HOST)
+            CHK(upload_pageable(k, (char *)rowj, (const char *)delta, bytes, st, record));
+        else
+            HIPCHK(hipMemcpyAsync(rowj, delta, bytes, hipMemcpyHostToDevice, st));
+        for (int64_t q = 0; q < kn; ++q) {
+            double *dst = (double *)k->nstage.p + q * sld;
+            if (where == BK_HOST)
+                CHK(upload_pageable(k, (char *)dst, (const char *)noises[q], bytes, st, record));
+            else
+                HIPCHK(hipMemcpyAsync(dst, noises[q], bytes, hipMemcpyHostToDevice, st));
+            vecs[q] = dst;
+        }
+    }
+    const double *dsrc = dev ? delta : rowj;
+    const auto launch = [&](const void *store, int, int64_t ld, int n_, int64_t d_, int f_,
+                            const double *G, const int64_t *ord, double *sc, double *diag,
+                            int64_t *sel, double *mean, double *margin, double *sc_out,
+                            unsigned *ctr, int num_cu, hipStream_t s, uint64_t spin, int lines) {
+        return launch_collect_arrive_noised(store, ld, (int)j, dsrc, vecs, (int)kn, n_, d_, f_,
+                                            const_cast<double *>(G), ord, sc, diag, sel, mean,
+                                            margin, sc_out, ctr, num_cu, s, spin, lines);
+    };
+    CHK(finish_one_launch(c, k, launch, 3, order, n, f, sel_idx, m_out, scores, mean_out));
+    drain.armed = false;
+    k->count = j + 1;
+    if (first_slot) *first_slot = j;
+    return BK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -856,28 +968,54 @@ int bk_collect_add_finish(bk_ctx *c, const void *row, int where, const int64_t *
     if (1 > k->n_cap - k->count)
         return fail(BK_EINVAL, "bk_collect_add: %lld rows past n_cap=%lld (%lld collected)", 1LL,
                     (long long)k->n_cap, (long long)k->count);
-    const int64_t after = k->count + 1;
-    if (n < 1 || n > after)
-        return fail(BK_EINVAL, "bk_collect_finish: n=%lld, %lld rows collected", (long long)n,
-                    (long long)after);
-    if (!order && n != after)
-        return fail(BK_EINVAL, "bk_collect_finish: a null order needs n = %lld, the rows "
-                               "collected (n=%lld)",
-                    (long long)after, (long long)n);
-    CHK(bk_check_args(n, k->d, f));
-    if (order) {
-        std::vector<int64_t> seen((size_t)after, 0);
-        CHK(check_order(order, n, after, seen, -1));
-    }
+    CHK(check_finish_after(k, order, n, f));
     DeviceGuard dg(c->device);
+    return add_finish_checked(c, k, row, where, order, n, f, first_slot, sel_idx, m_out, scores,
+                              mean_out);
+}
+
+int bk_collect_add_noised_finish(bk_ctx *c, const double *delta, const double *const *noises,
+                                 int64_t kn, int where, const int64_t *order, int64_t n, int64_t f,
+                                 int64_t *first_slot, int64_t *sel_idx, int64_t *m_out,
+                                 double *scores, double *mean_out) {
+    // bk_collect_add_noised's checks on one update, then bk_collect_finish's on
+    // count + 1 rows, as bk_collect_add_finish does them
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!delta) return fail(BK_EINVAL, "null delta 0");
+    if (kn < 0) return fail(BK_EINVAL, "need k >= 0 (k=%lld)", (long long)kn);
+    if (!noises && kn > 0) return fail(BK_EINVAL, "null noises with k=%lld", (long long)kn);
+    if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
+        return fail(BK_EINVAL, "bad where %d", where);
+    if (kn > BK_COLLECT_NOISE_MAX_K)
+        return fail(BK_ENOTSUP, "k=%lld exceeds BK_COLLECT_NOISE_MAX_K=%d", (long long)kn,
+                    BK_COLLECT_NOISE_MAX_K);
+    if (!sel_idx) return fail(BK_EINVAL, "null sel_idx");
+    std::lock_guard<std::mutex> lk(c->mu);
+    Collect *k = c->collect;
+    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_add_noised without bk_collect_begin");
+    if (k->dtype != BK_F64)
+        return fail(BK_EINVAL, "bk_collect_add_noised: the collection is BK_F32 (noise is fp64 only)");
+    if (1 > k->n_cap - k->count)
+        return fail(BK_EINVAL, "bk_collect_add_noised: %lld rows past n_cap=%lld (%lld collected)",
+                    1LL, (long long)k->n_cap, (long long)k->count);
+    for (int64_t j = 0; j < kn; ++j)
+        if (!noises[j]) return fail(BK_EINVAL, "null noise vector (%lld, %lld)", 0LL, (long long)j);
+    CHK(check_finish_after(k, order, n, f));
+    DeviceGuard dg(c->device);
+    // no noisers: the row is the delta, bk_collect_add_finish's path and bits
+    if (kn == 0)
+        return add_finish_checked(c, k, delta, where, order, n, f, first_slot, sel_idx, m_out,
+                                  scores, mean_out);
     // the fused launch: the finish in k_collect_small's range, a border of at
-    // most 128 rows and no long pageable row; everything else is the two
+    // most 128 rows, and of the long host rows only pinned ones with one noise
+    // vector (ARRIVE_NOISED_HOST_MAX_BYTES); everything else is the two
     // entries' own paths
-    const bool long_host = where == BK_HOST && (size_t)k->d * esize(k->dtype) > ARRIVE_HOST_MAX_BYTES;
-    if (after <= 128 && !long_host && small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
-        return add_finish_fused(c, k, row, where, order, n, f, first_slot, sel_idx, m_out, scores,
-                                mean_out);
-    CHK(add_rows(c, k, &row, 1, where, first_slot));
+    const bool long_host = where != BK_DEVICE && !(where == BK_HOST_PINNED && kn == 1) &&
+                           (size_t)k->d * sizeof(double) > ARRIVE_NOISED_HOST_MAX_BYTES;
+    if (k->count + 1 <= 128 && !long_host && small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
+        return add_noised_finish_fused(c, k, delta, noises, kn, where, order, n, f, first_slot,
+                                       sel_idx, m_out, scores, mean_out);
+    CHK(add_noised(c, k, &delta, noises, kn, 1, where, first_slot));
     return finish_checked(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
 }
 

@@ -389,6 +389,20 @@ hipError_t launch_collect_arrive(const void *store, int dtype, int64_t ld, int j
                                  double *diag, int64_t *sel, double *mean, double *margin,
                                  double *scores_out, unsigned *ctr, int num_cu, hipStream_t st,
                                  uint64_t spin_max = SMALL_SPIN_MAX, int check_lines = 0);
+// bk_collect_arrive_noised.hip, k_collect_arrive_noised
+// (bk_collect_add_noised_finish): launch_collect_arrive on an fp64 store with
+// the new row noised inside the launch first -- row j = delta + (0 + vecs[0] +
+// .. + vecs[k-1]) / k, k_collect_noise's bits.  delta: row j itself (uploaded
+// there) or a device row of d doubles, 8-B aligned; vecs: k host-side pointers
+// to device vectors of d doubles, 8-B aligned (they travel in the arguments)
+constexpr int COLLECT_ARRIVE_NOISE_MAX_K = 64;
+hipError_t launch_collect_arrive_noised(const void *store, int64_t ld, int j, const double *delta,
+                                        const double *const *vecs, int k, int n, int64_t d, int f,
+                                        double *G, const int64_t *order, double *scores,
+                                        double *diag, int64_t *sel, double *mean, double *margin,
+                                        double *scores_out, unsigned *ctr, int num_cu,
+                                        hipStream_t st, uint64_t spin_max = SMALL_SPIN_MAX,
+                                        int check_lines = 0);
 // bk_small_batch.hip, k_small_batch / k_tiny_batch: W problems of one shape in one launch (problem
 // b's rows at X + b * stride elements).  Per problem: part_stride doubles of
 // partials, n scores, n diag, m = n - f sel, d mean (nullable), MARGIN_WORDS of

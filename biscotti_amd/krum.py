@@ -378,6 +378,70 @@ class Engine:
                                           ctypes.addressof(mo), _p(scores_ptr), _p(mean_ptr)))
         return first.value, mo.value
 
+    def collect_add_noised_finish(self, delta, noise=None, order=None, n=None, f=None,
+                                  want_scores=True, want_mean=True, where=_lib.BK_HOST):
+        """The last arrival as Delta and Noise and the verdict in one call
+        (bk_collect_add_noised_finish): collect_add_noised(delta, noise)
+        followed by collect_finish(order, n, f), bitwise, in one launch at the
+        deployed shapes.  delta and noise as collect_add_noised takes them
+        (noise None: k = 0, collect_add_finish on delta); order as
+        collect_add_finish's; where: BK_HOST_PINNED when delta and noise are
+        views of pinned memory.  Returns (slot, sel, scores, mean)."""
+        if getattr(self, "_collect", None) is None:
+            raise ValueError("collect_add_noised_finish without collect_begin")
+        dt, d = self._collect
+        if dt != np.float64:
+            raise ValueError("noise is float64 only: the collection is %s" % dt)
+        D = np.ascontiguousarray(delta, dtype=np.float64)
+        if D.ndim != 1 or D.shape[0] != d:
+            raise ValueError("delta must be a 1-D float64 array of length %d" % d)
+        if noise is None:
+            N = np.empty((0, d), dtype=np.float64)
+        else:
+            N = np.ascontiguousarray(noise, dtype=np.float64)
+            if N.ndim == 1:
+                N = N.reshape(1, -1)
+            if N.ndim != 2 or (N.shape[0] > 0 and N.shape[1] != d):
+                raise ValueError("noise must be None, a vector of length %d or a (k, %d) array"
+                                 % (d, d))
+        if f is None:
+            raise ValueError("f is required")
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.int64)
+            if n is None:
+                n = len(order)
+            if order.ndim != 1 or len(order) < n:
+                raise ValueError("order must list n arrival slots")
+        elif n is None:
+            n = self.collect_count() + 1
+        n, f = int(n), int(f)
+        check(lib().bk_check_args(n, d, f))
+        m = n - f
+        k = N.shape[0]
+        nz = (ctypes.c_void_p * k)(*[N[j].ctypes.data for j in range(k)]) if k else None
+        sel = np.empty(m, dtype=np.int64)
+        sc = np.empty(n, dtype=np.float64) if want_scores else None
+        mean = np.empty(d, dtype=np.float64) if want_mean else None
+        slot, mo = self.collect_add_noised_finish_ptr(
+            D.ctypes.data, nz, k, where, order.ctypes.data if order is not None else None, n, f,
+            sel.ctypes.data, sc.ctypes.data if sc is not None else None,
+            mean.ctypes.data if mean is not None else None)
+        assert mo == m
+        return slot, sel, sc, mean
+
+    def collect_add_noised_finish_ptr(self, delta_ptr, noise_ptrs, k, where, order_ptr, n, f,
+                                      sel_ptr, scores_ptr=None, mean_ptr=None):
+        """Raw pointers: the delta and the k noise vectors (a ctypes c_void_p
+        array; None when k = 0) pageable, pinned or device; order (nullable) and
+        the outputs host.  Returns (slot, m)."""
+        first, mo = ctypes.c_int64(-1), ctypes.c_int64(0)
+        check(lib().bk_collect_add_noised_finish(self._ctx, _p(delta_ptr), noise_ptrs, int(k),
+                                                 int(where), _p(order_ptr), int(n), int(f),
+                                                 ctypes.byref(first), _p(sel_ptr),
+                                                 ctypes.addressof(mo), _p(scores_ptr),
+                                                 _p(mean_ptr)))
+        return first.value, mo.value
+
     def collect_stats(self):
         """The collection's launches since collect_begin (bk_collect_stats): which
         path the adds and finishes took."""
@@ -973,19 +1037,25 @@ class KRUMValidator:
         """VerifyUpdateKRUM's append (krum.go:291).  In collect mode the update's
         NoisedDelta is uploaded and folded into the Gram now.  last=True is the
         threshold-th arrival (krum.go:291-314): the append, the sort by SourceID
-        and Krum in one engine call (bk_collect_add_finish), AcceptedList set on
-        return; outside plain collect mode it is add_update, then
-        compute_scores."""
-        if last and self._collect and not self._noised and self._slots:
-            row = np.ascontiguousarray(update.NoisedDelta, dtype=np.float64)
+        and Krum in one engine call (bk_collect_add_finish; noised mode:
+        bk_collect_add_noised_finish on Delta and Noise), AcceptedList set on
+        return; outside collect mode it is add_update, then compute_scores."""
+        if last and self._collect and self._slots:
+            row = np.ascontiguousarray(update.Delta if self._noised else update.NoisedDelta,
+                                       dtype=np.float64)
             ups = self.UpdateList + [update]
             slots = self._slots + [len(self._slots)]  # the new slot: the rows collected so far
             by_id = sorted(range(len(ups)), key=lambda i: ups[i].SourceID)
             order = [slots[i] for i in by_id]
             n = len(ups)
             clip = int(self.NumAdversaries * float(n))
-            slot, sel, _, _ = self._engine.collect_add_finish(row, order=order, n=n, f=clip,
-                                                              want_scores=False, want_mean=False)
+            if self._noised:
+                slot, sel, _, _ = self._engine.collect_add_noised_finish(
+                    row, update.Noise, order=order, n=n, f=clip, want_scores=False,
+                    want_mean=False)
+            else:
+                slot, sel, _, _ = self._engine.collect_add_finish(
+                    row, order=order, n=n, f=clip, want_scores=False, want_mean=False)
             assert slot == slots[-1]
             self.UpdateList = [ups[i] for i in by_id]
             self._slots = order

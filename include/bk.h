@@ -264,11 +264,52 @@ int bk_collect_add_finish(bk_ctx *ctx, const void *row, int where,
                           const int64_t *order, int64_t n, int64_t f,
                           int64_t *first_slot /* nullable */,
                           int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out);
+/* The threshold-th update arrives as Delta and Noise: exactly
+ * bk_collect_add_noised(ctx, &delta, noises, k, 1, where, first_slot) followed
+ * by bk_collect_finish(ctx, order, n, f, ...), in one call.  delta points at d
+ * doubles, noises[j] (j < k <= BK_COLLECT_NOISE_MAX_K) at noise vector j (d
+ * doubles; noises may be NULL only when k == 0); where applies to all of them,
+ * as bk_collect_add_noised's (BK_DEVICE rows 8-byte aligned, not necessarily
+ * 16).  The row stored in the new slot is, per element and in this order (fp64,
+ * no contraction), delta[c] + ((0 + v_0[c]) + ... + v_{k-1}[c]) / (double)k.
+ * Every output -- sel, scores, mean, the margin record -- and everything a later
+ * add, finish, batched or ragged finish or bk_collect_read_rows sees is BITWISE
+ * the two-call sequence's on the same collection under the same settings.
+ * Synchronous: every input is consumed on return, no pointer is retained, and
+ * the collection is not consumed.  k == 0 is bk_collect_add_finish on delta,
+ * path and bits.
+ * With k >= 1, the small path on, an fp64 collection, a finish of n <= 128, d <=
+ * 32,768 and at most 128 rows collected after the add, the copies (host rows:
+ * the delta into its store row, the k vectors into the collection's staging
+ * block; device rows: none, the kernel reads them where they are) are followed
+ * by ONE launch and one wait: k_collect_arrive_noised -- the noise of the new
+ * row, its border and the one-launch finish's work items -- timed under
+ * BK_K_SMALL and counted in bk_collect_stats' out[3].  The k pointers travel in
+ * the launch arguments (no table upload).  Everything else runs the two calls
+ * inside the entry, and so do host rows of more than 32 KiB other than
+ * BK_HOST_PINNED rows with k == 1: there a fused run measured no faster than
+ * the sequence's fastest.
+ * The checks, in this order, all before any copy, launch or state change (a
+ * refused call leaves the collection as it was), with the messages of the two
+ * entries: BK_EINVAL for a null ctx, a null delta, k < 0, null noises with k >
+ * 0, a bad where; BK_ENOTSUP for k > BK_COLLECT_NOISE_MAX_K; BK_EINVAL for a
+ * null sel_idx; then for a call without bk_collect_begin, a BK_F32 collection,
+ * an add past n_cap, a null noises[j]; then the finish's on count + 1 collected
+ * rows, as bk_collect_add_finish's.  If the launch's hand-off time-out (BK_EHIP)
+ * or a HIP error hits after the copies were queued, the row does not count.
+ * Added without a change of BK_ABI_VERSION (14), as bk_collect_add_finish was. */
+int bk_collect_add_noised_finish(bk_ctx *ctx, const double *delta,
+                                 const double *const *noises, int64_t k, int where,
+                                 const int64_t *order, int64_t n, int64_t f,
+                                 int64_t *first_slot /* nullable */,
+                                 int64_t *sel_idx, int64_t *m_out,
+                                 double *scores, double *mean_out);
 /* The launches of this collection since the last bk_collect_begin: out[0]
  * k_border, out[1] k_border_reduce (one each per group of up to 8 added rows),
  * out[2] one-launch finishes (bk_collect_finish's k_collect_small or
  * k_collect_wide), out[3] fused arrive launches (bk_collect_add_finish's
- * k_collect_arrive).  All 0 before any begin.  No kernel id of its own: the path
+ * k_collect_arrive, bk_collect_add_noised_finish's k_collect_arrive_noised).
+ * All 0 before any begin.  No kernel id of its own: the path
  * a call took, for tests and benches.  BK_EINVAL: a null ctx or out. */
 int bk_collect_stats(bk_ctx *ctx, int64_t out[4]);
 
