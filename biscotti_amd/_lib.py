@@ -116,6 +116,8 @@ SIGNATURES = {
     "bk_collect_add_noised_finish": (_i, [_p, _p, _p, _i64, _i, _p, _i64, _i64, _pi64, _p, _p, _p,
                                           _p]),
     "bk_collect_stats": (_i, [_p, _pi64]),
+    "bk_set_collect_tiny": (_i, [_p, _i]),
+    "bk_collect_tiny_stats": (_i, [_p, _pi64]),
     "bk_multikrum_batch_device": (_i, [_p, _p, _i, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p,
                                        _p]),
     "bk_multikrum_batch": (_i, [_p, _p, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p,

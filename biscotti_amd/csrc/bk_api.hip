@@ -537,6 +537,13 @@ int bk_set_collect_wide(bk_ctx *c, int on) {
     return BK_OK;
 }
 
+int bk_set_collect_tiny(bk_ctx *c, int on) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->collect_tiny = on ? 1 : 0;
+    return BK_OK;
+}
+
 int bk_synth_fill_device(bk_ctx *c, void *dX, int dtype, int64_t n, int64_t dl, int64_t ld,
                          int64_t c0, int64_t d_total, uint64_t seed, int64_t nbyz, double mu_scale,
                          double byz_scale, double sigma, int flags) {

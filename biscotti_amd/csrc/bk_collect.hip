@@ -35,6 +35,12 @@
 // Noise: the copies and ONE launch, k_collect_arrive_noised
 // (bk_collect_arrive_noised.hip), which noises the new row in front of the
 // border.
+// With bk_set_collect_tiny on, a collection of at most 16 rows with d <= 128
+// runs every add, finish and fused arrival as ONE launch of one workgroup,
+// k_collect_tiny (bk_collect_tiny.hip), with no copy call: host rows reach the
+// kernel through the collection's mapped pinned arrival block, device rows are
+// read where they are.  The store rows and the Gram runs are left as the paths
+// above leave them, so the two mix freely.
 // Every element of G is the same sum whatever the add's count and however many
 // rows are resident: chunk s covers the same columns, one wave sums a chunk's
 // products in lane order and the chunks are added in the same tree, so the
@@ -282,6 +288,15 @@ struct Collect {
     bool slot_used[RING_SLOTS] = {};
     int ring_next = 0;
     hipEvent_t ev_up = nullptr;
+    // bk_set_collect_tiny: the launches of k_collect_tiny since the begin (adds,
+    // finishes, adds with a finish) and the arrival block -- mapped pinned host
+    // memory the kernel reads over PCIe, TINY_SLOTS slots indexed by arrival
+    // slot, each a row and BK_COLLECT_NOISE_MAX_K noise vectors of
+    // COLLECT_TINY_SLOT_BYTES.  A slot is written once per collected row, before
+    // the launch that reads it; it is written again only after a failed call
+    // (which drains the stream) or the next begin (which waits for it)
+    int64_t tiny_stats[3] = {0, 0, 0};
+    char *arrive = nullptr, *arrive_dev = nullptr;
 };
 
 // the batched finish's buffers (the stream is idle)
@@ -300,6 +315,7 @@ void collect_destroy(Collect *k) {
                    &k->mean_part, &k->order, &k->horder, &k->ring, &k->nstage, &k->ntab, &k->hntab})
         if (b->p) (void)(b->pinned ? hipHostFree(b->p) : hipFree(b->p));
     collect_batch_release(k);
+    if (k->arrive) (void)hipHostFree(k->arrive);
     for (hipEvent_t ev : k->ev_slot)
         if (ev) (void)hipEventDestroy(ev);
     if (k->ev_up) (void)hipEventDestroy(k->ev_up);
@@ -503,11 +519,150 @@ size_t noise_stage_bytes() {
     return v > 0 && (size_t)v < dflt ? (size_t)v : dflt;
 }
 
+// ---- bk_set_collect_tiny: the one-workgroup collection (bk_collect_tiny.hip)
+
+// The fused arrivals of the tiny range whose rows are longer than this take
+// today's fused launches (k_collect_arrive, k_collect_arrive_noised) instead:
+// bk_collect_add_finish from any source, and bk_collect_add_noised_finish from
+// device rows.  At 16 x 128 fp64 (1 KiB rows) the three runs of the tiny call
+// were not all below today's there (31.3 [27.3 .. 32.6] against 33.6 [30.1 ..
+// 33.8] us plain; device rows 30.0 [25.3 .. 30.4] against 32.9 [30.1 .. 33.1] us
+// with k = 1), at 200 B (10 x 25, 4 x 25) they were; nothing was measured in
+// between.  Adds, finishes and the noised arrivals from host rows
+// were ahead at every shape measured and stay
+constexpr size_t TINY_ARRIVE_MAX_BYTES = 512;
+bool tiny_arrive_ok(const Collect *k, bool cut) {
+    return !cut || (size_t)k->d * esize(k->dtype) <= TINY_ARRIVE_MAX_BYTES;
+}
+
+constexpr size_t TINY_SLOT_STRIDE = (size_t)(1 + BK_COLLECT_NOISE_MAX_K) * COLLECT_TINY_SLOT_BYTES;
+
+// The tiny range: the switch and the small path on, d <= 128 and at most 16
+// rows collected after the call (a finish names collected slots only, so its n
+// is in the range with them)
+bool tiny_ok(const bk_ctx *c, const Collect *k, int64_t after) {
+    return c->collect_tiny && after <= COLLECT_TINY_MAX_N && k->d <= COLLECT_TINY_MAX_D &&
+           small_ok(c, k->store.p, k->dtype, after, k->d, k->ld);
+}
+
+// the arrival block, allocated whole at the first tiny call of the context's
+// collection and kept: uncached on the device's side, so every load of a slot
+// crosses PCIe and sees what the CPU wrote before the launch
+int tiny_block(Collect *k) {
+    if (k->arrive) return BK_OK;
+    void *hp = nullptr, *dp = nullptr;
+    const size_t bytes = (size_t)COLLECT_TINY_MAX_N * TINY_SLOT_STRIDE;
+    hipError_t e = hipHostMalloc(&hp, bytes,
+                                 hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess)
+        return fail(BK_ENOMEM, "bk_collect: hipHostMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+    e = hipHostGetDevicePointer(&dp, hp, 0);
+    if (e != hipSuccess) {
+        (void)hipHostFree(hp);
+        return fail(BK_EHIP, "bk_collect: hipHostGetDevicePointer: %s", hipGetErrorString(e));
+    }
+    k->arrive = (char *)hp;
+    k->arrive_dev = (char *)dp;
+    return BK_OK;
+}
+
+struct TinyFinish {
+    const int64_t *order;
+    int64_t n, f;
+    int64_t *sel_idx, *m_out;
+    double *scores, *mean_out;
+};
+
+// One call of the tiny range past its checks (the context mutex held, the
+// device selected): cnt >= 0 rows arrive (kn > 0: as deltas with kn noise
+// vectors each) and, with fz, the finish follows in the same launch.  Host rows
+// are memcpy'd into their arrival slots, device rows are named in the launch
+// arguments; no copy call anywhere.  A plain add is one launch for all its
+// rows, a noised add one launch per row (the k pointers of one row fill the
+// arguments), the finish rides on the last.  An add without a finish returns
+// behind the launch -- host rows were consumed by the memcpy; device rows are
+// waited for, as add_rows waits for their copies.  The rows count only when
+// every launch was queued and, with a finish, completed (add_finish_fused's rule)
+int tiny_call(bk_ctx *c, Collect *k, const void *const *rows, int64_t cnt,
+              const double *const *noises, int64_t kn, int where, const TinyFinish *fz,
+              int64_t *first_slot) {
+    const hipStream_t st = c->stream;
+    CHK(tiny_block(k));
+    Drain drain{st};
+    const size_t bytes = (size_t)k->d * esize(k->dtype);
+    const int64_t j0 = k->count;
+    const bool dev = where == BK_DEVICE;
+    const int64_t per = kn > 0 || cnt == 0 ? 1 : cnt;  // rows per launch
+    for (int64_t r0 = 0; r0 < (cnt > 0 ? cnt : 1); r0 += per) {
+        const int64_t nr = cnt > 0 ? per : 0;
+        const bool last = r0 + per >= cnt;
+        CollectTinyLaunch L;
+        L.store = k->store.p;
+        L.dtype = k->dtype;
+        L.ld = k->ld;
+        L.d = k->d;
+        L.G = (double *)k->G.p;
+        L.j0 = (int)(j0 + r0);
+        L.cnt = (int)nr;
+        const double *vecs[BK_COLLECT_NOISE_MAX_K];
+        for (int64_t r = 0; r < nr; ++r) {
+            const size_t at = (size_t)(j0 + r0 + r) * TINY_SLOT_STRIDE;
+            if (dev) {
+                L.src[r] = rows[r0 + r];
+            } else {
+                memcpy(k->arrive + at, rows[r0 + r], bytes);
+                L.src[r] = k->arrive_dev + at;
+            }
+            for (int64_t q = 0; q < kn; ++q) {  // (kn > 0: nr = 1)
+                const size_t vat = at + (size_t)(1 + q) * COLLECT_TINY_SLOT_BYTES;
+                if (dev) {
+                    vecs[q] = noises[(r0 + r) * kn + q];
+                } else {
+                    memcpy(k->arrive + vat, noises[(r0 + r) * kn + q], bytes);
+                    vecs[q] = (const double *)(k->arrive_dev + vat);
+                }
+            }
+        }
+        L.vecs = vecs;
+        L.k = (int)kn;
+        if (fz && last) {
+            const auto launch = [&](const void *, int, int64_t, int n_, int64_t, int f_, const double *,
+                                    const int64_t *ord, double *, double *, int64_t *sel,
+                                    double *mean, double *margin, double *sc_out, unsigned *, int,
+                                    hipStream_t s, uint64_t, int) {
+                L.fin = 1;
+                L.n = n_;
+                L.f = f_;
+                L.order = ord;
+                L.sel = sel;
+                L.mean = mean;
+                L.margin = margin;
+                L.scores_out = sc_out;
+                return launch_collect_tiny(L, s);
+            };
+            CHK(finish_one_launch(c, k, launch, nr > 0 ? 3 : 2, fz->order, fz->n, fz->f, fz->sel_idx,
+                                  fz->m_out, fz->scores, fz->mean_out));
+            ++k->tiny_stats[nr > 0 ? 2 : 1];
+        } else {
+            CHK(timed(c, BK_K_SMALL, [&] { return launch_collect_tiny(L, st); }));
+            ++k->tiny_stats[0];
+        }
+    }
+    // device rows are read by the kernel itself: consumed once it is done
+    if (dev && cnt > 0 && !fz) HIPCHK(hipStreamSynchronize(st));
+    drain.armed = false;
+    k->count = j0 + cnt;
+    if (first_slot && cnt > 0) *first_slot = j0;
+    return BK_OK;
+}
+
 // bk_collect_add past its checks (the context mutex held): the rows copied into
 // the slots from count on, then their border
 int add_rows(bk_ctx *c, Collect *k, const void *const *rows, int64_t count, int where,
              int64_t *first_slot) {
     DeviceGuard dg(c->device);
+    if (tiny_ok(c, k, k->count + count))
+        return tiny_call(c, k, rows, count, nullptr, 0, where, nullptr, first_slot);
     const hipStream_t st = c->stream;
     Drain drain{st};
     const size_t es = esize(k->dtype), bytes = (size_t)k->d * es;
@@ -583,6 +738,9 @@ int add_noised(bk_ctx *c, Collect *k, const double *const *deltas, const double 
                int64_t kn, int64_t count, int where, int64_t *first_slot) {
     static_assert(COLLECT_NOISE_ROWS == BORDER_ROWS, "one noise launch per border group");
     DeviceGuard dg(c->device);
+    if (tiny_ok(c, k, k->count + count))
+        return tiny_call(c, k, (const void *const *)deltas, count, noises, kn, where, nullptr,
+                         first_slot);
     const hipStream_t st = c->stream;
     const int64_t j0 = k->count, d = k->d;
     const size_t bytes = (size_t)d * sizeof(double);
@@ -692,6 +850,10 @@ int check_finish_after(const Collect *k, const int64_t *order, int64_t n, int64_
 int add_finish_checked(bk_ctx *c, Collect *k, const void *row, int where, const int64_t *order,
                        int64_t n, int64_t f, int64_t *first_slot, int64_t *sel_idx, int64_t *m_out,
                        double *scores, double *mean_out) {
+    if (tiny_ok(c, k, k->count + 1) && tiny_arrive_ok(k, true)) {
+        const TinyFinish fz = {order, n, f, sel_idx, m_out, scores, mean_out};
+        return tiny_call(c, k, &row, 1, nullptr, 0, where, &fz, first_slot);
+    }
     // the fused launch: the finish in k_collect_small's range, a border of at
     // most 128 rows and no long pageable row; everything else is the two
     // entries' own paths
@@ -841,6 +1003,7 @@ int bk_collect_begin(bk_ctx *c, int dtype, int64_t n_cap, int64_t d) {
     k->S = S;
     k->count = 0;
     for (int64_t &v : k->stats) v = 0;
+    for (int64_t &v : k->tiny_stats) v = 0;
     return BK_OK;
 }
 
@@ -1006,6 +1169,10 @@ int bk_collect_add_noised_finish(bk_ctx *c, const double *delta, const double *c
     if (kn == 0)
         return add_finish_checked(c, k, delta, where, order, n, f, first_slot, sel_idx, m_out,
                                   scores, mean_out);
+    if (tiny_ok(c, k, k->count + 1) && tiny_arrive_ok(k, where == BK_DEVICE)) {
+        const TinyFinish fz = {order, n, f, sel_idx, m_out, scores, mean_out};
+        return tiny_call(c, k, (const void *const *)&delta, 1, noises, kn, where, &fz, first_slot);
+    }
     // the fused launch: the finish in k_collect_small's range, a border of at
     // most 128 rows, and of the long host rows only pinned ones with one noise
     // vector (ARRIVE_NOISED_HOST_MAX_BYTES); everything else is the two
@@ -1028,6 +1195,15 @@ int bk_collect_stats(bk_ctx *c, int64_t out[4]) {
     return BK_OK;
 }
 
+int bk_collect_tiny_stats(bk_ctx *c, int64_t out[3]) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!out) return fail(BK_EINVAL, "null out");
+    std::lock_guard<std::mutex> lk(c->mu);
+    const Collect *k = c->collect;
+    for (int i = 0; i < 3; ++i) out[i] = k && k->begun ? k->tiny_stats[i] : 0;
+    return BK_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -1035,6 +1211,10 @@ namespace {
 // bk_collect_finish past its checks (the context mutex held, the device selected)
 int finish_checked(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
                    int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
+    if (tiny_ok(c, k, k->count)) {
+        const TinyFinish fz = {order, n, f, sel_idx, m_out, scores, mean_out};
+        return tiny_call(c, k, nullptr, 0, nullptr, 0, BK_HOST, &fz, nullptr);
+    }
     if (small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
         return finish_one_launch(c, k, launch_collect_small, 2, order, n, f, sel_idx, m_out, scores,
                                  mean_out);

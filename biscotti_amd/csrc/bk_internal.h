@@ -403,6 +403,33 @@ hipError_t launch_collect_arrive_noised(const void *store, int64_t ld, int j, co
                                         double *scores_out, unsigned *ctr, int num_cu,
                                         hipStream_t st, uint64_t spin_max = SMALL_SPIN_MAX,
                                         int check_lines = 0);
+// bk_collect_tiny.hip, k_collect_tiny (bk_set_collect_tiny): the arrival of cnt
+// rows at slots j0.., their border and, with fin, the finish of n rows through
+// order, in ONE workgroup; at most COLLECT_TINY_MAX_N rows after the launch, d
+// <= COLLECT_TINY_MAX_D.  src[r]: new row r where the device can read it (a row
+// of the collection's mapped arrival block, or a device row; d elements, aligned
+// to one element).  k > 0 (cnt = 1, fp64): src[0] is the delta and vecs the k
+// noise vectors, k_collect_noise's bits.  The store rows and the Gram runs are
+// left as bk_collect_add leaves them; sel, mean, margin and scores_out are the
+// finish's (launch_collect_small's: the mapped output block)
+constexpr int COLLECT_TINY_MAX_N = 16;
+constexpr int COLLECT_TINY_MAX_D = 128;
+constexpr int COLLECT_TINY_SLOT_BYTES = 1024;  // a row, or a noise vector, of the arrival block
+struct CollectTinyLaunch {
+    void *store = nullptr;
+    int dtype = 0;
+    int64_t ld = 0, d = 0;
+    double *G = nullptr;
+    int j0 = 0, cnt = 0;
+    const void *src[COLLECT_TINY_MAX_N] = {};
+    const double *const *vecs = nullptr;
+    int k = 0;
+    int fin = 0, n = 0, f = 0;
+    const int64_t *order = nullptr;
+    int64_t *sel = nullptr;
+    double *mean = nullptr, *margin = nullptr, *scores_out = nullptr;
+};
+hipError_t launch_collect_tiny(const CollectTinyLaunch &L, hipStream_t st);
 // bk_small_batch.hip, k_small_batch / k_tiny_batch: W problems of one shape in one launch (problem
 // b's rows at X + b * stride elements).  Per problem: part_stride doubles of
 // partials, n scores, n diag, m = n - f sel, d mean (nullable), MARGIN_WORDS of

@@ -450,6 +450,19 @@ class Engine:
         return {"border": out[0], "border_reduce": out[1], "one_launch_finishes": out[2],
                 "fused_arrivals": out[3]}
 
+    def set_collect_tiny(self, on=True):
+        """Opt in: a collection of at most 16 rows with d <= 128 runs every add,
+        finish and fused arrival as one launch of one workgroup with no copy call
+        (bk_set_collect_tiny); the outputs are bitwise the other paths'."""
+        check(lib().bk_set_collect_tiny(self._ctx, 1 if on else 0))
+
+    def collect_tiny_stats(self):
+        """The tiny path's launches since collect_begin (bk_collect_tiny_stats):
+        adds without a finish, finishes without an add, adds with a finish."""
+        out = (ctypes.c_int64 * 3)()
+        check(lib().bk_collect_tiny_stats(self._ctx, out))
+        return {"adds": out[0], "finishes": out[1], "arrivals": out[2]}
+
     def collect_finish_batch(self, orders, f, want_scores=True, want_mean=True):
         """B finishes over the one collection in one call (bk_collect_finish_batch):
         orders is a (B, n) integer array, row b the arrival slots of problem
@@ -998,7 +1011,7 @@ class KRUMValidator:
     """DistSys/krum.go:22-29, with getTopKRUMIndex running on libbk."""
 
     def __init__(self, num_adversaries=0.5, engine: Optional[Engine] = None, device=0,
-                 collect=False, n_cap=128, wide=False, noised=False):
+                 collect=False, n_cap=128, wide=False, noised=False, tiny=False):
         """collect=True (opt-in): add_update streams each update's NoisedDelta
         to the engine's collection as it arrives (bk_collect_add), and
         compute_scores only finishes (bk_collect_finish) in SourceID order;
@@ -1008,7 +1021,10 @@ class KRUMValidator:
         (with collect): add_update sends update.Delta and update.Noise through
         the noised add (bk_collect_add_noised; k = 1 when Noise is present, k =
         0 when it is absent, as the shim does), so NoisedDelta is never built on
-        the host; noised_delta(i) reads it back from the row store when asked."""
+        the host; noised_delta(i) reads it back from the row store when asked.
+        tiny=True (with collect, with or without noised) turns the engine's
+        one-workgroup tiny collection on when the round begins
+        (Engine.set_collect_tiny: creditcard's d, at most 16 updates)."""
         self.UpdateList: List[Update] = []
         self.AcceptedList: List[int] = []
         self.NumAdversaries = num_adversaries  # fixed at 0.5 (main.go:783)
@@ -1018,8 +1034,11 @@ class KRUMValidator:
         self._n_cap = int(n_cap)
         self._wide = bool(wide)
         self._noised = bool(noised)
+        self._tiny = bool(tiny)
         if self._noised and not self._collect:
             raise ValueError("noised=True needs collect=True")
+        if self._tiny and not self._collect:
+            raise ValueError("tiny=True needs collect=True")
         self._slots: List[int] = []  # collect mode: arrival slot of UpdateList[i]
 
     def initialize(self):
@@ -1073,6 +1092,8 @@ class KRUMValidator:
             if not self._slots:
                 if self._wide:
                     self._engine.set_collect_wide(True)
+                if self._tiny:
+                    self._engine.set_collect_tiny(True)
                 self._engine.collect_begin(self._n_cap, row.shape[0], np.float64)
             if self._noised:
                 self._slots.append(self._engine.collect_add_noised(row, update.Noise))

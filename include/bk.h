@@ -312,6 +312,47 @@ int bk_collect_add_noised_finish(bk_ctx *ctx, const double *delta,
  * All 0 before any begin.  No kernel id of its own: the path
  * a call took, for tests and benches.  BK_EINVAL: a null ctx or out. */
 int bk_collect_stats(bk_ctx *ctx, int64_t out[4]);
+/* The tiny collection (off by default): with it on, and the small path on
+ * (bk_set_small_path), every call of bk_collect_add (count <= 16),
+ * bk_collect_add_noised (k <= BK_COLLECT_NOISE_MAX_K), bk_collect_finish,
+ * bk_collect_add_finish and bk_collect_add_noised_finish on a collection with
+ * d <= 128 (either dtype; the noised forms fp64 only, as ever) that leaves at
+ * most 16 rows collected is ONE launch of ONE workgroup, k_collect_tiny, with no
+ * device copy call and no hand-off between workgroups: host rows (BK_HOST and
+ * BK_HOST_PINNED alike, any alignment) are memcpy'd by the CPU into a mapped
+ * pinned arrival block the collection owns -- 16 slots by arrival slot, each a
+ * row and up to 64 noise vectors of 1 KiB -- and read from there by the kernel
+ * over PCIe; BK_DEVICE rows (8-byte aligned) are read where they are through
+ * pointers in the launch arguments.  A plain add is one launch for all its rows,
+ * a noised add one launch per row.  n_cap may be larger than 16: what counts is
+ * the rows collected after the call, so a collection begun with
+ * KRUM_UPDATETHRESH and finished at the deadline qualifies.  Every other call --
+ * d > 128, the 17th arrival of the same collection, a batched or ragged finish
+ * -- takes the paths above, and the two mix freely: the kernel leaves the row
+ * store (pad columns untouched) and the packed Gram exactly as bk_collect_add
+ * leaves them.  Two fused arrivals are cut further: with rows of more than 512
+ * bytes, bk_collect_add_finish (any source) and bk_collect_add_noised_finish
+ * from BK_DEVICE rows take today's fused launches (k_collect_arrive,
+ * k_collect_arrive_noised) -- at 16 x 128 fp64 the tiny call's runs were not
+ * all below theirs, at 200-byte rows they were, nothing was measured between.
+ * Every output -- sel, scores, mean, the margin record, every stored row
+ * (bk_collect_read_rows) and whatever a later add, finish, batched or ragged
+ * finish gives -- is BITWISE what the same calls give with the switch off, and
+ * with bk_set_small_path(ctx, 0).  Checks, their order and their messages are
+ * the entries' own; a refused call leaves the collection and both stats as they
+ * were.  An add without a finish returns behind the launch with the rows
+ * consumed (device rows: once the kernel has read them); if a launch fails
+ * after a row was staged, the row does not count.  bk_collect_begin waits for
+ * outstanding launches before any slot can be written again.  The launches are
+ * timed under BK_K_SMALL; an add with a finish also counts in bk_collect_stats'
+ * out[3] and a finish in out[2], never in out[0] or out[1].
+ * bk_collect_tiny_stats: the k_collect_tiny launches since the last
+ * bk_collect_begin -- out[0] adds without a finish, out[1] finishes without an
+ * add, out[2] adds with a finish.  All 0 before any begin.
+ * BK_EINVAL: a null ctx (either entry), a null out; neither check needs a GPU.
+ * Added without a change of BK_ABI_VERSION (14), as bk_set_collect_wide was. */
+int bk_set_collect_tiny(bk_ctx *ctx, int on);
+int bk_collect_tiny_stats(bk_ctx *ctx, int64_t out[3]);
 
 /* Device-resident, asynchronous on the context stream.  All pointers are
  * device pointers; d_sel_idx gets m = n-f ascending indices; d_scores (n) and
