@@ -76,6 +76,12 @@ SIGNATURES = {
     "bk_aggregate_device": (_i, [_p, _p, _i, _i64, _i64, _i64, _p, _i64, _p]),
     "bk_aggregate": (_i, [_p, _p, _i, _i, _i64, _i64, _i64, _p, _i64, _p]),
     "bk_quantized_sum_device": (_i, [_p, _p, _i, _i64, _i64, _i64, _p, _i64, _i, _p, _p]),
+    "bk_block_begin": (_i, [_p, _i, _i64, _p, _i, _i]),
+    "bk_block_add": (_i, [_p, _p, _p, _i64, _i, _pi64]),
+    "bk_block_count": (_i, [_p, _pi64, _pi64]),
+    "bk_block_finish": (_i, [_p, _p, _p, _p]),
+    "bk_block_add_finish": (_i, [_p, _p, _i, _i, _pi64, _p, _p, _p]),
+    "bk_block_stats": (_i, [_p, _pi64]),
     "bk_noise_apply_device": (_i, [_p, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _i64]),
     "bk_multikrum_noised": (_i, [_p, _p, _i64, _p, _i64, _i64, _i, _i64, _i64, _i64, _p, _p,
                                  _p, _p, _p, _i64]),

@@ -25,7 +25,8 @@ import numpy as np
 from . import _lib
 from .krum import Engine, Update, default_engine
 
-__all__ = ["STAKE_UNIT", "PRECISION", "create_block", "quantized_sum", "apply_noise"]
+__all__ = ["STAKE_UNIT", "PRECISION", "create_block", "quantized_sum", "apply_noise",
+           "BlockCollector"]
 
 STAKE_UNIT = 5   # DistSys/honest.go:46
 PRECISION = 4    # DistSys/main.go:45
@@ -64,6 +65,86 @@ def create_block(global_w: np.ndarray, block_updates: Sequence[Update],
             X[i] = 0.0  # never read
     _engine(engine).aggregate(X, np.asarray(accepted, dtype=np.int64), out)
     return out
+
+
+class BlockCollector:
+    """The miner's side of a block, with every add done as its update arrives
+    (bk_block_*): addBlockUpdate (DistSys/honest.go:330-334) uploads Delta and
+    adds it to the running gradient at once, createBlock (honest.go:346-388)
+    reads the gradient back and does the stake bookkeeping.  The result equals
+    create_block(global_w, updates, stake_map) bitwise: the adds are the same
+    sequential fp64 adds in arrival order.
+
+    precision: None, or the PRECISION of the secure path, whose running int64
+    sum quantized_sum() returns.  One collector per engine at a time (the
+    engine's context holds one block)."""
+
+    def __init__(self, global_w, precision: Optional[int] = None,
+                 engine: Optional[Engine] = None, dtype=np.float64):
+        self._engine = _engine(engine)
+        self._g0 = np.array(global_w, dtype=np.float64, copy=True)
+        if self._g0.ndim != 1 or self._g0.shape[0] < 1:
+            raise ValueError("global_w must be a vector")
+        self._precision = precision
+        self._dtype = np.dtype(dtype)
+        self.flush()
+
+    def flush(self):
+        """Restart the block from the gradient it was made with."""
+        self._updates: List[Update] = []
+        self._result = None   # the fused last add's gradient, until another add
+        self._qsum = None
+        self._engine.block_begin(self._g0, self._precision, self._dtype)
+
+    def add_update(self, update: Update, last: bool = False) -> int:
+        """addBlockUpdate: append the update and add its Delta on the device if
+        it is accepted (a rejected update's Delta is never read).  last=True is
+        the NUM_SAMPLES / 2-th arrival: the add and the finish in one engine
+        call.  Returns the number of updates in the block."""
+        d = self._g0.shape[0]
+        row = None
+        if update.Accepted:
+            row = np.asarray(update.Delta, dtype=self._dtype)
+            if row.shape != (d,):
+                raise ValueError("update %d: Delta has %s entries, gradient has %d"
+                                 % (len(self._updates), row.shape, d))
+        elif last:
+            row = np.zeros(d, dtype=self._dtype)  # the entry wants a row; it is never read
+        want_q = self._precision is not None
+        if last:
+            out = self._engine.block_add_finish(row, bool(update.Accepted), want_qsum=want_q)
+            self._result = out[1]
+            self._qsum = (out[2], out[3]) if want_q else None
+        else:
+            self._engine.block_add([row], [1 if update.Accepted else 0])
+            self._result = self._qsum = None
+        self._updates.append(update)
+        return len(self._updates)
+
+    def _finish(self):
+        if self._result is None:
+            want_q = self._precision is not None
+            out = self._engine.block_finish(want_qsum=want_q)
+            self._result = out[0] if want_q else out
+            self._qsum = (out[1], out[2]) if want_q else None
+        return self._result
+
+    def create_block(self, stake_map: Dict[int, int]) -> np.ndarray:
+        """createBlock over the updates added so far (the deadline path may call
+        it with fewer than expected): the updated gradient, a new array, and the
+        +-STAKE_UNIT bookkeeping on stake_map.  The block is not consumed."""
+        for u in self._updates:
+            their = stake_map.get(u.SourceID, 0)
+            stake_map[u.SourceID] = their + (STAKE_UNIT if u.Accepted else -STAKE_UNIT)
+        return self._finish().copy()
+
+    def quantized_sum(self):
+        """(int64 sum, float64 sum) of the accepted updates so far, as
+        quantized_sum() over them gives."""
+        if self._precision is None:
+            raise ValueError("the collector was made without a precision")
+        self._finish()
+        return self._qsum[0].copy(), self._qsum[1].copy()
 
 
 def quantized_sum(deltas, idx, precision: int = PRECISION, engine: Optional[Engine] = None):

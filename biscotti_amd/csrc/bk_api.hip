@@ -193,6 +193,17 @@ int bk_create(bk_ctx **out, int device) {
     if (const char *v = getenv("BK_TEST_SPLIT_SCORES")) c->test_split_scores = atoi(v);
     if (const char *v = getenv("BK_EMU_SPLIT_SCORES")) c->emu_split_scores = atoi(v);
     if (const char *v = getenv("BK_TEST_SPLIT_FAIL")) c->test_split_fail = atoi(v);
+    // the block's path cuts in bytes (bk_ctx.h BLOCK_*_MAX; tools/block_bench.py
+    // and the tests of both sides of a cut), capped at what the arrival block holds
+    const auto cut = [](const char *name, int64_t &out, int64_t cap) {
+        if (const char *v = getenv(name)) {
+            const int64_t x = atoll(v);
+            out = x < 0 ? 0 : x > cap ? cap : x;
+        }
+    };
+    cut("BK_BLOCK_MAPPED_HOST", c->block_mapped_host, 4 << 20);
+    cut("BK_BLOCK_MAPPED_PINNED", c->block_mapped_pinned, 4 << 20);
+    cut("BK_BLOCK_FIN", c->block_fin_max, INT64_MAX);
     e = configure_kernels();
     if (e == hipSuccess) e = configure_aggregate_kernels();
     if (e == hipSuccess) e = configure_i8_kernels();
@@ -246,6 +257,7 @@ void bk_destroy(bk_ctx *c) {
         if (c->hsig) (void)hipHostFree(c->hsig);
         if (c->rstage) (void)hipHostFree(c->rstage);
         collect_destroy(c->collect);
+        block_destroy(c->block);
         delete c->hpool;
         if (c->copy) (void)hipStreamDestroy(c->copy);
         for (void *p : c->staged) (void)hipHostFree(p);

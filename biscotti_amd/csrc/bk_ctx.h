@@ -71,6 +71,68 @@ inline void free_pieces(Pieces &pc) {
     pc = Pieces();
 }
 
+// bk_block_*: the block of a context.  The running gradient
+// and the quantised sum are kept twice: a launch group reads g[cur] / q[cur]
+// and writes the other pair, and cur flips once the launch is queued, so a
+// launch that fails leaves the block as it was.  All buffers grow only.
+constexpr int BLOCK_RING_SLOTS = 4;
+constexpr size_t BLOCK_RING_SLOT_BYTES = (size_t)1 << 20;
+constexpr int BLOCK_ARRIVE_GROUPS = 8;
+// The measured cuts (profiles/r20/block_bench.json), in bytes of
+// one row / of the gradient; 0: the path is not taken.  Host rows up to
+// BLOCK_MAPPED_* are read by the kernel from the mapped arrival block instead
+// of being copied to the device; a gradient up to BLOCK_FIN_MAX is stored by
+// the kernel into mapped host memory instead of being copied back.  Measured at
+// d = 25 .. 262,144 fp64: the mapped rows won through d = 32,768 (21.5 us
+// against 34.2 .. 36.0 for add + wait) and lost at 262,144 (108 against 74 ..
+// 103); the mapped output won through d = 784 (14.0 against 23.8) and lost from
+// 7,850 on (16.4 against 13.2)
+constexpr int64_t BLOCK_MAPPED_HOST_MAX = 32768 * 8;
+constexpr int64_t BLOCK_MAPPED_PINNED_MAX = 32768 * 8;
+constexpr int64_t BLOCK_FIN_MAX = 784 * 8;
+struct Block {
+    bool begun = false;
+    int dtype = BK_F64;
+    int64_t d = 0;
+    int precision = -1;
+    double scale = 1.0;  // 10^precision
+    int64_t added = 0, accepted = 0;
+    // bk_block_stats, since the begin: add launches, fused add-finish launches,
+    // launches that read their rows from mapped host memory, finishes served
+    // without a D2H copy call
+    int64_t stats[4] = {0, 0, 0, 0};
+    double *g[2] = {nullptr, nullptr};
+    int64_t *q[2] = {nullptr, nullptr};
+    size_t g_elems = 0, q_elems = 0;
+    int cur = 0;
+    // host rows of one launch group on the device
+    char *stage = nullptr;
+    size_t stage_bytes = 0;
+    // pageable rows go up through this pinned ring, a slot's host copy under
+    // the DMA of the one before (the collection's upload_pageable)
+    char *ring = nullptr;
+    hipEvent_t ev_slot[BLOCK_RING_SLOTS] = {};
+    bool slot_used[BLOCK_RING_SLOTS] = {};
+    int ring_next = 0;
+    hipEvent_t ev_up = nullptr;  // behind a call's copies or launches: its rows are consumed
+    // the mapped pinned arrival block small host rows are memcpy'd into and the
+    // kernel reads over PCIe (no copy call), BLOCK_GROUP rows of arrive_row bytes
+    // A launch group takes the next of BLOCK_ARRIVE_GROUPS group slots and
+    // records the slot's event behind its launch; the group that comes round
+    // to the slot again waits for that event before the CPU writes
+    char *arrive = nullptr, *arrive_dev = nullptr;
+    size_t arrive_row = 0;
+    hipEvent_t ev_arrive[BLOCK_ARRIVE_GROUPS] = {};
+    bool arrive_used[BLOCK_ARRIVE_GROUPS] = {};
+    int arrive_next = 0;
+    // the mapped pinned output block a FIN launch stores into: d doubles of the
+    // gradient, then d int64 and d doubles of the quantised sum; out_valid: it
+    // holds the block's current state (no add since the launch that wrote it)
+    char *out = nullptr, *out_dev = nullptr;
+    size_t out_elems = 0;
+    bool out_valid = false;
+};
+
 }  // namespace bk
 
 // the C ABI's opaque handle, hence at global scope; its field types are bk::'s
@@ -290,6 +352,13 @@ struct bk_ctx {
     // bk_collect_*: the incremental collection (bk_collect.hip), which owns its
     // buffers -- none of the workspace above, so batch calls leave it intact
     bk::Collect *collect = nullptr;
+    // bk_block_*: the miner's block (bk_block_api.hip), buffers of its own as well
+    bk::Block *block = nullptr;
+    // its cuts (bk_create: BK_BLOCK_MAPPED_HOST / _PINNED / BK_BLOCK_FIN, bytes,
+    // for tools/block_bench.py's measurement of the paths on either side)
+    int64_t block_mapped_host = bk::BLOCK_MAPPED_HOST_MAX;
+    int64_t block_mapped_pinned = bk::BLOCK_MAPPED_PINNED_MAX;
+    int64_t block_fin_max = bk::BLOCK_FIN_MAX;
 };
 
 namespace bk {

@@ -633,4 +633,34 @@ hipError_t launch_collect_noise(const CollectNoiseArgs &a, int num_cu, hipStream
 struct Collect;
 void collect_destroy(Collect *k);
 
+// bk_block.hip: one launch group of the miner's block (bk_block_*): up to
+// BLOCK_GROUP arrivals added to the running gradient in arrival order,
+// gout = gin + rows (another buffer than gin); qin non-null: the quantised
+// int64 sum as well, qout = qin + int64(rows * scale); fin: the results also
+// stored to the mapped host block hg (and hq, hqf with qin).  rows.p[i] is read
+// only where bit i of acc is set; rows aligned to their element size
+constexpr int BLOCK_GROUP = 8;
+struct BlockRows {
+    const void *p[BLOCK_GROUP];
+};
+struct BlockLaunch {
+    BlockRows rows;
+    unsigned acc;
+    int dtype;
+    int64_t d;
+    const double *gin;
+    double *gout;
+    const int64_t *qin;
+    int64_t *qout;
+    double scale;
+    int fin;
+    double *hg;
+    int64_t *hq;
+    double *hqf;
+};
+hipError_t launch_block_add(const BlockLaunch &L, int num_cu, hipStream_t st);
+// bk_block_api.hip: a context's block, which owns its buffers; bk_destroy frees it
+struct Block;
+void block_destroy(Block *b);
+
 }  // namespace bk

@@ -768,6 +768,122 @@ class Engine:
         check(lib().bk_quantized_sum_device(self._ctx, _p(x_ptr), dtype, n, d, ld, _p(idx_ptr), m,
                                             int(precision), _p(sum_ptr), _p(sumf_ptr)))
 
+    # ---- the miner's block, added to as the updates arrive (bk_block_*) -----
+    def block_begin(self, global_w, precision=None, dtype=np.float64):
+        """Start (or restart) the context's block from the gradient global_w (a
+        float64 vector); rows will be `dtype`.  precision None: no quantised sum."""
+        dt = np.dtype(dtype)
+        if dt not in (np.float64, np.float32):
+            raise ValueError("dtype must be float64 or float32")
+        g = np.ascontiguousarray(global_w, dtype=np.float64)
+        if g.ndim != 1 or g.shape[0] < 1:
+            raise ValueError("global_w must be a float64 vector")
+        self.block_begin_ptr(g.ctypes.data, _lib.BK_HOST, g.shape[0], dt, precision)
+
+    def block_begin_ptr(self, global_ptr, where, d, dtype=np.float64, precision=None):
+        """global_w by raw pointer: pageable, pinned or device memory (d doubles)."""
+        dt = np.dtype(dtype)
+        p = -1 if precision is None else int(precision)
+        check(lib().bk_block_begin(self._ctx, _lib.BK_F32 if dt == np.float32 else _lib.BK_F64,
+                                   int(d), _p(global_ptr), int(where), p))
+        self._block = (dt, int(d), p)
+
+    def _block_state(self, who):
+        st = getattr(self, "_block", None)
+        if st is None:
+            raise ValueError("%s without block_begin" % who)
+        return st
+
+    def _block_row(self, r, dt, d):
+        a = np.asarray(r)
+        if a.dtype != dt or a.ndim != 1 or a.shape[0] != d:
+            raise ValueError("every row must be a 1-D %s array of length %d" % (dt, d))
+        return a if a.flags.c_contiguous else np.ascontiguousarray(a)
+
+    def block_add(self, rows, accepted=None):
+        """One 1-D array, or a sequence of them: host rows of the block's dtype
+        and d, in arrival order; accepted None (all) or one flag per row (a
+        rejected row may be None: it is never read).  Returns the first slot."""
+        dt, d, _ = self._block_state("block_add")
+        if isinstance(rows, np.ndarray) and rows.ndim == 1:
+            rows = [rows]
+        rows = list(rows)
+        if not rows:
+            raise ValueError("no rows")
+        if accepted is not None:
+            acc = np.ascontiguousarray(np.atleast_1d(accepted)).astype(np.uint8)
+            if acc.shape != (len(rows),):
+                raise ValueError("accepted must have one flag per row")
+        dummy = np.zeros(1, dtype=dt)
+        keep = [dummy if (r is None and accepted is not None and not acc[i])
+                else self._block_row(r, dt, d) for i, r in enumerate(rows)]
+        ptrs = (ctypes.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
+        return self.block_add_ptr(ptrs, len(keep), _lib.BK_HOST,
+                                  acc.ctypes.data if accepted is not None else None)
+
+    def block_add_ptr(self, row_ptrs, count, where, accepted_ptr=None):
+        """Raw row pointers (a ctypes c_void_p array): pageable, pinned or device
+        rows; accepted_ptr: count bytes, or None for all."""
+        first = ctypes.c_int64(-1)
+        check(lib().bk_block_add(self._ctx, row_ptrs, _p(accepted_ptr), int(count), int(where),
+                                 ctypes.byref(first)))
+        return first.value
+
+    def block_count(self):
+        """(rows added, rows accepted) since block_begin."""
+        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib().bk_block_count(self._ctx, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def _block_outs(self, want_qsum, p, d):
+        if want_qsum and p < 0:
+            raise ValueError("the block was begun without a precision: it keeps no quantised sum")
+        g = np.empty(d, dtype=np.float64)
+        q = np.empty(d, dtype=np.int64) if want_qsum else None
+        qf = np.empty(d, dtype=np.float64) if want_qsum else None
+        return g, q, qf
+
+    def block_finish(self, want_qsum=False):
+        """The block so far (it is not consumed): the gradient, or with want_qsum
+        (gradient, int64 sum, float sum)."""
+        _, d, p = self._block_state("block_finish")
+        g, q, qf = self._block_outs(want_qsum, p, d)
+        self.block_finish_ptr(g.ctypes.data, q.ctypes.data if want_qsum else None,
+                              qf.ctypes.data if want_qsum else None)
+        return (g, q, qf) if want_qsum else g
+
+    def block_finish_ptr(self, global_ptr, qsum_ptr=None, qsum_float_ptr=None):
+        """Host outputs by raw pointer (d entries each)."""
+        check(lib().bk_block_finish(self._ctx, _p(global_ptr), _p(qsum_ptr), _p(qsum_float_ptr)))
+
+    def block_add_finish(self, row, accepted=True, want_qsum=False):
+        """The last arrival and the block in one call (bk_block_add_finish):
+        block_add(row, accepted) followed by block_finish, bitwise.  Returns
+        (slot, gradient) or (slot, gradient, int64 sum, float sum)."""
+        dt, d, p = self._block_state("block_add_finish")
+        a = self._block_row(row, dt, d)
+        g, q, qf = self._block_outs(want_qsum, p, d)
+        slot = self.block_add_finish_ptr(a.ctypes.data, accepted, _lib.BK_HOST, g.ctypes.data,
+                                         q.ctypes.data if want_qsum else None,
+                                         qf.ctypes.data if want_qsum else None)
+        return (slot, g, q, qf) if want_qsum else (slot, g)
+
+    def block_add_finish_ptr(self, row_ptr, accepted, where, global_ptr, qsum_ptr=None,
+                             qsum_float_ptr=None):
+        first = ctypes.c_int64(-1)
+        check(lib().bk_block_add_finish(self._ctx, _p(row_ptr), 1 if accepted else 0, int(where),
+                                        ctypes.byref(first), _p(global_ptr), _p(qsum_ptr),
+                                        _p(qsum_float_ptr)))
+        return first.value
+
+    def block_stats(self):
+        """The block's launches since block_begin (bk_block_stats): [add launches,
+        fused add-finish launches, launches reading mapped host rows, finishes
+        without a D2H copy call]."""
+        out = (ctypes.c_int64 * 4)()
+        check(lib().bk_block_stats(self._ctx, out))
+        return list(out)
+
     def noise_apply_ptr(self, delta_ptr, n, d, ld, noise_ptr, k, noise_ld, out_ptr, out_ld):
         check(lib().bk_noise_apply_device(self._ctx, _p(delta_ptr), n, d, ld, _p(noise_ptr), k,
                                           noise_ld, _p(out_ptr), out_ld))

@@ -243,6 +243,81 @@ func logMargin() {
 	}
 }
 
+// ---- the miner's block, added to as the updates arrive (bk_block_*) ---------
+
+// bkBlockDim is the length of the gradient the engine's block was begun with
+// (0: no block); bkBlockLen counts the updates added to it.
+var (
+	bkBlockDim int
+	bkBlockLen int
+)
+
+// beginBlockGPU starts the engine's block from bc.getLatestGradient(); call it
+// where the miner resets blockUpdates for a new iteration.
+func beginBlockGPU(globalW []float64) bool {
+	d := len(globalW)
+	bkBlockDim, bkBlockLen = 0, 0
+	if bkCtx == nil || d == 0 {
+		return false
+	}
+	var gp *C.double
+	gp = (*C.double)(unsafe.Pointer(&globalW[0]))
+	if st := C.bk_block_begin(bkCtx, C.BK_F64, C.int64_t(d), gp, C.BK_HOST, -1); st != C.BK_OK {
+		outLog.Printf("bk_block_begin failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	bkBlockDim = d
+	return true
+}
+
+// addBlockUpdateGPU replaces the append of addBlockUpdate (honest.go:330-334):
+// the update's Delta goes to the GPU and is added to the running gradient at
+// once if the update is accepted (a rejected update is counted and its Delta
+// never read, honest.go:367-370).  Delta's backing array is pinned for the call
+// and consumed on return.  Returns the number of updates in the block, -1 on an
+// engine error (the caller then falls back to the host loop).
+func addBlockUpdateGPU(update Update) int {
+	if bkCtx == nil || bkBlockDim == 0 || len(update.Delta) != bkBlockDim {
+		return -1
+	}
+	var pinner runtime.Pinner
+	defer pinner.Unpin()
+	var rowsC unsafe.Pointer
+	rowsC = C.malloc(C.size_t(unsafe.Sizeof(uintptr(0))))
+	defer C.free(rowsC)
+	pinner.Pin(&update.Delta[0])
+	unsafe.Slice((*unsafe.Pointer)(rowsC), 1)[0] = unsafe.Pointer(&update.Delta[0])
+	var acc C.uint8_t
+	if update.Accepted {
+		acc = 1
+	}
+	if st := C.bk_block_add(bkCtx, (*unsafe.Pointer)(rowsC), &acc, 1, C.BK_HOST, nil); st != C.BK_OK {
+		outLog.Printf("bk_block_add failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return -1
+	}
+	bkBlockLen++
+	return bkBlockLen
+}
+
+// createBlockGPU replaces the update loop of createBlock (honest.go:346-388):
+// the gradient with every accepted update added in arrival order, bit for bit
+// what pulledGradientM.Add over blockUpdates gives.  The block is not consumed:
+// the deadline path may call it, add late updates and call it again.  The
+// stake bookkeeping stays in createBlock.  nil on an engine error.
+func createBlockGPU() []float64 {
+	if bkCtx == nil || bkBlockDim == 0 {
+		return nil
+	}
+	out := make([]float64, bkBlockDim)
+	var outp *C.double
+	outp = (*C.double)(unsafe.Pointer(&out[0]))
+	if st := C.bk_block_finish(bkCtx, outp, nil, nil); st != C.BK_OK {
+		outLog.Printf("bk_block_finish failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return nil
+	}
+	return out
+}
+
 func noisedDeltas(updates []Update) [][]float64 {
 	deltas := make([][]float64, len(updates))
 	for i := range updates {

@@ -833,6 +833,70 @@ int bk_quantized_sum_device(bk_ctx *ctx, const void *dX, int dtype, int64_t n, i
                             int64_t ld, const int64_t *d_idx, int64_t m, int precision,
                             int64_t *d_sum, double *d_sum_float);
 
+/* ---- the miner's block, added to as the updates arrive -------------------- */
+
+/* A miner receives its updates one RPC at a time (Peer.RegisterUpdate ->
+ * processUpdate -> addBlockUpdate, DistSys/main.go:375, :1206-1235,
+ * honest.go:330-334) and createBlock adds the accepted ones in arrival order
+ * (honest.go:346-388).  The block family does each add when its update
+ * arrives, so the last arrival waits for its own row only.  One block per
+ * context, serialised by the context mutex on the context stream; it owns its
+ * buffers, is independent of a collection on the same context, and any other
+ * call between two adds leaves it intact (and it them).
+ *
+ * bk_block_begin: start (or restart, reusing the buffers) a block of rows of
+ * `dtype` with d elements from the gradient global_w (d doubles at `where`:
+ * BK_HOST, BK_HOST_PINNED or BK_DEVICE; consumed on return).  precision -1: no
+ * quantised sum; 0..18: a running int64 sum of int64(row * 10^precision) is
+ * kept next to the fp64 one, cleared here. */
+int bk_block_begin(bk_ctx *ctx, int dtype, int64_t d, const double *global_w, int where,
+                   int precision);
+/* count >= 1 rows arrive (rows[i]: d elements at `where`, as bk_collect_add's:
+ * pageable with any alignment, pinned, or device rows aligned to their element
+ * size) and take the next `count` arrival slots (*first_slot, nullable: the
+ * first of them).  For each row with accepted[i] != 0 (accepted NULL: all), in
+ * the order given,
+ *     global[c] = global[c] + (double)rows[i][c]        (fp64, no contraction)
+ * and, with precision >= 0,
+ *     q[c] += int64((double)rows[i][c] * 10^precision)  (wrapping; Go's int64())
+ * Rejected rows are counted and never read (honest.go:367-370).  Every input is
+ * consumed on return. */
+int bk_block_add(bk_ctx *ctx, const void *const *rows, const uint8_t *accepted, int64_t count,
+                 int where, int64_t *first_slot);
+/* The rows added since the begin, and how many of them were accepted. */
+int bk_block_count(bk_ctx *ctx, int64_t *added, int64_t *accepted);
+/* The block so far, synchronously; it is not consumed (the deadline path
+ * finishes, more rows may arrive, and it finishes again).  global_out (d
+ * doubles, host) is bitwise bk_aggregate of the stacked rows with idx the
+ * accepted slots in arrival order and the begin's global_w; qsum_out and
+ * qsum_float_out (nullable, d entries each, host) are bitwise
+ * bk_quantized_sum_device on the same rows and idx -- asking for either on a
+ * block begun with precision -1 is BK_EINVAL. */
+int bk_block_finish(bk_ctx *ctx, double *global_out, int64_t *qsum_out, double *qsum_float_out);
+/* The last arrival (the NUM_SAMPLES / 2-th of main.go:1226-1231): exactly
+ * bk_block_add(ctx, &row, &accepted, 1, where, first_slot) followed by
+ * bk_block_finish, bitwise, in one call -- and in one launch where the
+ * gradient is small enough for the kernel's own stores into mapped host memory
+ * to beat the copy back (bk_block_stats). */
+int bk_block_add_finish(bk_ctx *ctx, const void *row, int accepted, int where, int64_t *first_slot,
+                        double *global_out, int64_t *qsum_out, double *qsum_float_out);
+/* Launches since the begin: out[0] add launches (one per group of up to 8
+ * arrivals with an accepted row), out[1] fused add-finish launches, out[2]
+ * launches that read their rows from mapped host memory (no copy call), out[3]
+ * finishes served without a D2H copy call.
+ *
+ * Errors of the family: BK_EINVAL for a null ctx or required pointer, count <
+ * 1, a bad where or dtype, d < 1, precision outside -1..18 (none of these needs
+ * a block or a GPU); then for add, count, finish or stats without begin, a null
+ * rows[i] (named) and more than BK_MAX_N rows in total; BK_ENOMEM for an
+ * allocation failure.  All checks precede any copy, launch or state change: a
+ * refused call leaves the block as it was.  A launch group reads the running
+ * sums and writes a second copy of them, which becomes current once the launch
+ * is queued: after a HIP error the group's rows do not count and the sums are
+ * unchanged.  The launches are timed under BK_K_AGGREGATE.  Added without a
+ * change of BK_ABI_VERSION (14), as bk_set_collect_wide was. */
+int bk_block_stats(bk_ctx *ctx, int64_t out[4]);
+
 /* Noise application (client DP step) -- requestNoiseFromNoisers
  * (DistSys/main.go:1606-1653: noiseVec = 0 + v_0 + ... + v_{k-1}, then
  * /= float64(k)) and NoisedDelta = Delta + noise (main.go:1524-1537), batched
