@@ -22,8 +22,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
-from .krum import Engine, Update, default_engine
+from .krum import Engine, Update, _dtype_code, default_engine
 
 __all__ = ["STAKE_UNIT", "PRECISION", "create_block", "quantized_sum", "apply_noise",
            "BlockCollector"]
@@ -165,9 +164,8 @@ def quantized_sum(deltas, idx, precision: int = PRECISION, engine: Optional[Engi
     s = torch.empty(d, dtype=torch.int64, device=dev)
     sf = torch.empty(d, dtype=torch.float64, device=dev)
     eng.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    dt = _lib.BK_F32 if X.dtype == np.float32 else _lib.BK_F64
-    eng.quantized_sum_ptr(tX.data_ptr(), dt, n, d, d, tI.data_ptr(), len(idx), precision,
-                          s.data_ptr(), sf.data_ptr())
+    eng.quantized_sum_ptr(tX.data_ptr(), _dtype_code(X.dtype), n, d, d, tI.data_ptr(), len(idx),
+                          precision, s.data_ptr(), sf.data_ptr())
     torch.cuda.synchronize(dev)
     return s.cpu().numpy(), sf.cpu().numpy()
 

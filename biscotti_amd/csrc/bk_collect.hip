@@ -415,8 +415,35 @@ int upload_pageable(Collect *k, char *dst, const char *src, size_t bytes, hipStr
     return BK_OK;
 }
 
-int finish_checked(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
-                   int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out);
+// one row (or noise vector) to the device: a pageable one through the ring,
+// a pinned or a device one by a copy of its own
+int copy_row(Collect *k, void *dst, const void *src, size_t bytes, int where, hipStream_t st,
+             bool record = true) {
+    if (where == BK_HOST)
+        return upload_pageable(k, (char *)dst, (const char *)src, bytes, st, record);
+    HIPCHK(hipMemcpyAsync(dst, src, bytes,
+                          where == BK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    return BK_OK;
+}
+
+// a call that added cnt rows succeeded: nothing is left to drain, the caller
+// learns the first new slot and the rows count
+int rows_added(Collect *k, Drain &drain, int64_t cnt, int64_t *first_slot) {
+    drain.armed = false;
+    if (first_slot && cnt > 0) *first_slot = k->count;
+    k->count += cnt;
+    return BK_OK;
+}
+
+// bk_collect_finish's arguments behind the context, as every finish takes them
+struct FinishArgs {
+    const int64_t *order;
+    int64_t n, f;
+    int64_t *sel_idx, *m_out;
+    double *scores, *mean_out;
+};
+
+int finish_checked(bk_ctx *c, Collect *k, const FinishArgs &a);
 
 // every order entry a collected slot (0..count-1), none repeated within its
 // problem; slots may be reused across problems: seen[o] = 1 + the last problem
@@ -440,6 +467,80 @@ int check_order(const int64_t *order, int64_t n, int64_t count, std::vector<int6
     return BK_OK;
 }
 
+// ---- the entries' checks, one per message.  `who` is the entry the message
+// names: a fused entry answers as the add and the finish it stands for
+
+int check_where(int where) {
+    if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
+        return fail(BK_EINVAL, "bad where %d", where);
+    return BK_OK;
+}
+
+// the context's collection if one was begun, else null with BK_EINVAL's message
+// set (the context mutex held, as for every check below that takes k)
+Collect *begun(bk_ctx *c, const char *who) {
+    Collect *k = c->collect;
+    if (k && k->begun) return k;
+    (void)fail(BK_EINVAL, "%s without bk_collect_begin", who);
+    return nullptr;
+}
+
+int check_room(const Collect *k, const char *who, int64_t count) {
+    if (count > k->n_cap - k->count)
+        return fail(BK_EINVAL, "%s: %lld rows past n_cap=%lld (%lld collected)", who,
+                    (long long)count, (long long)k->n_cap, (long long)k->count);
+    return BK_OK;
+}
+
+int check_f64(const Collect *k, const char *who, const char *only) {
+    if (k->dtype != BK_F64)
+        return fail(BK_EINVAL, "%s: the collection is BK_F32 (%s)", who, only);
+    return BK_OK;
+}
+
+// bk_collect_add_noised's checks that need no collection: k, noises and where
+int check_noised_args(const double *const *noises, int64_t kn, int where) {
+    if (kn < 0) return fail(BK_EINVAL, "need k >= 0 (k=%lld)", (long long)kn);
+    if (!noises && kn > 0) return fail(BK_EINVAL, "null noises with k=%lld", (long long)kn);
+    CHK(check_where(where));
+    if (kn > BK_COLLECT_NOISE_MAX_K)
+        return fail(BK_ENOTSUP, "k=%lld exceeds BK_COLLECT_NOISE_MAX_K=%d", (long long)kn,
+                    BK_COLLECT_NOISE_MAX_K);
+    return BK_OK;
+}
+
+// and those on the collection and on its count updates' pointers
+int check_noised_updates(const Collect *k, const double *const *deltas,
+                         const double *const *noises, int64_t kn, int64_t count) {
+    CHK(check_f64(k, "bk_collect_add_noised", "noise is fp64 only"));
+    CHK(check_room(k, "bk_collect_add_noised", count));
+    for (int64_t i = 0; i < count; ++i) {
+        if (!deltas[i]) return fail(BK_EINVAL, "null delta %lld", (long long)i);
+        for (int64_t j = 0; j < kn; ++j)
+            if (!noises[i * kn + j])
+                return fail(BK_EINVAL, "null noise vector (%lld, %lld)", (long long)i, (long long)j);
+    }
+    return BK_OK;
+}
+
+// bk_collect_finish's checks against `rows` collected rows: the count, or
+// count + 1 for the fused entries, whose row arrives in the same call
+int check_finish(const Collect *k, int64_t rows, const int64_t *order, int64_t n, int64_t f) {
+    if (n < 1 || n > rows)
+        return fail(BK_EINVAL, "bk_collect_finish: n=%lld, %lld rows collected", (long long)n,
+                    (long long)rows);
+    if (!order && n != rows)
+        return fail(BK_EINVAL, "bk_collect_finish: a null order needs n = %lld, the rows "
+                               "collected (n=%lld)",
+                    (long long)rows, (long long)n);
+    CHK(bk_check_args(n, k->d, f));
+    if (order) {
+        std::vector<int64_t> seen((size_t)rows, 0);
+        CHK(check_order(order, n, rows, seen, -1));
+    }
+    return BK_OK;
+}
+
 // The finish of n <= 128 rows in one launch: k_collect_small for the deployed
 // shapes (small_ok: d <= 32,768; launch_collect_small) or, in the wide range
 // (wide_ok), k_collect_wide, whose M items stream COLLECT_WIDE_COLS columns of
@@ -452,11 +553,10 @@ int check_order(const int64_t *order, int64_t n, int64_t count, std::vector<int6
 // arguments; stat: the launch's counter in bk_collect_stats.  The arguments are
 // validated by the caller.
 template <typename L>
-int finish_one_launch(bk_ctx *c, Collect *k, L launch, int stat, const int64_t *order, int64_t n,
-                      int64_t f, int64_t *sel_idx, int64_t *m_out, double *scores,
-                      double *mean_out) {
+int finish_one_launch(bk_ctx *c, Collect *k, L launch, int stat, const FinishArgs &a) {
     static_assert(BK_MAX_N <= 65536, "arrival slots travel as 16-bit kernel arguments");
-    const int64_t m = n - f, d = k->d;
+    const int64_t n = a.n, f = a.f, m = n - f, d = k->d;
+    double *const scores = a.scores, *const mean_out = a.mean_out;
     constexpr size_t MPAD = HOUT_MPAD;
     CHK(ensure_small_queue(c));
     CHK(ensure(c->diag, (size_t)n * sizeof(double)));
@@ -464,7 +564,7 @@ int finish_one_launch(bk_ctx *c, Collect *k, L launch, int stat, const int64_t *
     double *blk = c->hout_dev;
     const uint64_t spin = next_spin(c);
     CHK(timed(c, BK_K_SMALL, [&] {
-        return launch(k->store.p, k->dtype, k->ld, (int)n, d, (int)f, (const double *)k->G.p, order,
+        return launch(k->store.p, k->dtype, k->ld, (int)n, d, (int)f, (const double *)k->G.p, a.order,
                       (double *)k->scores.p, (double *)c->diag.p, (int64_t *)(blk + MPAD),
                       mean_out ? blk + MPAD + 2 * n : nullptr, blk,
                       scores ? blk + MPAD + n : nullptr, (unsigned *)c->small_ctr.p, c->num_cu,
@@ -478,10 +578,10 @@ int finish_one_launch(bk_ctx *c, Collect *k, L launch, int stat, const int64_t *
     const double *h = (const double *)c->hout;
     c->margin_unchecked = 0;
     CHK(margin_status(h));
-    memcpy(sel_idx, h + MPAD, (size_t)m * sizeof(int64_t));
+    memcpy(a.sel_idx, h + MPAD, (size_t)m * sizeof(int64_t));
     if (scores) memcpy(scores, h + MPAD + n, (size_t)n * sizeof(double));
     if (mean_out) memcpy(mean_out, h + MPAD + 2 * n, (size_t)d * sizeof(double));
-    if (m_out) *m_out = m;
+    if (a.m_out) *a.m_out = m;
     return BK_OK;
 }
 
@@ -566,13 +666,6 @@ int tiny_block(Collect *k) {
     return BK_OK;
 }
 
-struct TinyFinish {
-    const int64_t *order;
-    int64_t n, f;
-    int64_t *sel_idx, *m_out;
-    double *scores, *mean_out;
-};
-
 // One call of the tiny range past its checks (the context mutex held, the
 // device selected): cnt >= 0 rows arrive (kn > 0: as deltas with kn noise
 // vectors each) and, with fz, the finish follows in the same launch.  Host rows
@@ -584,7 +677,7 @@ struct TinyFinish {
 // waited for, as add_rows waits for their copies.  The rows count only when
 // every launch was queued and, with a finish, completed (add_finish_fused's rule)
 int tiny_call(bk_ctx *c, Collect *k, const void *const *rows, int64_t cnt,
-              const double *const *noises, int64_t kn, int where, const TinyFinish *fz,
+              const double *const *noises, int64_t kn, int where, const FinishArgs *fz,
               int64_t *first_slot) {
     const hipStream_t st = c->stream;
     CHK(tiny_block(k));
@@ -640,8 +733,7 @@ int tiny_call(bk_ctx *c, Collect *k, const void *const *rows, int64_t cnt,
                 L.scores_out = sc_out;
                 return launch_collect_tiny(L, s);
             };
-            CHK(finish_one_launch(c, k, launch, nr > 0 ? 3 : 2, fz->order, fz->n, fz->f, fz->sel_idx,
-                                  fz->m_out, fz->scores, fz->mean_out));
+            CHK(finish_one_launch(c, k, launch, nr > 0 ? 3 : 2, *fz));
             ++k->tiny_stats[nr > 0 ? 2 : 1];
         } else {
             CHK(timed(c, BK_K_SMALL, [&] { return launch_collect_tiny(L, st); }));
@@ -650,10 +742,7 @@ int tiny_call(bk_ctx *c, Collect *k, const void *const *rows, int64_t cnt,
     }
     // device rows are read by the kernel itself: consumed once it is done
     if (dev && cnt > 0 && !fz) HIPCHK(hipStreamSynchronize(st));
-    drain.armed = false;
-    k->count = j0 + cnt;
-    if (first_slot && cnt > 0) *first_slot = j0;
-    return BK_OK;
+    return rows_added(k, drain, cnt, first_slot);
 }
 
 // bk_collect_add past its checks (the context mutex held): the rows copied into
@@ -667,24 +756,15 @@ int add_rows(bk_ctx *c, Collect *k, const void *const *rows, int64_t count, int 
     Drain drain{st};
     const size_t es = esize(k->dtype), bytes = (size_t)k->d * es;
     const int64_t j0 = k->count;
-    for (int64_t i = 0; i < count; ++i) {
-        char *dst = (char *)k->store.p + (size_t)(j0 + i) * (size_t)k->ld * es;
-        if (where == BK_HOST)
-            CHK(upload_pageable(k, dst, (const char *)rows[i], bytes, st));
-        else
-            HIPCHK(hipMemcpyAsync(dst, rows[i], bytes,
-                                  where == BK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                  st));
-    }
+    for (int64_t i = 0; i < count; ++i)
+        CHK(copy_row(k, (char *)k->store.p + (size_t)(j0 + i) * (size_t)k->ld * es, rows[i], bytes,
+                     where, st));
     if (where != BK_HOST) HIPCHK(hipEventRecord(k->ev_up, st));
     CHK(fold_border(k, j0, count, c->num_cu, st));
     // pinned and device rows are read by the copies themselves: consumed once
     // those are done (the border runs on)
     if (where != BK_HOST) HIPCHK(hipEventSynchronize(k->ev_up));
-    drain.armed = false;
-    k->count = j0 + count;
-    if (first_slot) *first_slot = j0;
-    return BK_OK;
+    return rows_added(k, drain, count, first_slot);
 }
 
 // bk_collect_add_finish's fused path past its checks (the context mutex held,
@@ -694,22 +774,16 @@ int add_rows(bk_ctx *c, Collect *k, const void *const *rows, int64_t count, int 
 // wait of finish_one_launch, behind which the row has been consumed.  The
 // collection counts the row only when all of it succeeded: after a failure the
 // next add rewrites the slot and its Gram run
-int add_finish_fused(bk_ctx *c, Collect *k, const void *row, int where, const int64_t *order,
-                     int64_t n, int64_t f, int64_t *first_slot, int64_t *sel_idx, int64_t *m_out,
-                     double *scores, double *mean_out) {
+int add_finish_fused(bk_ctx *c, Collect *k, const void *row, int where, int64_t *first_slot,
+                     const FinishArgs &a) {
     const hipStream_t st = c->stream;
     Drain drain{st};
     const size_t es = esize(k->dtype), bytes = (size_t)k->d * es;
     const int64_t j = k->count;
-    char *dst = (char *)k->store.p + (size_t)j * (size_t)k->ld * es;
     // (a row of the fused range is one ring slot: d <= 32,768; the stream is
     // waited for below, or drained on a failure, before any later add)
-    if (where == BK_HOST)
-        CHK(upload_pageable(k, dst, (const char *)row, bytes, st, false));
-    else
-        HIPCHK(hipMemcpyAsync(dst, row, bytes,
-                              where == BK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                              st));
+    CHK(copy_row(k, (char *)k->store.p + (size_t)j * (size_t)k->ld * es, row, bytes, where, st,
+                 false));
     const auto launch = [j](const void *store, int dtype, int64_t ld, int n_, int64_t d, int f_,
                             const double *G, const int64_t *ord, double *sc, double *diag,
                             int64_t *sel, double *mean, double *margin, double *sc_out,
@@ -718,11 +792,8 @@ int add_finish_fused(bk_ctx *c, Collect *k, const void *row, int where, const in
                                      ord, sc, diag, sel, mean, margin, sc_out, ctr, num_cu, s, spin,
                                      lines);
     };
-    CHK(finish_one_launch(c, k, launch, 3, order, n, f, sel_idx, m_out, scores, mean_out));
-    drain.armed = false;
-    k->count = j + 1;
-    if (first_slot) *first_slot = j;
-    return BK_OK;
+    CHK(finish_one_launch(c, k, launch, 3, a));
+    return rows_added(k, drain, 1, first_slot);
 }
 
 // bk_collect_add_noised past its checks, k >= 1 (fp64 collection, the context
@@ -775,13 +846,8 @@ int add_noised(bk_ctx *c, Collect *k, const double *const *deltas, const double 
         HIPCHK(hipMemcpyAsync(k->ntab.p, ht, (size_t)count * (size_t)kn * sizeof(double *),
                               hipMemcpyHostToDevice, st));
     } else {
-        for (int64_t i = 0; i < count; ++i) {
-            char *dst = (char *)(store + (j0 + i) * k->ld);
-            if (where == BK_HOST)
-                CHK(upload_pageable(k, dst, (const char *)deltas[i], bytes, st));
-            else
-                HIPCHK(hipMemcpyAsync(dst, deltas[i], bytes, hipMemcpyHostToDevice, st));
-        }
+        for (int64_t i = 0; i < count; ++i)
+            CHK(copy_row(k, store + (j0 + i) * k->ld, deltas[i], bytes, where, st));
     }
     for (int64_t r0 = 0; r0 < count; r0 += fit) {
         const int nr = (int)(count - r0 < fit ? count - r0 : fit);
@@ -800,15 +866,10 @@ int add_noised(bk_ctx *c, Collect *k, const double *const *deltas, const double 
             for (int r = 0; r < nr; ++r) {
                 a.out[r] = store + (j0 + r0 + r) * k->ld;
                 a.delta[r] = dev ? deltas[r0 + r] : a.out[r];
-                for (int64_t j = 0; j < kn && !dev; ++j) {
-                    char *dst = (char *)(k->nstage.p) + (size_t)((r * kn + j) * a.sld) * sizeof(double);
-                    const char *src = (const char *)(noises[(r0 + r) * kn + j] + c0);
-                    const size_t len = (size_t)(c1 - c0) * sizeof(double);
-                    if (where == BK_HOST)
-                        CHK(upload_pageable(k, dst, src, len, st));
-                    else
-                        HIPCHK(hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, st));
-                }
+                for (int64_t j = 0; j < kn && !dev; ++j)
+                    CHK(copy_row(k, (double *)k->nstage.p + (r * kn + j) * a.sld,
+                                 noises[(r0 + r) * kn + j] + c0, (size_t)(c1 - c0) * sizeof(double),
+                                 where, st));
             }
             // pinned rows are read by the copies: consumed with the last of them
             if (where == BK_HOST_PINNED && r0 + nr == count && c1 == d)
@@ -820,49 +881,23 @@ int add_noised(bk_ctx *c, Collect *k, const double *const *deltas, const double 
     if (dev) HIPCHK(hipEventRecord(k->ev_up, st));
     CHK(fold_border(k, j0, count, c->num_cu, st));
     if (where != BK_HOST) HIPCHK(hipEventSynchronize(k->ev_up));  // (the border runs on)
-    drain.armed = false;
-    k->count = j0 + count;
-    if (first_slot) *first_slot = j0;
-    return BK_OK;
-}
-
-// bk_collect_finish's checks on the count + 1 rows a fused arrival leaves
-// (bk_collect_add_finish, bk_collect_add_noised_finish; the context mutex held)
-int check_finish_after(const Collect *k, const int64_t *order, int64_t n, int64_t f) {
-    const int64_t after = k->count + 1;
-    if (n < 1 || n > after)
-        return fail(BK_EINVAL, "bk_collect_finish: n=%lld, %lld rows collected", (long long)n,
-                    (long long)after);
-    if (!order && n != after)
-        return fail(BK_EINVAL, "bk_collect_finish: a null order needs n = %lld, the rows "
-                               "collected (n=%lld)",
-                    (long long)after, (long long)n);
-    CHK(bk_check_args(n, k->d, f));
-    if (order) {
-        std::vector<int64_t> seen((size_t)after, 0);
-        CHK(check_order(order, n, after, seen, -1));
-    }
-    return BK_OK;
+    return rows_added(k, drain, count, first_slot);
 }
 
 // bk_collect_add_finish past its checks (the context mutex held, the device
 // selected)
-int add_finish_checked(bk_ctx *c, Collect *k, const void *row, int where, const int64_t *order,
-                       int64_t n, int64_t f, int64_t *first_slot, int64_t *sel_idx, int64_t *m_out,
-                       double *scores, double *mean_out) {
-    if (tiny_ok(c, k, k->count + 1) && tiny_arrive_ok(k, true)) {
-        const TinyFinish fz = {order, n, f, sel_idx, m_out, scores, mean_out};
-        return tiny_call(c, k, &row, 1, nullptr, 0, where, &fz, first_slot);
-    }
+int add_finish_checked(bk_ctx *c, Collect *k, const void *row, int where, int64_t *first_slot,
+                       const FinishArgs &a) {
+    if (tiny_ok(c, k, k->count + 1) && tiny_arrive_ok(k, true))
+        return tiny_call(c, k, &row, 1, nullptr, 0, where, &a, first_slot);
     // the fused launch: the finish in k_collect_small's range, a border of at
     // most 128 rows and no long pageable row; everything else is the two
     // entries' own paths
     const bool long_host = where == BK_HOST && (size_t)k->d * esize(k->dtype) > ARRIVE_HOST_MAX_BYTES;
-    if (k->count + 1 <= 128 && !long_host && small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
-        return add_finish_fused(c, k, row, where, order, n, f, first_slot, sel_idx, m_out, scores,
-                                mean_out);
+    if (k->count + 1 <= 128 && !long_host && small_ok(c, k->store.p, k->dtype, a.n, k->d, k->ld))
+        return add_finish_fused(c, k, row, where, first_slot, a);
     CHK(add_rows(c, k, &row, 1, where, first_slot));
-    return finish_checked(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
+    return finish_checked(c, k, a);
 }
 
 // bk_collect_add_noised_finish's fused path past its checks, k >= 1 (fp64
@@ -876,8 +911,7 @@ int add_finish_checked(bk_ctx *c, Collect *k, const void *row, int where, const 
 // collection counts the row only when all of it succeeded (add_finish_fused)
 int add_noised_finish_fused(bk_ctx *c, Collect *k, const double *delta,
                             const double *const *noises, int64_t kn, int where,
-                            const int64_t *order, int64_t n, int64_t f, int64_t *first_slot,
-                            int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
+                            int64_t *first_slot, const FinishArgs &a) {
     static_assert(BK_COLLECT_NOISE_MAX_K == COLLECT_ARRIVE_NOISE_MAX_K, "the launch's vector table");
     const hipStream_t st = c->stream;
     const int64_t j = k->count, d = k->d;
@@ -901,16 +935,10 @@ int add_noised_finish_fused(bk_ctx *c, Collect *k, const double *delta,
     if (dev) {
         for (int64_t q = 0; q < kn; ++q) vecs[q] = noises[q];
     } else {
-        if (where == BK_HOST)
-            CHK(upload_pageable(k, (char *)rowj, (const char *)delta, bytes, st, record));
-        else
-            HIPCHK(hipMemcpyAsync(rowj, delta, bytes, hipMemcpyHostToDevice, st));
+        CHK(copy_row(k, rowj, delta, bytes, where, st, record));
         for (int64_t q = 0; q < kn; ++q) {
             double *dst = (double *)k->nstage.p + q * sld;
-            if (where == BK_HOST)
-                CHK(upload_pageable(k, (char *)dst, (const char *)noises[q], bytes, st, record));
-            else
-                HIPCHK(hipMemcpyAsync(dst, noises[q], bytes, hipMemcpyHostToDevice, st));
+            CHK(copy_row(k, dst, noises[q], bytes, where, st, record));
             vecs[q] = dst;
         }
     }
@@ -923,11 +951,8 @@ int add_noised_finish_fused(bk_ctx *c, Collect *k, const double *delta,
                                             const_cast<double *>(G), ord, sc, diag, sel, mean,
                                             margin, sc_out, ctr, num_cu, s, spin, lines);
     };
-    CHK(finish_one_launch(c, k, launch, 3, order, n, f, sel_idx, m_out, scores, mean_out));
-    drain.armed = false;
-    k->count = j + 1;
-    if (first_slot) *first_slot = j;
-    return BK_OK;
+    CHK(finish_one_launch(c, k, launch, 3, a));
+    return rows_added(k, drain, 1, first_slot);
 }
 
 }  // namespace
@@ -1012,14 +1037,11 @@ int bk_collect_add(bk_ctx *c, const void *const *rows, int64_t count, int where,
     if (!c) return fail(BK_EINVAL, "null context");
     if (!rows) return fail(BK_EINVAL, "null rows");
     if (count < 1) return fail(BK_EINVAL, "need count >= 1 (count=%lld)", (long long)count);
-    if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
-        return fail(BK_EINVAL, "bad where %d", where);
+    CHK(check_where(where));
     std::lock_guard<std::mutex> lk(c->mu);
-    Collect *k = c->collect;
-    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_add without bk_collect_begin");
-    if (count > k->n_cap - k->count)
-        return fail(BK_EINVAL, "bk_collect_add: %lld rows past n_cap=%lld (%lld collected)",
-                    (long long)count, (long long)k->n_cap, (long long)k->count);
+    Collect *k = begun(c, "bk_collect_add");
+    if (!k) return BK_EINVAL;
+    CHK(check_room(k, "bk_collect_add", count));
     for (int64_t i = 0; i < count; ++i)
         if (!rows[i]) return fail(BK_EINVAL, "null row %lld", (long long)i);
     return add_rows(c, k, rows, count, where, first_slot);
@@ -1030,27 +1052,11 @@ int bk_collect_add_noised(bk_ctx *c, const double *const *deltas, const double *
     if (!c) return fail(BK_EINVAL, "null context");
     if (!deltas) return fail(BK_EINVAL, "null deltas");
     if (count < 1) return fail(BK_EINVAL, "need count >= 1 (count=%lld)", (long long)count);
-    if (kn < 0) return fail(BK_EINVAL, "need k >= 0 (k=%lld)", (long long)kn);
-    if (!noises && kn > 0) return fail(BK_EINVAL, "null noises with k=%lld", (long long)kn);
-    if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
-        return fail(BK_EINVAL, "bad where %d", where);
-    if (kn > BK_COLLECT_NOISE_MAX_K)
-        return fail(BK_ENOTSUP, "k=%lld exceeds BK_COLLECT_NOISE_MAX_K=%d", (long long)kn,
-                    BK_COLLECT_NOISE_MAX_K);
+    CHK(check_noised_args(noises, kn, where));
     std::lock_guard<std::mutex> lk(c->mu);
-    Collect *k = c->collect;
-    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_add_noised without bk_collect_begin");
-    if (k->dtype != BK_F64)
-        return fail(BK_EINVAL, "bk_collect_add_noised: the collection is BK_F32 (noise is fp64 only)");
-    if (count > k->n_cap - k->count)
-        return fail(BK_EINVAL, "bk_collect_add_noised: %lld rows past n_cap=%lld (%lld collected)",
-                    (long long)count, (long long)k->n_cap, (long long)k->count);
-    for (int64_t i = 0; i < count; ++i) {
-        if (!deltas[i]) return fail(BK_EINVAL, "null delta %lld", (long long)i);
-        for (int64_t j = 0; j < kn; ++j)
-            if (!noises[i * kn + j])
-                return fail(BK_EINVAL, "null noise vector (%lld, %lld)", (long long)i, (long long)j);
-    }
+    Collect *k = begun(c, "bk_collect_add_noised");
+    if (!k) return BK_EINVAL;
+    CHK(check_noised_updates(k, deltas, noises, kn, count));
     // no noisers: the row is the delta, bitwise (bk_multikrum_noised's rule)
     if (kn == 0)
         return add_rows(c, k, (const void *const *)deltas, count, where, first_slot);
@@ -1063,10 +1069,9 @@ int bk_collect_read_rows(bk_ctx *c, const int64_t *slots, int64_t count, double 
     if (!out_rows) return fail(BK_EINVAL, "null out_rows");
     if (count < 1) return fail(BK_EINVAL, "need count >= 1 (count=%lld)", (long long)count);
     std::lock_guard<std::mutex> lk(c->mu);
-    Collect *k = c->collect;
-    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_read_rows without bk_collect_begin");
-    if (k->dtype != BK_F64)
-        return fail(BK_EINVAL, "bk_collect_read_rows: the collection is BK_F32 (fp64 rows only)");
+    Collect *k = begun(c, "bk_collect_read_rows");
+    if (!k) return BK_EINVAL;
+    CHK(check_f64(k, "bk_collect_read_rows", "fp64 rows only"));
     for (int64_t i = 0; i < count; ++i)
         if (slots[i] < 0 || slots[i] >= k->count)
             return fail(BK_EINVAL, "slots[%lld] = %lld is no collected slot (0..%lld)", (long long)i,
@@ -1098,22 +1103,11 @@ int bk_collect_finish(bk_ctx *c, const int64_t *order, int64_t n, int64_t f, int
     if (!c) return fail(BK_EINVAL, "null context");
     if (!sel_idx) return fail(BK_EINVAL, "null sel_idx");
     std::lock_guard<std::mutex> lk(c->mu);
-    Collect *k = c->collect;
-    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_finish without bk_collect_begin");
-    if (n < 1 || n > k->count)
-        return fail(BK_EINVAL, "bk_collect_finish: n=%lld, %lld rows collected", (long long)n,
-                    (long long)k->count);
-    if (!order && n != k->count)
-        return fail(BK_EINVAL, "bk_collect_finish: a null order needs n = %lld, the rows "
-                               "collected (n=%lld)",
-                    (long long)k->count, (long long)n);
-    CHK(bk_check_args(n, k->d, f));
-    if (order) {
-        std::vector<int64_t> seen((size_t)k->count, 0);
-        CHK(check_order(order, n, k->count, seen, -1));
-    }
+    Collect *k = begun(c, "bk_collect_finish");
+    if (!k) return BK_EINVAL;
+    CHK(check_finish(k, k->count, order, n, f));
     DeviceGuard dg(c->device);
-    return finish_checked(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
+    return finish_checked(c, k, {order, n, f, sel_idx, m_out, scores, mean_out});
 }
 
 int bk_collect_add_finish(bk_ctx *c, const void *row, int where, const int64_t *order, int64_t n,
@@ -1122,19 +1116,16 @@ int bk_collect_add_finish(bk_ctx *c, const void *row, int where, const int64_t *
     // bk_collect_add's checks, then bk_collect_finish's on count + 1 rows
     if (!c) return fail(BK_EINVAL, "null context");
     if (!row) return fail(BK_EINVAL, "null row 0");
-    if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
-        return fail(BK_EINVAL, "bad where %d", where);
+    CHK(check_where(where));
     if (!sel_idx) return fail(BK_EINVAL, "null sel_idx");
     std::lock_guard<std::mutex> lk(c->mu);
-    Collect *k = c->collect;
-    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_add without bk_collect_begin");
-    if (1 > k->n_cap - k->count)
-        return fail(BK_EINVAL, "bk_collect_add: %lld rows past n_cap=%lld (%lld collected)", 1LL,
-                    (long long)k->n_cap, (long long)k->count);
-    CHK(check_finish_after(k, order, n, f));
+    Collect *k = begun(c, "bk_collect_add");
+    if (!k) return BK_EINVAL;
+    CHK(check_room(k, "bk_collect_add", 1));
+    CHK(check_finish(k, k->count + 1, order, n, f));
     DeviceGuard dg(c->device);
-    return add_finish_checked(c, k, row, where, order, n, f, first_slot, sel_idx, m_out, scores,
-                              mean_out);
+    return add_finish_checked(c, k, row, where, first_slot,
+                              {order, n, f, sel_idx, m_out, scores, mean_out});
 }
 
 int bk_collect_add_noised_finish(bk_ctx *c, const double *delta, const double *const *noises,
@@ -1145,34 +1136,19 @@ int bk_collect_add_noised_finish(bk_ctx *c, const double *delta, const double *c
     // count + 1 rows, as bk_collect_add_finish does them
     if (!c) return fail(BK_EINVAL, "null context");
     if (!delta) return fail(BK_EINVAL, "null delta 0");
-    if (kn < 0) return fail(BK_EINVAL, "need k >= 0 (k=%lld)", (long long)kn);
-    if (!noises && kn > 0) return fail(BK_EINVAL, "null noises with k=%lld", (long long)kn);
-    if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
-        return fail(BK_EINVAL, "bad where %d", where);
-    if (kn > BK_COLLECT_NOISE_MAX_K)
-        return fail(BK_ENOTSUP, "k=%lld exceeds BK_COLLECT_NOISE_MAX_K=%d", (long long)kn,
-                    BK_COLLECT_NOISE_MAX_K);
+    CHK(check_noised_args(noises, kn, where));
     if (!sel_idx) return fail(BK_EINVAL, "null sel_idx");
     std::lock_guard<std::mutex> lk(c->mu);
-    Collect *k = c->collect;
-    if (!k || !k->begun) return fail(BK_EINVAL, "bk_collect_add_noised without bk_collect_begin");
-    if (k->dtype != BK_F64)
-        return fail(BK_EINVAL, "bk_collect_add_noised: the collection is BK_F32 (noise is fp64 only)");
-    if (1 > k->n_cap - k->count)
-        return fail(BK_EINVAL, "bk_collect_add_noised: %lld rows past n_cap=%lld (%lld collected)",
-                    1LL, (long long)k->n_cap, (long long)k->count);
-    for (int64_t j = 0; j < kn; ++j)
-        if (!noises[j]) return fail(BK_EINVAL, "null noise vector (%lld, %lld)", 0LL, (long long)j);
-    CHK(check_finish_after(k, order, n, f));
+    Collect *k = begun(c, "bk_collect_add_noised");
+    if (!k) return BK_EINVAL;
+    CHK(check_noised_updates(k, &delta, noises, kn, 1));
+    CHK(check_finish(k, k->count + 1, order, n, f));
     DeviceGuard dg(c->device);
+    const FinishArgs a = {order, n, f, sel_idx, m_out, scores, mean_out};
     // no noisers: the row is the delta, bk_collect_add_finish's path and bits
-    if (kn == 0)
-        return add_finish_checked(c, k, delta, where, order, n, f, first_slot, sel_idx, m_out,
-                                  scores, mean_out);
-    if (tiny_ok(c, k, k->count + 1) && tiny_arrive_ok(k, where == BK_DEVICE)) {
-        const TinyFinish fz = {order, n, f, sel_idx, m_out, scores, mean_out};
-        return tiny_call(c, k, (const void *const *)&delta, 1, noises, kn, where, &fz, first_slot);
-    }
+    if (kn == 0) return add_finish_checked(c, k, delta, where, first_slot, a);
+    if (tiny_ok(c, k, k->count + 1) && tiny_arrive_ok(k, where == BK_DEVICE))
+        return tiny_call(c, k, (const void *const *)&delta, 1, noises, kn, where, &a, first_slot);
     // the fused launch: the finish in k_collect_small's range, a border of at
     // most 128 rows, and of the long host rows only pinned ones with one noise
     // vector (ARRIVE_NOISED_HOST_MAX_BYTES); everything else is the two
@@ -1180,10 +1156,9 @@ int bk_collect_add_noised_finish(bk_ctx *c, const double *delta, const double *c
     const bool long_host = where != BK_DEVICE && !(where == BK_HOST_PINNED && kn == 1) &&
                            (size_t)k->d * sizeof(double) > ARRIVE_NOISED_HOST_MAX_BYTES;
     if (k->count + 1 <= 128 && !long_host && small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
-        return add_noised_finish_fused(c, k, delta, noises, kn, where, order, n, f, first_slot,
-                                       sel_idx, m_out, scores, mean_out);
+        return add_noised_finish_fused(c, k, delta, noises, kn, where, first_slot, a);
     CHK(add_noised(c, k, &delta, noises, kn, 1, where, first_slot));
-    return finish_checked(c, k, order, n, f, sel_idx, m_out, scores, mean_out);
+    return finish_checked(c, k, a);
 }
 
 int bk_collect_stats(bk_ctx *c, int64_t out[4]) {
@@ -1209,18 +1184,13 @@ int bk_collect_tiny_stats(bk_ctx *c, int64_t out[3]) {
 namespace {
 
 // bk_collect_finish past its checks (the context mutex held, the device selected)
-int finish_checked(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
-                   int64_t *sel_idx, int64_t *m_out, double *scores, double *mean_out) {
-    if (tiny_ok(c, k, k->count)) {
-        const TinyFinish fz = {order, n, f, sel_idx, m_out, scores, mean_out};
-        return tiny_call(c, k, nullptr, 0, nullptr, 0, BK_HOST, &fz, nullptr);
-    }
+int finish_checked(bk_ctx *c, Collect *k, const FinishArgs &a) {
+    const auto [order, n, f, sel_idx, m_out, scores, mean_out] = a;
+    if (tiny_ok(c, k, k->count)) return tiny_call(c, k, nullptr, 0, nullptr, 0, BK_HOST, &a, nullptr);
     if (small_ok(c, k->store.p, k->dtype, n, k->d, k->ld))
-        return finish_one_launch(c, k, launch_collect_small, 2, order, n, f, sel_idx, m_out, scores,
-                                 mean_out);
+        return finish_one_launch(c, k, launch_collect_small, 2, a);
     if (wide_ok(c, n, k->d, mean_out != nullptr))
-        return finish_one_launch(c, k, launch_collect_wide, 2, order, n, f, sel_idx, m_out, scores,
-                                 mean_out);
+        return finish_one_launch(c, k, launch_collect_wide, 2, a);
     const hipStream_t st = c->stream;
     Drain drain{st};
     int64_t *ho = (int64_t *)k->horder.p;
@@ -1330,7 +1300,7 @@ int batch_close(bk_ctx *c, int64_t batch) {
 // the device and none back
 int finish_one_of_batch(bk_ctx *c, Collect *k, const int64_t *order, int64_t n, int64_t f,
                         int64_t *sel_idx, double *scores, double *mean_out, double *rec) {
-    CHK(finish_checked(c, k, order, n, f, sel_idx, nullptr, scores, mean_out));
+    CHK(finish_checked(c, k, {order, n, f, sel_idx, nullptr, scores, mean_out}));
     memcpy(rec, c->margin_host, MARGIN_WORDS * sizeof(double));
     return BK_OK;
 }
@@ -1427,9 +1397,8 @@ int bk_collect_finish_batch(bk_ctx *c, const int64_t *orders, int64_t batch, int
     if (!orders) return fail(BK_EINVAL, "null orders");
     if (!sel_idx) return fail(BK_EINVAL, "null sel_idx");
     std::lock_guard<std::mutex> lk(c->mu);
-    Collect *k = c->collect;
-    if (!k || !k->begun)
-        return fail(BK_EINVAL, "bk_collect_finish_batch without bk_collect_begin");
+    Collect *k = begun(c, "bk_collect_finish_batch");
+    if (!k) return BK_EINVAL;
     if (n < 1 || n > k->count)
         return fail(BK_EINVAL, "bk_collect_finish_batch: n=%lld, %lld rows collected",
                     (long long)n, (long long)k->count);
@@ -1610,9 +1579,8 @@ int bk_collect_finish_ragged(bk_ctx *c, const int64_t *orders, const int64_t *of
     if (!fs) return fail(BK_EINVAL, "null fs");
     if (!sel_idx) return fail(BK_EINVAL, "null sel_idx");
     std::lock_guard<std::mutex> lk(c->mu);
-    Collect *k = c->collect;
-    if (!k || !k->begun)
-        return fail(BK_EINVAL, "bk_collect_finish_ragged without bk_collect_begin");
+    Collect *k = begun(c, "bk_collect_finish_ragged");
+    if (!k) return BK_EINVAL;
     if (offsets[0] != 0)
         return fail(BK_EINVAL, "bk_collect_finish_ragged: offsets[0] = %lld, not 0",
                     (long long)offsets[0]);

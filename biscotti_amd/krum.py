@@ -50,6 +50,93 @@ def _as_rows(X):
     return X
 
 
+def _dtype_code(dt):
+    return _lib.BK_F32 if dt == np.float32 else _lib.BK_F64
+
+
+def _ptr(a):
+    """a's address, or None for an output that was not asked for."""
+    return a.ctypes.data if a is not None else None
+
+
+def _ptr_array(arrays):
+    return (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+
+def _row(r, dt, d, what="every row"):
+    a = np.asarray(r)
+    if a.dtype != dt or a.ndim != 1 or a.shape[0] != d:
+        raise ValueError("%s must be a 1-D %s array of length %d" % (what, dt, d))
+    return a if a.flags.c_contiguous else np.ascontiguousarray(a)
+
+
+def _outs(n, d, f, want_scores, want_mean, batch=None):
+    """bk_check_args, then a call's outputs (sel, scores, mean), the last two
+    None when not wanted; batch: of B problems of this shape."""
+    check(lib().bk_check_args(n, d, f))
+    lead = () if batch is None else (batch,)
+    sel = np.empty(lead + (n - f,), dtype=np.int64)
+    sc = np.empty(lead + (n,), dtype=np.float64) if want_scores else None
+    mean = np.empty(lead + (d,), dtype=np.float64) if want_mean else None
+    return sel, sc, mean
+
+
+def _noise_arg(delta, noise, dt, d):
+    """One noised update as the collection takes it: delta (d,), the noise as a
+    (k, d) array (None: k = 0) and its k row pointers (None when k = 0)."""
+    if dt != np.float64:
+        raise ValueError("noise is float64 only: the collection is %s" % dt)
+    D = np.ascontiguousarray(delta, dtype=np.float64)
+    if D.ndim != 1 or D.shape[0] != d:
+        raise ValueError("delta must be a 1-D float64 array of length %d" % d)
+    if noise is None:
+        N = np.empty((0, d), dtype=np.float64)
+    else:
+        N = np.ascontiguousarray(noise, dtype=np.float64)
+        if N.ndim == 1:
+            N = N.reshape(1, -1)
+        if N.ndim != 2 or (N.shape[0] > 0 and N.shape[1] != d):
+            raise ValueError("noise must be None, a vector of length %d or a (k, %d) array"
+                             % (d, d))
+    return D, N, _ptr_array(list(N)) if len(N) else None
+
+
+def _fs_arg(fs, B):
+    """fs as B int64s (an int: the same f for all) and nothing else."""
+    if np.ndim(fs) == 0:
+        fs = [int(fs)] * B
+    fs = np.ascontiguousarray(fs, dtype=np.int64)
+    if fs.ndim != 1 or fs.shape[0] != B:
+        raise ValueError("fs must be an int or one f per problem (%d problems)" % B)
+    return fs
+
+
+def _offsets(ns):
+    offsets = np.zeros(len(ns) + 1, dtype=np.int64)
+    np.cumsum(ns, out=offsets[1:])
+    return offsets
+
+
+def _ragged_outs(ns, fs, d, want_scores, want_mean):
+    """A ragged call's outputs (sel, the m per problem, scores, mean), with room
+    for every problem even where a check in the library would refuse the call."""
+    B = len(ns)
+    sel = np.empty(max(int(np.maximum(ns - fs, 0).sum()), 1), dtype=np.int64)
+    mo = np.zeros(B, dtype=np.int64)
+    sc = np.empty(max(int(ns.sum()), 1), dtype=np.float64) if want_scores else None
+    mean = np.empty((B, max(d, 1)), dtype=np.float64) if want_mean else None
+    return sel, mo, sc, mean
+
+
+def _ragged_unpack(sel, mo, sc, offsets):
+    """The packed sel and scores as one copy per problem (scores None stays None)."""
+    so = _offsets(mo)
+    B = len(mo)
+    sels = [sel[so[b]:so[b + 1]].copy() for b in range(B)]
+    scs = [sc[offsets[b]:offsets[b + 1]].copy() for b in range(B)] if sc is not None else None
+    return sels, scs
+
+
 class GroupEngine:
     """One process driving G GPUs (bk_group_*): the Go verifier's multi-GPU
     form.  Each device copies its column shard of the host batch over its own
@@ -87,20 +174,13 @@ class GroupEngine:
         X = _as_rows(X)
         n, d = X.shape
         f = int(f)
-        check(lib().bk_check_args(n, d, f))
-        m = n - f
-        sel = np.empty(m, dtype=np.int64)
+        sel, sc, mean = _outs(n, d, f, want_scores, want_mean)
         mo = ctypes.c_int64(0)
-        sc = np.empty(n, dtype=np.float64) if want_scores else None
-        mean = np.empty(d, dtype=np.float64) if want_mean else None
-        dt = _lib.BK_F32 if X.dtype == np.float32 else _lib.BK_F64
         check(lib().bk_group_multikrum(self._g, X.ctypes.data,
-                                       _lib.BK_HOST_PINNED if pinned else _lib.BK_HOST, dt, n, d,
-                                       X.strides[0] // X.itemsize, f, sel.ctypes.data,
-                                       ctypes.addressof(mo),
-                                       sc.ctypes.data if sc is not None else None,
-                                       mean.ctypes.data if mean is not None else None))
-        assert mo.value == m
+                                       _lib.BK_HOST_PINNED if pinned else _lib.BK_HOST,
+                                       _dtype_code(X.dtype), n, d, X.strides[0] // X.itemsize, f,
+                                       sel.ctypes.data, ctypes.addressof(mo), _ptr(sc), _ptr(mean)))
+        assert mo.value == n - f
         return sel, sc, mean
 
 
@@ -129,28 +209,15 @@ class Engine:
 
     # ---- host entry (bk_multikrum): numpy in, numpy out -----------------
     def multikrum(self, X, f, want_scores=True, want_mean=True):
-        X = np.asarray(X)
-        if X.dtype not in (np.float64, np.float32):
-            X = X.astype(np.float64)
-        if X.ndim != 2:
-            raise ValueError("deltas must be 2-D (n updates x d)")
-        if X.strides[1] != X.itemsize or X.strides[0] % X.itemsize:
-            X = np.ascontiguousarray(X)
+        X = _as_rows(X)
         n, d = X.shape
-        ld = X.strides[0] // X.itemsize
         f = int(f)
-        check(lib().bk_check_args(n, d, f))
-        m = n - f
-        sel = np.empty(m, dtype=np.int64)
+        sel, sc, mean = _outs(n, d, f, want_scores, want_mean)
         mo = ctypes.c_int64(0)
-        sc = np.empty(n, dtype=np.float64) if want_scores else None
-        mean = np.empty(d, dtype=np.float64) if want_mean else None
-        dt = _lib.BK_F32 if X.dtype == np.float32 else _lib.BK_F64
-        check(lib().bk_multikrum(self._ctx, X.ctypes.data, _lib.BK_HOST, dt, n, d, ld, f,
-                                 sel.ctypes.data, ctypes.addressof(mo),
-                                 sc.ctypes.data if sc is not None else None,
-                                 mean.ctypes.data if mean is not None else None))
-        assert mo.value == m
+        check(lib().bk_multikrum(self._ctx, X.ctypes.data, _lib.BK_HOST, _dtype_code(X.dtype), n,
+                                 d, X.strides[0] // X.itemsize, f, sel.ctypes.data,
+                                 ctypes.addressof(mo), _ptr(sc), _ptr(mean)))
+        assert mo.value == n - f
         return sel, sc, mean
 
     # ---- row-fed host entry (bk_multikrum_rows): n separate host rows, ---
@@ -176,19 +243,11 @@ class Engine:
         if any(a.shape[0] != d for a in keep):
             raise ValueError("ragged rows")
         f = int(f)
-        check(lib().bk_check_args(n, d, f))
-        m = n - f
-        ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in keep])
-        sel = np.empty(m, dtype=np.int64)
+        sel, sc, mean = _outs(n, d, f, want_scores, want_mean)
         mo = ctypes.c_int64(0)
-        sc = np.empty(n, dtype=np.float64) if want_scores else None
-        mean = np.empty(d, dtype=np.float64) if want_mean else None
-        check(lib().bk_multikrum_rows(self._ctx, ptrs, _lib.BK_F32 if dt == np.float32 else
-                                      _lib.BK_F64, n, d, f, sel.ctypes.data,
-                                      ctypes.addressof(mo),
-                                      sc.ctypes.data if sc is not None else None,
-                                      mean.ctypes.data if mean is not None else None))
-        assert mo.value == m
+        check(lib().bk_multikrum_rows(self._ctx, _ptr_array(keep), _dtype_code(dt), n, d, f,
+                                      sel.ctypes.data, ctypes.addressof(mo), _ptr(sc), _ptr(mean)))
+        assert mo.value == n - f
         return sel, sc, mean
 
     def multikrum_rows_ptr(self, row_ptrs, dtype, n, d, f, sel_ptr, scores_ptr=None,
@@ -210,29 +269,42 @@ class Engine:
         dt = np.dtype(dtype)
         if dt not in (np.float64, np.float32):
             raise ValueError("dtype must be float64 or float32")
-        check(lib().bk_collect_begin(self._ctx, _lib.BK_F32 if dt == np.float32 else _lib.BK_F64,
-                                     int(n_cap), int(d)))
+        check(lib().bk_collect_begin(self._ctx, _dtype_code(dt), int(n_cap), int(d)))
         self._collect = (dt, int(d))
+
+    def _collection(self, who):
+        st = getattr(self, "_collect", None)
+        if st is None:
+            raise ValueError("%s without collect_begin" % who)
+        return st
+
+    def _order_arg(self, order, n, f, extra=0):
+        """A finish's order, n and f as the library takes them: order int64 slots
+        or None (every collected row, and the `extra` the call itself adds); n
+        defaults to the order's length."""
+        if f is None:
+            raise ValueError("f is required")
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.int64)
+            if n is None:
+                n = len(order)
+            if order.ndim != 1 or len(order) < n:
+                raise ValueError("order must list n arrival slots")
+        elif n is None:
+            n = self.collect_count() + extra
+        return order, int(n), int(f)
 
     def collect_add(self, rows):
         """One 1-D array, or a sequence of them (one add: the resident rows are
         read once for the group): host rows of the collection's dtype and d.
         Returns the first arrival slot."""
-        if getattr(self, "_collect", None) is None:
-            raise ValueError("collect_add without collect_begin")
-        dt, d = self._collect
+        dt, d = self._collection("collect_add")
         if isinstance(rows, np.ndarray) and rows.ndim == 1:
             rows = [rows]
-        keep = []
-        for r in rows:
-            a = np.asarray(r)
-            if a.dtype != dt or a.ndim != 1 or a.shape[0] != d:
-                raise ValueError("every row must be a 1-D %s array of length %d" % (dt, d))
-            keep.append(a if a.flags.c_contiguous else np.ascontiguousarray(a))
+        keep = [_row(r, dt, d) for r in rows]
         if not keep:
             raise ValueError("no rows")
-        ptrs = (ctypes.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
-        return self.collect_add_ptr(ptrs, len(keep), _lib.BK_HOST)
+        return self.collect_add_ptr(_ptr_array(keep), len(keep), _lib.BK_HOST)
 
     def collect_add_ptr(self, row_ptrs, count, where):
         """Raw row pointers (a ctypes c_void_p array): pageable, pinned or device."""
@@ -247,27 +319,9 @@ class Engine:
         row is delta), a vector of length d (k = 1) or a (k, d) array.  The
         stored row is delta + (0 + v_0 + ... + v_{k-1}) / k, added on the
         device.  Returns the arrival slot."""
-        if getattr(self, "_collect", None) is None:
-            raise ValueError("collect_add_noised without collect_begin")
-        dt, d = self._collect
-        if dt != np.float64:
-            raise ValueError("noise is float64 only: the collection is %s" % dt)
-        D = np.ascontiguousarray(delta, dtype=np.float64)
-        if D.ndim != 1 or D.shape[0] != d:
-            raise ValueError("delta must be a 1-D float64 array of length %d" % d)
-        if noise is None:
-            N = np.empty((0, d), dtype=np.float64)
-        else:
-            N = np.ascontiguousarray(noise, dtype=np.float64)
-            if N.ndim == 1:
-                N = N.reshape(1, -1)
-            if N.ndim != 2 or (N.shape[0] > 0 and N.shape[1] != d):
-                raise ValueError("noise must be None, a vector of length %d or a (k, %d) array"
-                                 % (d, d))
-        k = N.shape[0]
-        dp = (ctypes.c_void_p * 1)(D.ctypes.data)
-        nz = (ctypes.c_void_p * k)(*[N[j].ctypes.data for j in range(k)]) if k else None
-        return self.collect_add_noised_ptr(dp, nz, k, 1, _lib.BK_HOST)
+        dt, d = self._collection("collect_add_noised")
+        D, N, nz = _noise_arg(delta, noise, dt, d)
+        return self.collect_add_noised_ptr(_ptr_array([D]), nz, len(N), 1, _lib.BK_HOST)
 
     def collect_add_noised_ptr(self, delta_ptrs, noise_ptrs, k, count, where):
         """Raw pointers (ctypes c_void_p arrays): count deltas and count * k noise
@@ -281,15 +335,13 @@ class Engine:
     def collect_read_rows(self, slots):
         """The stored rows of the named arrival slots (bk_collect_read_rows), a
         (len(slots), d) float64 array: after a noised add, NoisedDelta."""
-        if getattr(self, "_collect", None) is None:
-            raise ValueError("collect_read_rows without collect_begin")
-        _, d = self._collect
+        _, d = self._collection("collect_read_rows")
         slots = np.ascontiguousarray(np.atleast_1d(slots), dtype=np.int64)
         if slots.ndim != 1 or len(slots) < 1:
             raise ValueError("slots must list at least one arrival slot")
         out = np.empty((len(slots), d), dtype=np.float64)
-        ptrs = (ctypes.c_void_p * len(slots))(*[out[i].ctypes.data for i in range(len(slots))])
-        check(lib().bk_collect_read_rows(self._ctx, slots.ctypes.data, len(slots), ptrs))
+        check(lib().bk_collect_read_rows(self._ctx, slots.ctypes.data, len(slots),
+                                         _ptr_array(list(out))))
         return out
 
     def collect_count(self):
@@ -301,31 +353,13 @@ class Engine:
         """Multi-Krum over the collected rows: order[i] = arrival slot of the
         caller's row i (None: every row, in arrival order).  Returns (sel,
         scores, mean) as multikrum, indices into the caller's rows."""
-        if getattr(self, "_collect", None) is None:
-            raise ValueError("collect_finish without collect_begin")
-        if f is None:
-            raise ValueError("f is required")
-        _, d = self._collect
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.int64)
-            if n is None:
-                n = len(order)
-            if order.ndim != 1 or len(order) < n:
-                raise ValueError("order must list n arrival slots")
-        elif n is None:
-            n = self.collect_count()
-        n, f = int(n), int(f)
-        check(lib().bk_check_args(n, d, f))
-        m = n - f
-        sel = np.empty(m, dtype=np.int64)
+        _, d = self._collection("collect_finish")
+        order, n, f = self._order_arg(order, n, f)
+        sel, sc, mean = _outs(n, d, f, want_scores, want_mean)
         mo = ctypes.c_int64(0)
-        sc = np.empty(n, dtype=np.float64) if want_scores else None
-        mean = np.empty(d, dtype=np.float64) if want_mean else None
-        check(lib().bk_collect_finish(self._ctx, order.ctypes.data if order is not None else None,
-                                      n, f, sel.ctypes.data, ctypes.addressof(mo),
-                                      sc.ctypes.data if sc is not None else None,
-                                      mean.ctypes.data if mean is not None else None))
-        assert mo.value == m
+        check(lib().bk_collect_finish(self._ctx, _ptr(order), n, f, sel.ctypes.data,
+                                      ctypes.addressof(mo), _ptr(sc), _ptr(mean)))
+        assert mo.value == n - f
         return sel, sc, mean
 
     def collect_add_finish(self, row, order=None, n=None, f=None, want_scores=True,
@@ -337,35 +371,13 @@ class Engine:
         BK_HOST_PINNED when row is a view of pinned memory (a pageable row of
         more than 32 KiB takes the two calls inside the entry: no faster fused).
         Returns (slot, sel, scores, mean)."""
-        if getattr(self, "_collect", None) is None:
-            raise ValueError("collect_add_finish without collect_begin")
-        dt, d = self._collect
-        a = np.asarray(row)
-        if a.dtype != dt or a.ndim != 1 or a.shape[0] != d:
-            raise ValueError("the row must be a 1-D %s array of length %d" % (dt, d))
-        if not a.flags.c_contiguous:
-            a = np.ascontiguousarray(a)
-        if f is None:
-            raise ValueError("f is required")
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.int64)
-            if n is None:
-                n = len(order)
-            if order.ndim != 1 or len(order) < n:
-                raise ValueError("order must list n arrival slots")
-        elif n is None:
-            n = self.collect_count() + 1
-        n, f = int(n), int(f)
-        check(lib().bk_check_args(n, d, f))
-        m = n - f
-        sel = np.empty(m, dtype=np.int64)
-        sc = np.empty(n, dtype=np.float64) if want_scores else None
-        mean = np.empty(d, dtype=np.float64) if want_mean else None
-        slot, mo = self.collect_add_finish_ptr(
-            a.ctypes.data, where, order.ctypes.data if order is not None else None, n, f,
-            sel.ctypes.data, sc.ctypes.data if sc is not None else None,
-            mean.ctypes.data if mean is not None else None)
-        assert mo == m
+        dt, d = self._collection("collect_add_finish")
+        a = _row(row, dt, d, "the row")
+        order, n, f = self._order_arg(order, n, f, extra=1)
+        sel, sc, mean = _outs(n, d, f, want_scores, want_mean)
+        slot, mo = self.collect_add_finish_ptr(a.ctypes.data, where, _ptr(order), n, f,
+                                               sel.ctypes.data, _ptr(sc), _ptr(mean))
+        assert mo == n - f
         return slot, sel, sc, mean
 
     def collect_add_finish_ptr(self, row_ptr, where, order_ptr, n, f, sel_ptr, scores_ptr=None,
@@ -387,46 +399,14 @@ class Engine:
         (noise None: k = 0, collect_add_finish on delta); order as
         collect_add_finish's; where: BK_HOST_PINNED when delta and noise are
         views of pinned memory.  Returns (slot, sel, scores, mean)."""
-        if getattr(self, "_collect", None) is None:
-            raise ValueError("collect_add_noised_finish without collect_begin")
-        dt, d = self._collect
-        if dt != np.float64:
-            raise ValueError("noise is float64 only: the collection is %s" % dt)
-        D = np.ascontiguousarray(delta, dtype=np.float64)
-        if D.ndim != 1 or D.shape[0] != d:
-            raise ValueError("delta must be a 1-D float64 array of length %d" % d)
-        if noise is None:
-            N = np.empty((0, d), dtype=np.float64)
-        else:
-            N = np.ascontiguousarray(noise, dtype=np.float64)
-            if N.ndim == 1:
-                N = N.reshape(1, -1)
-            if N.ndim != 2 or (N.shape[0] > 0 and N.shape[1] != d):
-                raise ValueError("noise must be None, a vector of length %d or a (k, %d) array"
-                                 % (d, d))
-        if f is None:
-            raise ValueError("f is required")
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.int64)
-            if n is None:
-                n = len(order)
-            if order.ndim != 1 or len(order) < n:
-                raise ValueError("order must list n arrival slots")
-        elif n is None:
-            n = self.collect_count() + 1
-        n, f = int(n), int(f)
-        check(lib().bk_check_args(n, d, f))
-        m = n - f
-        k = N.shape[0]
-        nz = (ctypes.c_void_p * k)(*[N[j].ctypes.data for j in range(k)]) if k else None
-        sel = np.empty(m, dtype=np.int64)
-        sc = np.empty(n, dtype=np.float64) if want_scores else None
-        mean = np.empty(d, dtype=np.float64) if want_mean else None
-        slot, mo = self.collect_add_noised_finish_ptr(
-            D.ctypes.data, nz, k, where, order.ctypes.data if order is not None else None, n, f,
-            sel.ctypes.data, sc.ctypes.data if sc is not None else None,
-            mean.ctypes.data if mean is not None else None)
-        assert mo == m
+        dt, d = self._collection("collect_add_noised_finish")
+        D, N, nz = _noise_arg(delta, noise, dt, d)
+        order, n, f = self._order_arg(order, n, f, extra=1)
+        sel, sc, mean = _outs(n, d, f, want_scores, want_mean)
+        slot, mo = self.collect_add_noised_finish_ptr(D.ctypes.data, nz, len(N), where,
+                                                      _ptr(order), n, f, sel.ctypes.data,
+                                                      _ptr(sc), _ptr(mean))
+        assert mo == n - f
         return slot, sel, sc, mean
 
     def collect_add_noised_finish_ptr(self, delta_ptr, noise_ptrs, k, where, order_ptr, n, f,
@@ -475,25 +455,17 @@ class Engine:
             raise ValueError("orders must be 2-D (B problems x n arrival slots)")
         if orders.dtype.kind not in "iu":
             raise ValueError("orders must be an integer array")
-        if getattr(self, "_collect", None) is None:
-            raise ValueError("collect_finish_batch without collect_begin")
+        _, d = self._collection("collect_finish_batch")
         orders = np.ascontiguousarray(orders, dtype=np.int64)
         B, n = orders.shape
         if B < 1:
             raise ValueError("need at least one problem (B=%d)" % B)
-        _, d = self._collect
         f = int(f)
-        check(lib().bk_check_args(n, d, f))
-        m = n - f
-        sel = np.empty((B, m), dtype=np.int64)
+        sel, sc, mean = _outs(n, d, f, want_scores, want_mean, batch=B)
         mo = ctypes.c_int64(0)
-        sc = np.empty((B, n), dtype=np.float64) if want_scores else None
-        mean = np.empty((B, d), dtype=np.float64) if want_mean else None
         check(lib().bk_collect_finish_batch(self._ctx, orders.ctypes.data, B, n, f, sel.ctypes.data,
-                                            ctypes.addressof(mo),
-                                            sc.ctypes.data if sc is not None else None,
-                                            mean.ctypes.data if mean is not None else None))
-        assert mo.value == m
+                                            ctypes.addressof(mo), _ptr(sc), _ptr(mean)))
+        assert mo.value == n - f
         return sel, sc, mean
 
     def collect_finish_ragged(self, orders, fs, want_scores=True, want_mean=True):
@@ -515,34 +487,17 @@ class Engine:
             if o.dtype.kind not in "iu":
                 raise ValueError("orders[%d] must be an integer array" % b)
         B = len(orders)
-        if np.ndim(fs) == 0:
-            fs = [int(fs)] * B
-        fs = np.ascontiguousarray(fs, dtype=np.int64)
-        if fs.ndim != 1 or fs.shape[0] != B:
-            raise ValueError("fs must be an int or one f per problem (%d problems)" % B)
-        if getattr(self, "_collect", None) is None:
-            raise ValueError("collect_finish_ragged without collect_begin")
-        _, d = self._collect
+        fs = _fs_arg(fs, B)
+        _, d = self._collection("collect_finish_ragged")
         ns = np.array([len(o) for o in orders], dtype=np.int64)
-        offsets = np.zeros(B + 1, dtype=np.int64)
-        np.cumsum(ns, out=offsets[1:])
+        offsets = _offsets(ns)
         packed = np.ascontiguousarray(np.concatenate(orders), dtype=np.int64)
-        # room for every problem even where a check below would refuse the call
-        ms = np.maximum(ns - fs, 0)
-        sel = np.empty(max(int(ms.sum()), 1), dtype=np.int64)
-        mo = np.zeros(B, dtype=np.int64)
-        sc = np.empty(max(int(offsets[B]), 1), dtype=np.float64) if want_scores else None
-        mean = np.empty((B, d), dtype=np.float64) if want_mean else None
+        sel, mo, sc, mean = _ragged_outs(ns, fs, d, want_scores, want_mean)
         check(lib().bk_collect_finish_ragged(self._ctx, packed.ctypes.data, offsets.ctypes.data,
                                              fs.ctypes.data, B, sel.ctypes.data, mo.ctypes.data,
-                                             sc.ctypes.data if sc is not None else None,
-                                             mean.ctypes.data if mean is not None else None))
+                                             _ptr(sc), _ptr(mean)))
         assert np.array_equal(mo, ns - fs)
-        so = np.zeros(B + 1, dtype=np.int64)
-        np.cumsum(mo, out=so[1:])
-        sels = [sel[so[b]:so[b + 1]].copy() for b in range(B)]
-        scs = [sc[offsets[b]:offsets[b + 1]].copy() for b in range(B)] if want_scores else None
-        return sels, scs, mean
+        return _ragged_unpack(sel, mo, sc, offsets) + (mean,)
 
     # ---- host entry with the noise applied in the H2D staging -----------
     #      (bk_multikrum_noised) -------------------
@@ -563,20 +518,14 @@ class Engine:
             raise ValueError("noise must be (n, k, d) matching delta (n, d)")
         k = N.shape[1]
         f = int(f)
-        check(lib().bk_check_args(n, d, f))
-        m = n - f
-        sel = np.empty(m, dtype=np.int64)
+        sel, sc, mean = _outs(n, d, f, want_scores, want_mean)
         mo = ctypes.c_int64(0)
-        sc = np.empty(n, dtype=np.float64) if want_scores else None
-        mean = np.empty(d, dtype=np.float64) if want_mean else None
         out = np.empty((n, d), dtype=np.float64) if want_noised else None
         check(lib().bk_multikrum_noised(self._ctx, D.ctypes.data, D.strides[0] // 8,
                                         N.ctypes.data if k else None, k, d, _lib.BK_HOST, n, d,
-                                        f, sel.ctypes.data, ctypes.addressof(mo),
-                                        sc.ctypes.data if sc is not None else None,
-                                        mean.ctypes.data if mean is not None else None,
-                                        out.ctypes.data if out is not None else None, d))
-        assert mo.value == m
+                                        f, sel.ctypes.data, ctypes.addressof(mo), _ptr(sc),
+                                        _ptr(mean), _ptr(out), d))
+        assert mo.value == n - f
         return sel, sc, mean, out
 
     def multikrum_noised_ptr(self, delta_ptr, ld, noise_ptr, k, noise_ld, where, n, d, f,
@@ -619,19 +568,13 @@ class Engine:
         ld = X.strides[1] // it
         stride = X.strides[0] // it
         f = int(f)
-        check(lib().bk_check_args(n, d, f))
-        m = n - f
-        sel = np.empty((B, m), dtype=np.int64)
+        sel, sc, mean = _outs(n, d, f, want_scores, want_mean, batch=B)
         mo = ctypes.c_int64(0)
-        sc = np.empty((B, n), dtype=np.float64) if want_scores else None
-        mean = np.empty((B, d), dtype=np.float64) if want_mean else None
-        dt = _lib.BK_F32 if X.dtype == np.float32 else _lib.BK_F64
         check(lib().bk_multikrum_batch(self._ctx, X.ctypes.data,
-                                       _lib.BK_HOST_PINNED if pinned else _lib.BK_HOST, dt, B, n,
-                                       d, ld, stride, f, sel.ctypes.data, ctypes.addressof(mo),
-                                       sc.ctypes.data if sc is not None else None,
-                                       mean.ctypes.data if mean is not None else None))
-        assert mo.value == m
+                                       _lib.BK_HOST_PINNED if pinned else _lib.BK_HOST,
+                                       _dtype_code(X.dtype), B, n, d, ld, stride, f,
+                                       sel.ctypes.data, ctypes.addressof(mo), _ptr(sc), _ptr(mean)))
+        assert mo.value == n - f
         return sel, sc, mean
 
     def multikrum_batch_device_ptr(self, x_ptr, dtype, batch, n, d, ld, stride, f, sel_ptr,
@@ -670,14 +613,9 @@ class Engine:
                 raise ValueError("problems[%d] is %s, problems[0] is %s: the problems share a dtype"
                                  % (b, x.dtype, dtype))
         B = len(problems)
-        if np.ndim(fs) == 0:
-            fs = [int(fs)] * B
-        fs = np.ascontiguousarray(fs, dtype=np.int64)
-        if fs.ndim != 1 or fs.shape[0] != B:
-            raise ValueError("fs must be an int or one f per problem (%d problems)" % B)
+        fs = _fs_arg(fs, B)
         ns = np.array([x.shape[0] for x in problems], dtype=np.int64)
-        offsets = np.zeros(B + 1, dtype=np.int64)
-        np.cumsum(ns, out=offsets[1:])
+        offsets = _offsets(ns)
         it = dtype.itemsize
         packed = all(x.flags.c_contiguous for x in problems) and all(
             problems[b + 1].ctypes.data == problems[b].ctypes.data + int(ns[b]) * d * it
@@ -688,25 +626,15 @@ class Engine:
             X = np.concatenate(problems, axis=0) if offsets[B] else np.empty((0, d), dtype=dtype)
             X = np.ascontiguousarray(X)
             x_ptr, pinned = X.ctypes.data, False
-        # room for every problem even where a check below would refuse the call
-        ms = np.maximum(ns - fs, 0)
-        sel = np.empty(max(int(ms.sum()), 1), dtype=np.int64)
-        mo = np.zeros(B, dtype=np.int64)
-        sc = np.empty(max(int(offsets[B]), 1), dtype=np.float64) if want_scores else None
-        mean = np.empty((B, max(d, 1)), dtype=np.float64) if want_mean else None
-        dt = _lib.BK_F32 if dtype == np.float32 else _lib.BK_F64
+        sel, mo, sc, mean = _ragged_outs(ns, fs, d, want_scores, want_mean)
         check(lib().bk_multikrum_ragged(self._ctx, x_ptr,
-                                        _lib.BK_HOST_PINNED if pinned else _lib.BK_HOST, dt, B,
-                                        offsets.ctypes.data, fs.ctypes.data, d, d, sel.ctypes.data,
-                                        mo.ctypes.data,
-                                        sc.ctypes.data if sc is not None else None,
-                                        mean.ctypes.data if mean is not None else None))
+                                        _lib.BK_HOST_PINNED if pinned else _lib.BK_HOST,
+                                        _dtype_code(dtype), B, offsets.ctypes.data, fs.ctypes.data,
+                                        d, d, sel.ctypes.data, mo.ctypes.data, _ptr(sc), _ptr(mean)))
         assert np.array_equal(mo, ns - fs)
-        so = np.zeros(B + 1, dtype=np.int64)
-        np.cumsum(mo, out=so[1:])
-        return [(sel[so[b]:so[b + 1]].copy(),
-                 sc[offsets[b]:offsets[b + 1]].copy() if want_scores else None,
-                 mean[b].copy() if want_mean else None) for b in range(B)]
+        sels, scs = _ragged_unpack(sel, mo, sc, offsets)
+        return [(sels[b], scs[b] if want_scores else None, mean[b].copy() if want_mean else None)
+                for b in range(B)]
 
     def multikrum_ragged_device_ptr(self, x_ptr, dtype, offsets, fs, d, ld, sel_ptr,
                                     scores_ptr=None, mean_ptr=None):
@@ -753,8 +681,7 @@ class Engine:
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         if global_w.dtype != np.float64 or not global_w.flags.c_contiguous or global_w.shape != (d,):
             raise ValueError("global_w must be a C-contiguous float64 vector of length d")
-        dt = _lib.BK_F32 if X.dtype == np.float32 else _lib.BK_F64
-        check(lib().bk_aggregate(self._ctx, X.ctypes.data, _lib.BK_HOST, dt, n, d,
+        check(lib().bk_aggregate(self._ctx, X.ctypes.data, _lib.BK_HOST, _dtype_code(X.dtype), n, d,
                                  X.strides[0] // X.itemsize, idx.ctypes.data, len(idx),
                                  global_w.ctypes.data))
         return global_w
@@ -784,8 +711,8 @@ class Engine:
         """global_w by raw pointer: pageable, pinned or device memory (d doubles)."""
         dt = np.dtype(dtype)
         p = -1 if precision is None else int(precision)
-        check(lib().bk_block_begin(self._ctx, _lib.BK_F32 if dt == np.float32 else _lib.BK_F64,
-                                   int(d), _p(global_ptr), int(where), p))
+        check(lib().bk_block_begin(self._ctx, _dtype_code(dt), int(d), _p(global_ptr), int(where),
+                                   p))
         self._block = (dt, int(d), p)
 
     def _block_state(self, who):
@@ -793,12 +720,6 @@ class Engine:
         if st is None:
             raise ValueError("%s without block_begin" % who)
         return st
-
-    def _block_row(self, r, dt, d):
-        a = np.asarray(r)
-        if a.dtype != dt or a.ndim != 1 or a.shape[0] != d:
-            raise ValueError("every row must be a 1-D %s array of length %d" % (dt, d))
-        return a if a.flags.c_contiguous else np.ascontiguousarray(a)
 
     def block_add(self, rows, accepted=None):
         """One 1-D array, or a sequence of them: host rows of the block's dtype
@@ -816,9 +737,8 @@ class Engine:
                 raise ValueError("accepted must have one flag per row")
         dummy = np.zeros(1, dtype=dt)
         keep = [dummy if (r is None and accepted is not None and not acc[i])
-                else self._block_row(r, dt, d) for i, r in enumerate(rows)]
-        ptrs = (ctypes.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
-        return self.block_add_ptr(ptrs, len(keep), _lib.BK_HOST,
+                else _row(r, dt, d) for i, r in enumerate(rows)]
+        return self.block_add_ptr(_ptr_array(keep), len(keep), _lib.BK_HOST,
                                   acc.ctypes.data if accepted is not None else None)
 
     def block_add_ptr(self, row_ptrs, count, where, accepted_ptr=None):
@@ -848,8 +768,7 @@ class Engine:
         (gradient, int64 sum, float sum)."""
         _, d, p = self._block_state("block_finish")
         g, q, qf = self._block_outs(want_qsum, p, d)
-        self.block_finish_ptr(g.ctypes.data, q.ctypes.data if want_qsum else None,
-                              qf.ctypes.data if want_qsum else None)
+        self.block_finish_ptr(g.ctypes.data, _ptr(q), _ptr(qf))
         return (g, q, qf) if want_qsum else g
 
     def block_finish_ptr(self, global_ptr, qsum_ptr=None, qsum_float_ptr=None):
@@ -861,11 +780,10 @@ class Engine:
         block_add(row, accepted) followed by block_finish, bitwise.  Returns
         (slot, gradient) or (slot, gradient, int64 sum, float sum)."""
         dt, d, p = self._block_state("block_add_finish")
-        a = self._block_row(row, dt, d)
+        a = _row(row, dt, d)
         g, q, qf = self._block_outs(want_qsum, p, d)
         slot = self.block_add_finish_ptr(a.ctypes.data, accepted, _lib.BK_HOST, g.ctypes.data,
-                                         q.ctypes.data if want_qsum else None,
-                                         qf.ctypes.data if want_qsum else None)
+                                         _ptr(q), _ptr(qf))
         return (slot, g, q, qf) if want_qsum else (slot, g)
 
     def block_add_finish_ptr(self, row_ptr, accepted, where, global_ptr, qsum_ptr=None,
