@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "bk_device.h"
 #include "bk_internal.h"
 
@@ -423,12 +425,43 @@ __device__ __forceinline__ void off_mma_gran(typename G3T<T>::acc (&acc)[4][4],
 #else
 #define G3_PROBE(v) const long long v = 0
 #endif
+// The glds split (g3_wave): of the 8 NB glds that stage one k-block, waves 0-3
+// issue NB + ESPL each and the staggered waves 4-7 NB - ESPL, down to none
+// (BK_GLDS_E6 <= 6 for the super pairs' NB = 6, BK_GLDS_E4 <= 4 for the band
+// quads' NB = 4).  BK_GLDS_SPREAD = 1: waves 0-3 issue theirs one per
+// ceil(MFMAs / glds) MFMAs through the k-block instead of in one burst.
+// -DBK_GLDS_E6=2 -DBK_GLDS_E4=2 -DBK_GLDS_SPREAD=0 is the r1-r21 kernel.
+#ifndef BK_GLDS_E6
+#define BK_GLDS_E6 2
+#endif
+#ifndef BK_GLDS_E4
+#define BK_GLDS_E4 2
+#endif
+#ifndef BK_GLDS_SPREAD
+#define BK_GLDS_SPREAD 1
+#endif
+#ifndef G3_STAGGER
+#define G3_STAGGER 1
+#endif
+#if defined(BK_K1_NOHIGLDS) && !defined(BK_PROBES)
+#error "BK_K1_NOHIGLDS is a timing-only ablation (wrong results): probe builds only"
+#endif
+// the split follows the stagger: the fp32-MFMA kernel (and a G3_STAGGER = 0
+// build) runs unstaggered, so its waves split evenly (the uneven split put the
+// fp32 MFMA's band quads' loop at 0.65, even 0.905)
+template <typename T, int NB>
+__device__ __forceinline__ constexpr int g3_espl() {
+    return (G3T<T>::F32C || !G3_STAGGER) ? 0 : NB == 6 ? BK_GLDS_E6 : NB == 4 ? BK_GLDS_E4 : 0;
+}
 // NB > 0: the group stages exactly NB row-blocks (compile time: a single
 // s_waitcnt and straight-line glds); NB = 0: read G.nb at run time.
 // XT (balanced band quads, GroupDesc::xt): OFF 1 / 2 = also block (0,3) of the
 // A / B row-block's diagonal tile, stored into xout (the PAIR wave's slab);
 // PAIR 1 = skip that block in both diagonal tiles
-template <typename T, int KIND, int MODE, bool STAG, int NB, int XT = 0>
+// HI: one of waves 4-7, known at compile time wherever the glds split is
+// uneven (g3_espl != 0; g3_dispatch), so that each wave class carries only its
+// own glds table
+template <typename T, int KIND, int MODE, bool STAG, int NB, int XT = 0, bool HI = STAG>
 __device__ __forceinline__ void g3_wave(const T *__restrict__ X, int64_t ld, int n, int nfull,
                                         int64_t d, const GroupDesc &G, const int *wd, char *lds,
                                         int wave, int lane, double *out, long long (&probe)[2],
@@ -457,31 +490,26 @@ __device__ __forceinline__ void g3_wave(const T *__restrict__ X, int64_t ld, int
     // latter are the critical path, and each glds costs its wave ~100-185
     // cycles of issue.  Super pairs 6 -> 8 / 4, quads 4 -> 6 / 2: K1 at D
     // 4.07 -> 4.00 ms, the 8-GPU shard and C unchanged (profiles/r01/ab_gldssplit.log);
-    // -DBK_GLDS_E6=0 -DBK_GLDS_E4=0 restores the even split.
-#ifndef BK_GLDS_E6
-#define BK_GLDS_E6 2
-#endif
-#ifndef BK_GLDS_E4
-#define BK_GLDS_E4 2
-#endif
-    // the fp32-MFMA kernel runs unstaggered, so its waves split evenly (the
-    // uneven split put the band quads' loop at 0.65 there, even 0.905)
-    constexpr int ESPL = G3T<T>::F32C ? 0 : NB == 6 ? BK_GLDS_E6 : NB == 4 ? BK_GLDS_E4 : 0;
+    // -DBK_GLDS_E6=0 -DBK_GLDS_E4=0 restores the even split.  Which wave issues
+    // instruction i never changes the bytes it moves: the LDS image is the same
+    // for every split.
+    constexpr int ESPL = g3_espl<T, NB>();
     constexpr int CLO = NB + ESPL, CHI = NB - ESPL;
-    constexpr int GMAX = G3_MAXB + 2;
-    static_assert(CLO <= GMAX && CHI >= 0, "glds split exceeds the per-wave pointer table");
-    const bool hi = wave >= 4;
+    // this wave's glds per k-block and its table size (uneven split: its class's)
+    constexpr int CNT = ESPL != 0 ? (HI ? CHI : CLO) : NB;
+    constexpr int GMAX = ESPL != 0 ? (CNT > 0 ? CNT : 1) : G3_MAXB;
+    static_assert(ESPL >= 0 && CHI >= 0 && 4 * CLO + 4 * CHI == 8 * NB,
+                  "the two wave classes' glds must add up to the stage's 8 NB");
     const T *gsrc[GMAX];
     int gdst[GMAX];
     {
         const int rq = lane >> 3, j = lane & 7;
 #pragma unroll
         for (int m = 0; m < GMAX; ++m) {
+            // waves 0-3 take instructions 0 .. 4 CLO - 1, waves 4-7 the rest
             int i = wave + 8 * m;
-            if constexpr (ESPL != 0) {
-                i = hi ? 4 * CLO + (wave - 4) + 4 * m : wave + 4 * m;
-                if (i >= 8 * NB) i = 0;  // beyond this wave's count: never issued
-            }
+            if constexpr (ESPL != 0) i = HI ? 4 * CLO + (wave - 4) + 4 * m : wave + 4 * m;
+            if (i >= 8 * G3_MAXB) i = 0;  // a wave with no glds (CNT = 0): never issued
             const int b = i >> 3, ii = i & 7;
             const int rl = ii * 8 + rq;
 #ifdef BK_K1_SAMEROWS  // timing-only ablation: every slot reads row-block 0 (all L2 hits)
@@ -504,17 +532,10 @@ __device__ __forceinline__ void g3_wave(const T *__restrict__ X, int64_t ld, int
 #define BK_K1_GLDS_LIMIT G3_MAXB
 #endif
         if constexpr (ESPL != 0) {
-            if (hi) {
 #pragma unroll
-                for (int m = 0; m < CHI; ++m)
-                    __builtin_amdgcn_global_load_lds((const void *)(gsrc[m] + col),
-                                                     (void *)(base + gdst[m]), 16, 0, 0);
-            } else {
-#pragma unroll
-                for (int m = 0; m < CLO; ++m)
-                    __builtin_amdgcn_global_load_lds((const void *)(gsrc[m] + col),
-                                                     (void *)(base + gdst[m]), 16, 0, 0);
-            }
+            for (int m = 0; m < CNT; ++m)
+                __builtin_amdgcn_global_load_lds((const void *)(gsrc[m] + col),
+                                                 (void *)(base + gdst[m]), 16, 0, 0);
             return;
         }
 #pragma unroll
@@ -546,89 +567,30 @@ __device__ __forceinline__ void g3_wave(const T *__restrict__ X, int64_t ld, int
 #pragma unroll
     for (int s = 0; s < G3_STAGES - 1; ++s)
         if (s < nk && MODE != 2) issue(kst + (int64_t)s * kstr, s);
-    int buf = 0;
-    for (int t = 0; t < nk; ++t) {
-        const int ahead = min(nk - t - 1, G3_STAGES - 2);  // stages issued after t
-        G3_PROBE(p0);
-        if constexpr (NB > 0 && MODE != 2 && ESPL != 0) {
-            if (ahead > 0) {
-                if (hi)
-                    g3_waitc<CHI>();
-                else
-                    g3_waitc<CLO>();
-            } else {
-                g3_waitc<0>();
-            }
-        } else if constexpr (NB > 0 && MODE != 2) {
-            if (ahead > 0)
-                g3_waitc<(NB < BK_K1_GLDS_LIMIT ? NB : BK_K1_GLDS_LIMIT)>();
-            else
-                g3_waitc<0>();
-        } else {
-            g3_wait(MODE == 2 ? 0 : ahead * c);
+#ifdef BK_K1_NOHIGLDS  // timing-only ablation: waves 4-7 stage nothing after the prologue
+    constexpr bool NOHI = HI && ESPL != 0;
+#else
+    constexpr bool NOHI = false;
+#endif
+    // every glds of stage t + 2 is issued after barrier t and before the wait of
+    // k-block t + 1, which leaves exactly that stage's CNT outstanding
+    constexpr int WCNT = NOHI ? 0 : CNT;
+    // SPR: waves 0-3 spread their glds through the k-block's MFMAs.  That
+    // needs the k-block in one basic block, so the k-blocks that still stage
+    // (STEADY: t + 2 < nk, no run-time "more") are peeled from the last two.
+    // fp64 rows only: on widened fp32 rows the spread order keeps the converted
+    // operands alive across the glds and spills (664 B of scratch per lane)
+    constexpr bool SPR = BK_GLDS_SPREAD && ESPL != 0 && MODE == 0 && std::is_same<T, double>::value;
+    int buf = 0, t = 0;
+    if constexpr (SPR) {
+        for (; t + G3_STAGES - 1 < nk; ++t) {
+            constexpr bool STEADY = true;
+#include "bk_gram_kblock.inc"
         }
-        G3_PROBE(p1);
-        g3_barrier();
-        G3_PROBE(p2);
-        probe[0] += p1 - p0;
-        probe[1] += p2 - p1;
-        const char *ls = lds + buf * G3_STAGE;
-        const int nbuf = buf == 0 ? G3_STAGES - 1 : buf - 1;  // (t + STAGES - 1) % STAGES
-        const bool more = t + G3_STAGES - 1 < nk && MODE != 2;
-        const int64_t nkb = kst + (int64_t)(t + G3_STAGES - 1) * kstr;
-        buf = buf == G3_STAGES - 1 ? 0 : buf + 1;
-        if constexpr (MODE == 1) {
-            if (more) issue(nkb, nbuf);
-            continue;
-        }
-        if constexpr (KIND == T_OFF) {
-            gran a0[4], b0[4], a1[4], b1[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a0[q] = g3_frag<T>(ls + sA * G3_BLK, q, 0, rr, g);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) b0[q] = g3_frag<T>(ls + sB * G3_BLK, q, 0, rr, g);
-            if constexpr (STAG) {
-                if (t > 0) off_mma_gran<T, XO>(acc.a, ha, hb, xacc);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a1[q] = g3_frag<T>(ls + sA * G3_BLK, q, 1, rr, g);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) b1[q] = g3_frag<T>(ls + sB * G3_BLK, q, 1, rr, g);
-            if (more) issue(nkb, nbuf);
-            off_mma_gran<T, XO>(acc.a, a0, b0, xacc);
-            if constexpr (STAG) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    ha[q] = a1[q];
-                    hb[q] = b1[q];
-                }
-            } else {
-                off_mma_gran<T, XO>(acc.a, a1, b1, xacc);
-            }
-        } else if constexpr (KIND == T_PAIR) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                gran a[4], b[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) a[q] = g3_frag<T>(ls + sA * G3_BLK, q, h, rr, g);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) b[q] = g3_frag<T>(ls + sB * G3_BLK, q, h, rr, g);
-                if (h == 0 && more) issue(nkb, nbuf);
-                diag_mma_g<T, XP>(acc.a, a);
-                diag_mma_g<T, XP>(acc.b, b);
-            }
-        } else if constexpr (KIND == T_DIAG1) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                gran a[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) a[q] = g3_frag<T>(ls + sA * G3_BLK, q, h, rr, g);
-                if (h == 0 && more) issue(nkb, nbuf);
-                diag_mma_g<T>(acc.a, a);
-            }
-        } else {
-            if (more) issue(nkb, nbuf);
-        }
+    }
+    for (; t < nk; ++t) {
+        constexpr bool STEADY = false;
+#include "bk_gram_kblock.inc"
     }
     if constexpr (KIND == T_OFF && STAG && MODE != 1)
         if (nk > 0) off_mma_gran<T, XO>(acc.a, ha, hb, xacc);
@@ -674,9 +636,6 @@ __device__ __forceinline__ void g3_wave(const T *__restrict__ X, int64_t ld, int
     }
 }
 
-#ifndef G3_STAGGER
-#define G3_STAGGER 1
-#endif
 template <typename T, int MODE, int NB>
 __device__ __forceinline__ void g3_dispatch(const T *__restrict__ X, int64_t ld, int n,
                                             int nfull, int64_t d, const GroupDesc &G,
@@ -685,6 +644,9 @@ __device__ __forceinline__ void g3_dispatch(const T *__restrict__ X, int64_t ld,
     // the balanced quads always stage 4 row-blocks: only NB = 4 (and the
     // run-time NB = 0 of the ablation modes) carries the XT variants
     const int xt = (NB == 4 || NB == 0) ? G.xt[wave] : 0;
+    // an uneven glds split: the wave's class (0-3 / 4-7) is a template argument.
+    // It follows the stagger, so an OFF wave's class is its STAG
+    constexpr bool SPLIT = g3_espl<T, NB>() != 0;
     double *xout = out - (int64_t)wave * 2 * 4096 + (int64_t)G.xslot[wave] * 4096;
     switch (G.task[wave][0]) {
     case T_OFF:
@@ -711,16 +673,29 @@ __device__ __forceinline__ void g3_dispatch(const T *__restrict__ X, int64_t ld,
         }
         break;
     case T_PAIR:
-        if (xt)
-            g3_wave<T, T_PAIR, MODE, false, NB, (NB == 4 || NB == 0) ? 1 : 0>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
-        else
-            g3_wave<T, T_PAIR, MODE, false, NB>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
+        if (SPLIT && wave >= 4) {
+            if (xt)
+                g3_wave<T, T_PAIR, MODE, false, NB, (NB == 4 || NB == 0) ? 1 : 0, SPLIT>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
+            else
+                g3_wave<T, T_PAIR, MODE, false, NB, 0, SPLIT>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
+        } else {
+            if (xt)
+                g3_wave<T, T_PAIR, MODE, false, NB, (NB == 4 || NB == 0) ? 1 : 0>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
+            else
+                g3_wave<T, T_PAIR, MODE, false, NB>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
+        }
         break;
     case T_DIAG1:
-        g3_wave<T, T_DIAG1, MODE, false, NB>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
+        if (SPLIT && wave >= 4)
+            g3_wave<T, T_DIAG1, MODE, false, NB, 0, SPLIT>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
+        else
+            g3_wave<T, T_DIAG1, MODE, false, NB>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
         break;
     default:
-        g3_wave<T, T_NONE, MODE, false, NB>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
+        if (SPLIT && wave >= 4)
+            g3_wave<T, T_NONE, MODE, false, NB, 0, SPLIT>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
+        else
+            g3_wave<T, T_NONE, MODE, false, NB>(X, ld, n, nfull, d, G, wd, lds, wave, lane, out, probe, nullptr, wt);
         break;
     }
 }
