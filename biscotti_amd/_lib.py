@@ -112,6 +112,9 @@ SIGNATURES = {
     "bk_comm_stats": (_i, [_p, _pi64, _pd]),
     "bk_set_small_path": (_i, [_p, _i]),
     "bk_set_collect_wide": (_i, [_p, _i]),
+    "bk_set_collect_wide_arrive": (_i, [_p, _i]),
+    "bk_collect_wide_arrive_item": (_i, [_i64, _i64, _i, _i64, _i, _i64, ctypes.POINTER(_i),
+                                         ctypes.POINTER(_i), ctypes.POINTER(_i), _pi64]),
     "bk_collect_begin": (_i, [_p, _i, _i64, _i64]),
     "bk_collect_add": (_i, [_p, _p, _i64, _i, _pi64]),
     "bk_collect_add_noised": (_i, [_p, _p, _p, _i64, _i64, _i, _pi64]),

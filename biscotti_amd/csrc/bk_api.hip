@@ -549,6 +549,13 @@ int bk_set_collect_wide(bk_ctx *c, int on) {
     return BK_OK;
 }
 
+int bk_set_collect_wide_arrive(bk_ctx *c, int on) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->collect_wide_arrive = on == 2 ? 2 : on ? 1 : 0;  // 2: every shape of the range
+    return BK_OK;
+}
+
 int bk_set_collect_tiny(bk_ctx *c, int on) {
     if (!c) return fail(BK_EINVAL, "null context");
     std::lock_guard<std::mutex> lk(c->mu);

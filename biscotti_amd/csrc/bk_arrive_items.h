@@ -4,7 +4,8 @@
 // of the one new row, the bits of k_border + k_border_reduce) and the S item's
 // Gram row with the new run handed off inside the launch.  The kernels' item
 // loops are NOT here: each kernel keeps its own, written out.
-// Private to those two files; in an unnamed namespace, as bk_collect_arrive.hip
+// k_collect_arrive_wide (bk_collect_arrive_wide.hip) takes the vector types and
+// arrive_row from here.  Private to those files; in an unnamed namespace, as bk_collect_arrive.hip
 // held them: the kernels keep internal linkage, and k_collect_arrive the code
 // and registers it had.
 #pragma once

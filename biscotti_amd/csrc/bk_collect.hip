@@ -31,6 +31,9 @@
 // k_collect_small's range with at most 128 rows collected it is the row's copy
 // and ONE launch, k_collect_arrive (bk_collect_arrive.hip): that row's border,
 // bit for bit k_border + k_border_reduce's, in front of k_collect_small's items.
+// With bk_set_collect_wide_arrive on (and the wide path) a pinned or device row
+// in k_collect_wide's range takes ONE launch too: k_collect_arrive_wide
+// (bk_collect_arrive_wide.hip), whose border partials meet in P.
 // bk_collect_add_noised_finish is that for an update that arrives as Delta and
 // Noise: the copies and ONE launch, k_collect_arrive_noised
 // (bk_collect_arrive_noised.hip), which noises the new row in front of the
@@ -78,6 +81,16 @@ constexpr size_t ARRIVE_HOST_MAX_BYTES = 32768;
 // (DESIGN 5o); nothing was measured in between.  Device rows are fused at
 // every d of the range
 constexpr size_t ARRIVE_NOISED_HOST_MAX_BYTES = 32768;
+// bk_set_collect_wide_arrive(ctx, 1): the fused wide launch is taken only for a
+// pinned row of at most this many bytes in a call that asks for the mean -- at
+// 100 x 40,000 fp64 that call's three runs were all below the sequence's (88.0
+// [87.5 .. 89.1] against 89.8 [89.4 .. 90.7] us); without the mean they
+// overlapped (51.0 [49.7 .. 53.7] against 55.3 [50.7 .. 55.8]), device rows were
+// level (40.6 against 39.7), and at 100 x 163,850 and 100 x 259,770 the fused
+// call was level or behind in every setting (fp64 device rows without the mean:
+// 58.3 against 54.3, 73.9 against 68.6 us).  Nothing was measured in
+// between.  on = 2 takes the launch in the whole range (tests, measurements)
+constexpr size_t ARRIVE_WIDE_MAX_BYTES = 320000;
 
 typedef double cd2 __attribute__((ext_vector_type(2)));
 typedef float cf4 __attribute__((ext_vector_type(4)));
@@ -773,21 +786,29 @@ int add_rows(bk_ctx *c, Collect *k, const void *const *rows, int64_t count, int 
 // the border of that slot in front of k_collect_small's items -- and the one
 // wait of finish_one_launch, behind which the row has been consumed.  The
 // collection counts the row only when all of it succeeded: after a failure the
-// next add rewrites the slot and its Gram run
+// next add rewrites the slot and its Gram run.  wide (bk_set_collect_wide_arrive;
+// a pinned or a device row, the finish wide_ok): the launch is
+// k_collect_arrive_wide, whose border partials meet in the collection's P
 int add_finish_fused(bk_ctx *c, Collect *k, const void *row, int where, int64_t *first_slot,
-                     const FinishArgs &a) {
+                     const FinishArgs &a, bool wide = false) {
     const hipStream_t st = c->stream;
     Drain drain{st};
     const size_t es = esize(k->dtype), bytes = (size_t)k->d * es;
     const int64_t j = k->count;
-    // (a row of the fused range is one ring slot: d <= 32,768; the stream is
-    // waited for below, or drained on a failure, before any later add)
+    // (a pageable row of the fused range is one ring slot: d <= 32,768; the
+    // stream is waited for below, or drained on a failure, before any later add)
     CHK(copy_row(k, (char *)k->store.p + (size_t)j * (size_t)k->ld * es, row, bytes, where, st,
                  false));
-    const auto launch = [j](const void *store, int dtype, int64_t ld, int n_, int64_t d, int f_,
-                            const double *G, const int64_t *ord, double *sc, double *diag,
-                            int64_t *sel, double *mean, double *margin, double *sc_out,
-                            unsigned *ctr, int num_cu, hipStream_t s, uint64_t spin, int lines) {
+    double *const P = (double *)k->P.p;
+    const auto launch = [j, wide, P](const void *store, int dtype, int64_t ld, int n_, int64_t d,
+                                     int f_, const double *G, const int64_t *ord, double *sc,
+                                     double *diag, int64_t *sel, double *mean, double *margin,
+                                     double *sc_out, unsigned *ctr, int num_cu, hipStream_t s,
+                                     uint64_t spin, int lines) {
+        if (wide)
+            return launch_collect_arrive_wide(store, dtype, ld, (int)j, n_, d, f_,
+                                              const_cast<double *>(G), P, ord, sc, diag, sel, mean,
+                                              margin, sc_out, ctr, num_cu, s, spin, lines);
         return launch_collect_arrive(store, dtype, ld, (int)j, n_, d, f_, const_cast<double *>(G),
                                      ord, sc, diag, sel, mean, margin, sc_out, ctr, num_cu, s, spin,
                                      lines);
@@ -896,6 +917,16 @@ int add_finish_checked(bk_ctx *c, Collect *k, const void *row, int where, int64_
     const bool long_host = where == BK_HOST && (size_t)k->d * esize(k->dtype) > ARRIVE_HOST_MAX_BYTES;
     if (k->count + 1 <= 128 && !long_host && small_ok(c, k->store.p, k->dtype, a.n, k->d, k->ld))
         return add_finish_fused(c, k, row, where, first_slot, a);
+    // the fused wide launch (bk_set_collect_wide_arrive): the finish in
+    // k_collect_wide's range, a border of at most 128 rows, a pinned or a device
+    // row (a pageable row this long is past ARRIVE_HOST_MAX_BYTES); with on = 1
+    // only where it was measured ahead (ARRIVE_WIDE_MAX_BYTES)
+    const bool wide_cut = c->collect_wide_arrive == 1 &&
+                          !(where == BK_HOST_PINNED && a.mean_out &&
+                            (size_t)k->d * esize(k->dtype) <= ARRIVE_WIDE_MAX_BYTES);
+    if (c->collect_wide_arrive && !wide_cut && k->count + 1 <= 128 && where != BK_HOST &&
+        wide_ok(c, a.n, k->d, a.mean_out != nullptr))
+        return add_finish_fused(c, k, row, where, first_slot, a, true);
     CHK(add_rows(c, k, &row, 1, where, first_slot));
     return finish_checked(c, k, a);
 }
@@ -1606,6 +1637,27 @@ int bk_collect_finish_ragged(bk_ctx *c, const int64_t *orders, const int64_t *of
     }
     DeviceGuard dg(c->device);
     return finish_ragged(c, k, orders, offsets, fs, batch, sel_idx, m_out, scores, mean_out);
+}
+
+int bk_collect_wide_arrive_item(int64_t rows, int64_t d, int dtype, int64_t n, int mean,
+                                int64_t item, int *kind, int *a, int *b, int64_t counts[4]) {
+    if (!kind || !a || !b || !counts) return fail(BK_EINVAL, "null kind / a / b / counts");
+    WideArriveQueue q;
+    if (!wide_arrive_queue(q, rows, d, dtype, n, mean != 0))
+        return fail(BK_EINVAL,
+                    "need 1 <= rows <= 128, 1 <= n <= 128, a dtype and at most %d chunks of a row "
+                    "(rows=%lld n=%lld d=%lld dtype=%d)",
+                    WIDE_ARRIVE_MAX_B, (long long)rows, (long long)n, (long long)d, dtype);
+    const int64_t total = (int64_t)q.nB + q.nR + q.nS + q.nM;
+    if (item < 0 || item >= total)
+        return fail(BK_EINVAL, "item %lld outside the queue (0..%lld)", (long long)item,
+                    (long long)total - 1);
+    counts[0] = q.nB;
+    counts[1] = q.nR;
+    counts[2] = q.nS;
+    counts[3] = q.nM;
+    wide_arrive_decode(q, (int)rows, (int)item, *kind, *a, *b);
+    return BK_OK;
 }
 
 int bk_ragged_queue_item(const int32_t *n, int W, int C, int64_t item, int *p, int *it) {

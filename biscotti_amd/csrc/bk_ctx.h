@@ -184,6 +184,7 @@ struct bk_ctx {
     int small_on = 1;
     int collect_wide = 0;  // bk_set_collect_wide: the wide one-launch collection finishes (opt-in)
     int collect_tiny = 0;  // bk_set_collect_tiny: the one-workgroup tiny collection (opt-in)
+    int collect_wide_arrive = 0;  // bk_set_collect_wide_arrive: the fused wide last arrival (opt-in)
     uint64_t small_spin_max = SMALL_SPIN_MAX;  // test knob BK_SMALL_SPIN_MAX=<polls>[,<launches>]
     int64_t small_spin_left = -1;              // ... for this many launches (-1: all)
     int small_check_lines = 0;                 // debug knob BK_SMALL_CHECK_LINES (bk_create)

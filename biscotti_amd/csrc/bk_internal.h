@@ -606,6 +606,77 @@ hipError_t launch_collect_wide_ragged(const void *store, int dtype, int64_t ld, 
                                       int64_t *sel, double *mean, double *margin, unsigned *lines,
                                       int num_cu, hipStream_t st,
                                       uint64_t spin_max = SMALL_SPIN_MAX);
+// bk_collect_arrive_wide.hip, k_collect_arrive_wide (bk_set_collect_wide_arrive):
+// the last arrival of a WIDE row at slot j <= 127 and k_collect_wide's finish
+// behind it, in one launch.  The queue numbers four kinds of item in dependency
+// order; an item waits only for items numbered before it:
+//   B  nB = S RB   chunk s of the new row against the resident rows of block rb
+//                  (rpb rows, one per wave and round): k_border's partials for
+//                  C = 1 -> P[s (j + 1) + i]
+//   R  nR          the chunk sum of WIDE_ARRIVE_NW elements i <= j, one wave
+//                  each: k_border_reduce's -> G[j (j + 1) / 2 + i]
+//   S  n           k_collect_wide's S items (run j of G read with sc1 loads)
+//   M  nM          k_collect_wide's M items (1 without a mean)
+// The B items arrive on G_GRP's 32 groups of 32, so nB <= 1,024: rpb is the
+// smallest multiple of the workgroup's waves that keeps S ceil(rows / rpb)
+// there -- the most items the lines count, for the grid's balance.
+constexpr int WIDE_ARRIVE_NW = 8;        // waves of a workgroup (SMALL_NW)
+constexpr int WIDE_ARRIVE_MAX_B = 1024;  // B items a launch may number
+enum { WIDE_ARRIVE_B = 0, WIDE_ARRIVE_R = 1, WIDE_ARRIVE_S = 2, WIDE_ARRIVE_M = 3 };
+struct WideArriveQueue {
+    int S, rpb, RB;       // chunks of a row; resident rows per B item; row blocks
+    int nB, nR, nS, nM;   // items of each kind, in queue order
+};
+// rows: the rows collected after the add (j + 1); false outside the range
+__host__ __device__ inline bool wide_arrive_queue(WideArriveQueue &q, int64_t rows, int64_t d,
+                                                  int dtype, int64_t n, bool mean) {
+    if (rows < 1 || rows > 128 || n < 1 || n > 128 || d < 1 || (dtype != 0 && dtype != 1))
+        return false;
+    const int64_t S = (d * (dtype == 0 ? 8 : 4) + COLLECT_BORDER_CHUNK_BYTES - 1) /
+                      COLLECT_BORDER_CHUNK_BYTES;
+    if (S > WIDE_ARRIVE_MAX_B) return false;
+    int rpb = WIDE_ARRIVE_NW;
+    while (S * ((rows + rpb - 1) / rpb) > WIDE_ARRIVE_MAX_B) rpb += WIDE_ARRIVE_NW;
+    q.S = (int)S;
+    q.rpb = rpb;
+    q.RB = (int)((rows + rpb - 1) / rpb);
+    q.nB = q.S * q.RB;
+    q.nR = (int)((rows + WIDE_ARRIVE_NW - 1) / WIDE_ARRIVE_NW);
+    q.nS = (int)n;
+    q.nM = mean ? (int)((d + COLLECT_WIDE_COLS - 1) / COLLECT_WIDE_COLS) : 1;
+    return true;
+}
+// item it of the queue -> its kind and (B: chunk a, row block b; R: first
+// element a, elements b; S: row a; M: mean item a).  Consecutive B items take
+// consecutive chunks of one row block: the workgroups that start together
+// stream neighbouring columns of the same rows
+__host__ __device__ inline void wide_arrive_decode(const WideArriveQueue &q, int rows, int it,
+                                                   int &kind, int &a, int &b) {
+    b = 0;
+    if (it < q.nB) {
+        kind = WIDE_ARRIVE_B;
+        a = it % q.S;
+        b = it / q.S;
+    } else if (it < q.nB + q.nR) {
+        kind = WIDE_ARRIVE_R;
+        a = (it - q.nB) * WIDE_ARRIVE_NW;
+        b = rows - a < WIDE_ARRIVE_NW ? rows - a : WIDE_ARRIVE_NW;
+    } else if (it < q.nB + q.nR + q.nS) {
+        kind = WIDE_ARRIVE_S;
+        a = it - q.nB - q.nR;
+    } else {
+        kind = WIDE_ARRIVE_M;
+        a = it - q.nB - q.nR - q.nS;
+    }
+}
+// P: the collection's partials buffer, S (j + 1) doubles at least; the other
+// arguments are launch_collect_arrive's
+hipError_t launch_collect_arrive_wide(const void *store, int dtype, int64_t ld, int j, int n,
+                                      int64_t d, int f, double *G, double *P, const int64_t *order,
+                                      double *scores, double *diag, int64_t *sel, double *mean,
+                                      double *margin, double *scores_out, unsigned *ctr, int num_cu,
+                                      hipStream_t st, uint64_t spin_max = SMALL_SPIN_MAX,
+                                      int check_lines = 0);
 hipError_t launch_synth(void *X, int dtype, int64_t ld, int64_t n, int64_t dl, int64_t c0,
                         const int64_t *perm, const SynthParams &P, hipStream_t st);
 // bk_collect_noise.hip, k_collect_noise (bk_collect_add_noised): one launch adds

@@ -3,7 +3,7 @@
 // the queue words and the hand-off code are bk_small_items.h's, unchanged; an M
 // item here owns COLLECT_WIDE_COLS columns and streams the selected rows from
 // the row store instead of staging every row's 64 columns in LDS.  Private to
-// bk_collect_wide.hip.
+// bk_collect_wide.hip and bk_collect_arrive_wide.hip (k_collect_arrive_wide).
 #pragma once
 #include "bk_small_items.h"
 

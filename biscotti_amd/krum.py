@@ -865,6 +865,16 @@ class Engine:
         are bitwise the chain's."""
         check(lib().bk_set_collect_wide(self._ctx, 1 if on else 0))
 
+    def set_collect_wide_arrive(self, on=True, everywhere=False):
+        """opt-in (default off; needs set_collect_wide): collect_add_finish of a
+        pinned or a device row whose finish is in the wide one-launch range is
+        the row's copy and one launch, k_collect_arrive_wide
+        (bk_set_collect_wide_arrive); the outputs are bitwise the two calls'.
+        on alone takes the launch only where it was measured ahead (a pinned
+        row of at most 320,000 bytes with the mean); everywhere=True in the
+        whole range."""
+        check(lib().bk_set_collect_wide_arrive(self._ctx, (2 if everywhere else 1) if on else 0))
+
     def certified_reruns(self):
         return int(lib().bk_certified_reruns(self._ctx))
 
@@ -1045,7 +1055,8 @@ class KRUMValidator:
     """DistSys/krum.go:22-29, with getTopKRUMIndex running on libbk."""
 
     def __init__(self, num_adversaries=0.5, engine: Optional[Engine] = None, device=0,
-                 collect=False, n_cap=128, wide=False, noised=False, tiny=False):
+                 collect=False, n_cap=128, wide=False, noised=False, tiny=False,
+                 wide_arrive=False):
         """collect=True (opt-in): add_update streams each update's NoisedDelta
         to the engine's collection as it arrives (bk_collect_add), and
         compute_scores only finishes (bk_collect_finish) in SourceID order;
@@ -1058,7 +1069,12 @@ class KRUMValidator:
         the host; noised_delta(i) reads it back from the row store when asked.
         tiny=True (with collect, with or without noised) turns the engine's
         one-workgroup tiny collection on when the round begins
-        (Engine.set_collect_tiny: creditcard's d, at most 16 updates)."""
+        (Engine.set_collect_tiny: creditcard's d, at most 16 updates).
+        wide_arrive=True (with collect and wide) turns the fused wide last
+        arrival on as well (Engine.set_collect_wide_arrive): add_update(u,
+        last=True) hands a row of more than 32 KiB over through pinned staging
+        (bk_stage_alloc, as the cgo shim packs Go's rows), so that the copy and
+        k_collect_arrive_wide are the whole call."""
         self.UpdateList: List[Update] = []
         self.AcceptedList: List[int] = []
         self.NumAdversaries = num_adversaries  # fixed at 0.5 (main.go:783)
@@ -1069,10 +1085,13 @@ class KRUMValidator:
         self._wide = bool(wide)
         self._noised = bool(noised)
         self._tiny = bool(tiny)
+        self._wide_arrive = bool(wide_arrive)
         if self._noised and not self._collect:
             raise ValueError("noised=True needs collect=True")
         if self._tiny and not self._collect:
             raise ValueError("tiny=True needs collect=True")
+        if self._wide_arrive and not (self._collect and self._wide):
+            raise ValueError("wide_arrive=True needs collect=True and wide=True")
         self._slots: List[int] = []  # collect mode: arrival slot of UpdateList[i]
 
     def initialize(self):
@@ -1106,6 +1125,8 @@ class KRUMValidator:
                 slot, sel, _, _ = self._engine.collect_add_noised_finish(
                     row, update.Noise, order=order, n=n, f=clip, want_scores=False,
                     want_mean=False)
+            elif self._wide_arrive and row.nbytes > 32768:
+                slot, sel = self._last_pinned(row, order, n, clip)
             else:
                 slot, sel, _, _ = self._engine.collect_add_finish(
                     row, order=order, n=n, f=clip, want_scores=False, want_mean=False)
@@ -1128,12 +1149,30 @@ class KRUMValidator:
                     self._engine.set_collect_wide(True)
                 if self._tiny:
                     self._engine.set_collect_tiny(True)
+                if self._wide_arrive:
+                    self._engine.set_collect_wide_arrive(True)
                 self._engine.collect_begin(self._n_cap, row.shape[0], np.float64)
             if self._noised:
                 self._slots.append(self._engine.collect_add_noised(row, update.Noise))
             else:
                 self._slots.append(self._engine.collect_add(row))
         self.UpdateList.append(update)
+
+    def _last_pinned(self, row, order, n, clip):
+        """the last arrival from pinned staging: (slot, sel)"""
+        pin = ctypes.c_void_p()
+        check(lib().bk_stage_alloc(self._engine.ctx, row.nbytes, ctypes.byref(pin)))
+        try:
+            ctypes.memmove(pin, row.ctypes.data, row.nbytes)
+            order = np.ascontiguousarray(order, dtype=np.int64)
+            sel = np.empty(n - clip, dtype=np.int64)
+            slot, m = self._engine.collect_add_finish_ptr(pin.value, _lib.BK_HOST_PINNED,
+                                                          order.ctypes.data, n, clip,
+                                                          sel.ctypes.data)
+            assert m == n - clip
+        finally:
+            lib().bk_stage_free(self._engine.ctx, pin)
+        return slot, sel
 
     def noised_delta(self, i):
         """noised mode: UpdateList[i].NoisedDelta, read back from the row store

@@ -248,8 +248,9 @@ int bk_collect_finish(bk_ctx *ctx, const int64_t *order, int64_t n, int64_t f,
  * bk_collect_add's) in front of the one-launch finish's work items, timed under
  * BK_K_SMALL; then one wait.  Everything else (bk_set_small_path(ctx, 0), n >
  * 128, more than 128 rows collected, d > 32,768 with or without
- * bk_set_collect_wide, and a BK_HOST row of more than 32 KiB, where the fused
- * call measured no faster) runs the add and then the finish inside the call.
+ * bk_set_collect_wide -- but see bk_set_collect_wide_arrive -- and a BK_HOST row
+ * of more than 32 KiB, where the fused call measured no faster) runs the add and
+ * then the finish inside the call.
  * The checks, in this order, all before any copy, launch or state change (a
  * refused call leaves the collection as it was), with the messages of the two
  * entries: BK_EINVAL for a null ctx, a null row, a bad where, a null sel_idx;
@@ -608,6 +609,45 @@ int bk_set_small_path(bk_ctx *ctx, int on);
 #define BK_COLLECT_WIDE_MAX_D 1048576
 #define BK_COLLECT_WIDE_MEAN_MAX_D 165888 /* 81 mean items of 2,048 columns */
 int bk_set_collect_wide(bk_ctx *ctx, int on);
+/* Opt-in (default off), with effect only while bk_set_collect_wide is on: the
+ * last arrival of a WIDE row and its finish in one launch.  With on != 0,
+ * bk_collect_add_finish whose finish is in the wide one-launch range (n <= 128,
+ * 32,768 < d <= BK_COLLECT_WIDE_MAX_D without a mean, <=
+ * BK_COLLECT_WIDE_MEAN_MAX_D with one), with at most 128 rows collected after
+ * the add and a BK_HOST_PINNED or BK_DEVICE row, is the row's copy into its
+ * slot followed by ONE launch and one wait: k_collect_arrive_wide -- the
+ * border of the new row spread over the grid (k_border's chunk partials into
+ * the collection's partials buffer, k_border_reduce's chunk sums into the
+ * Gram, every element the bits of bk_collect_add's) in front of
+ * k_collect_wide's score and mean items.  Timed under BK_K_SMALL and counted
+ * in bk_collect_stats' out[3], never in out[0] or out[1].  Every output --
+ * sel, scores, mean, the margin record -- and everything a later add, finish,
+ * batched or ragged finish or bk_collect_read_rows sees is BITWISE the
+ * two-call sequence's.  Checks, their order and their messages are
+ * bk_collect_add_finish's; a refused call leaves the collection and the stats
+ * as they were, and a row whose launch failed does not count.  A pageable
+ * (BK_HOST) row, bk_collect_add_noised_finish, bk_collect_add and the batched
+ * and ragged finishes are unchanged; with the switch off every call takes
+ * exactly the launches it took before.  on = 1 takes the fused launch only
+ * where it was measured ahead of the sequence: a BK_HOST_PINNED row of at most
+ * 320,000 bytes (40,000 fp64 columns) in a call that asks for the mean (88.0
+ * against 89.8 us at 100 x 40,000; at 100 x 163,850 and beyond, from device
+ * rows and without the mean it was level or behind, e.g. 58.3 against 54.3 us)
+ * -- every other call of the range runs the sequence inside the entry.  on = 2
+ * takes it in the whole range (for tests and measurements).  BK_EINVAL: a null
+ * ctx.
+ * bk_collect_wide_arrive_item: the kernel's queue, for tests -- item `item` of
+ * the launch for `rows` rows collected after the add (1..128), a finish of n
+ * rows with (mean != 0) or without a mean: kind 0 B (a = chunk, b = row block
+ * of the border partials), 1 R (a = first Gram element of run rows - 1, b =
+ * elements), 2 S (a = row), 3 M (a = mean item); counts[0..3] = the items of
+ * each kind, numbered in that order.  Host-side only.  BK_EINVAL: a null
+ * output, a shape outside the range, an item outside the queue.
+ * Both added without a change of BK_ABI_VERSION (14), as bk_set_collect_tiny
+ * was. */
+int bk_set_collect_wide_arrive(bk_ctx *ctx, int on);
+int bk_collect_wide_arrive_item(int64_t rows, int64_t d, int dtype, int64_t n, int mean,
+                                int64_t item, int *kind, int *a, int *b, int64_t counts[4]);
 /* Replay bk_multikrum_device as a hipGraph (one captured launch sequence per
  * call signature: pointers, shape, f; up to 4 cached).  The first call of a
  * signature runs eagerly, the second captures, later ones replay; graphs are
