@@ -30,6 +30,7 @@ ROUND_KERNELS = ["k_roni_round", "k_roni_round_sm"]
 ALL_KERNELS = KERNELS + ROUND_KERNELS
 K = {name: i for i, name in enumerate(ALL_KERNELS)}
 BK_RONI_ROUND_G = 8
+BK_EVAL_MAX_SETS = 4
 
 # every symbol include/bk.h declares: name -> (restype, argtypes)
 _i = ctypes.c_int
@@ -100,6 +101,12 @@ SIGNATURES = {
     "bk_roni_softmax_round_begin": (_i, [_p, _p, _i]),
     "bk_roni_softmax_round_score": (_i, [_p, _p, _i64, _i, _p, _p]),
     "bk_roni_softmax_round_score_batches": (_i, [_p, _p, _i64, _i, _p, _i64, _p, _p]),
+    "bk_eval_set_logistic": (_i, [_p, _i, _p, _i64, _i64, _i64, _p]),
+    "bk_eval_set_softmax": (_i, [_p, _i, _p, _i64, _i64, _i64, _p, _i64]),
+    "bk_eval_clear": (_i, [_p, _i]),
+    "bk_eval": (_i, [_p, _p, _i64, _i, _p, _i, _p, _p, _p]),
+    "bk_eval_stats": (_i, [_p, _pi64]),
+    "bk_block_finish_eval": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _p]),
     "bk_group_create": (_i, [ctypes.POINTER(_p), _i, _p, _i]),
     "bk_group_destroy": (None, [_p]),
     "bk_group_size": (_i, [_p]),

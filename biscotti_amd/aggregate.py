@@ -128,14 +128,27 @@ class BlockCollector:
             self._qsum = (out[1], out[2]) if want_q else None
         return self._result
 
-    def create_block(self, stake_map: Dict[int, int]) -> np.ndarray:
+    def create_block(self, stake_map: Dict[int, int], evaluator=None, threshold=None):
         """createBlock over the updates added so far (the deadline path may call
         it with fewer than expected): the updated gradient, a new array, and the
-        +-STAKE_UNIT bookkeeping on stake_map.  The block is not consumed."""
+        +-STAKE_UNIT bookkeeping on stake_map.  The block is not consumed.
+
+        evaluator (an evaluate.ModelEvaluator on this collector's engine): the
+        new gradient is also scored where it is, on the device
+        (bk_block_finish_eval), and the return value is (gradient, (converged,
+        train_error, attack_rate or None)) -- checkConvergence's answer
+        (honest.go:141-162; converged is None without a threshold)."""
         for u in self._updates:
             their = stake_map.get(u.SourceID, 0)
             stake_map[u.SourceID] = their + (STAKE_UNIT if u.Accepted else -STAKE_UNIT)
-        return self._finish().copy()
+        if evaluator is None:
+            return self._finish().copy()
+        want_q = self._precision is not None
+        out, verdict = evaluator.finish_block(
+            lambda slots: self._engine.block_finish_eval(slots, want_qsum=want_q), threshold)
+        self._result = out[0]
+        self._qsum = (out[1], out[2]) if want_q else None
+        return self._result.copy(), verdict
 
     def quantized_sum(self):
         """(int64 sum, float64 sum) of the accepted updates so far, as

@@ -204,6 +204,9 @@ int bk_create(bk_ctx **out, int device) {
     cut("BK_BLOCK_MAPPED_HOST", c->block_mapped_host, 4 << 20);
     cut("BK_BLOCK_MAPPED_PINNED", c->block_mapped_pinned, 4 << 20);
     cut("BK_BLOCK_FIN", c->block_fin_max, INT64_MAX);
+    // bk_block_finish_eval's two routes, bit-identical (tools/eval_bench.py)
+    // (1: the sequence everywhere, 0: one wait everywhere; unset: routed)
+    if (const char *v = getenv("BK_BLOCK_EVAL_SEQ")) c->block_eval_one_wait = atoi(v) ? 0 : 2;
     e = configure_kernels();
     if (e == hipSuccess) e = configure_aggregate_kernels();
     if (e == hipSuccess) e = configure_i8_kernels();
@@ -258,6 +261,7 @@ void bk_destroy(bk_ctx *c) {
         if (c->rstage) (void)hipHostFree(c->rstage);
         collect_destroy(c->collect);
         block_destroy(c->block);
+        eval_destroy(c->eval);
         delete c->hpool;
         if (c->copy) (void)hipStreamDestroy(c->copy);
         for (void *p : c->staged) (void)hipHostFree(p);

@@ -283,8 +283,16 @@ int add_rows(bk_ctx *c, Block *b, const void *const *rows, const uint8_t *accept
     return BK_OK;
 }
 
-// bk_block_finish past its checks (the context mutex held, the device selected)
-int finish(bk_ctx *c, Block *b, double *global_out, int64_t *qsum_out, double *qsum_float_out) {
+struct NoBehind {
+    int operator()() const { return BK_OK; }
+};
+
+// bk_block_finish past its checks (the context mutex held, the device selected).
+// behind: more work for the stream, queued once the finish's own is and before
+// the one wait (bk_block_finish_eval's evaluation of g[cur])
+template <typename F = NoBehind>
+int finish(bk_ctx *c, Block *b, double *global_out, int64_t *qsum_out, double *qsum_float_out,
+           F &&behind = F()) {
     const hipStream_t st = c->stream;
     const size_t db = (size_t)b->d * 8, s = out_stride(b->d);
     Drain drain{st};
@@ -296,6 +304,7 @@ int finish(bk_ctx *c, Block *b, double *global_out, int64_t *qsum_out, double *q
             BlockRows none = {};
             CHK(launch_group(c, b, none, 0, true));
         }
+        CHK(behind());
         HIPCHK(wait_stream(c));
         drain.armed = false;
         memcpy(global_out, b->out, db);
@@ -310,6 +319,7 @@ int finish(bk_ctx *c, Block *b, double *global_out, int64_t *qsum_out, double *q
             e = hipMemcpyAsync(qsum_out, b->q[b->cur], db, hipMemcpyDeviceToHost, st);
         return e;
     }));
+    CHK(behind());
     HIPCHK(wait_stream(c));
     drain.armed = false;
     return BK_OK;
@@ -469,6 +479,38 @@ int bk_block_add_finish(bk_ctx *c, const void *row, int accepted, int where, int
     if (fused) CHK(ensure_out(c, b));
     CHK(add_rows(c, b, rows, &acc, 1, where, fused, first_slot));
     return finish(c, b, global_out, qsum_out, qsum_float_out);
+}
+
+// createBlock's gradient and checkConvergence's scores of it in one call: the
+// evaluation reads g[cur] where the finish leaves it.  One wait for both, or
+// the finish, then the evaluation (c->block_eval_one_wait): the same bits
+int bk_block_finish_eval(bk_ctx *c, double *global_out, int64_t *qsum_out, double *qsum_float_out,
+                         const int *sets, int nsets, double *err, int64_t *wrong,
+                         int32_t *near_ties) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!global_out) return fail(BK_EINVAL, "null global_out");
+    std::lock_guard<std::mutex> lk(c->mu);
+    CHK(check_live(c, "bk_block_finish_eval"));
+    Block *b = c->block;
+    CHK(check_finish_args(b, global_out, qsum_out, qsum_float_out));
+    CHK(eval_check_args(sets, nsets, err, wrong));
+    CHK(eval_check_sets(c, b->d, sets, nsets));
+    DeviceGuard dg(c->device);
+    const auto queue = [&] { return eval_queue(c, b->g[b->cur], sets, nsets); };
+    // measured: one wait is ahead where the finish is a D2H
+    // copy, and behind where it is a FIN launch's stores into mapped memory
+    const bool fin = fin_ok(c, b) || qsum_float_out;
+    if (c->block_eval_one_wait == 2 || (c->block_eval_one_wait == 1 && !fin)) {
+        CHK(finish(c, b, global_out, qsum_out, qsum_float_out, queue));
+    } else {
+        CHK(finish(c, b, global_out, qsum_out, qsum_float_out));
+        Drain drain{c->stream};
+        CHK(queue());
+        HIPCHK(wait_stream(c));
+        drain.armed = false;
+    }
+    eval_collect(c, nsets, err, wrong, near_ties);
+    return BK_OK;
 }
 
 int bk_block_stats(bk_ctx *c, int64_t out[4]) {

@@ -133,6 +133,22 @@ struct Block {
     bool out_valid = false;
 };
 
+// bk_eval*: the evaluation sets of a context (bk_eval.hip),
+// buffers of their own: RONI's validation sets and rounds never see them
+enum { EVAL_EMPTY = 0, EVAL_LOGISTIC = 1, EVAL_SOFTMAX = 2 };
+struct EvalSlot {
+    int kind = EVAL_EMPTY;
+    int64_t nv = 0, d = 0;    // samples; the model's length
+    int64_t din = 0, C = 0;   // softmax: d = C (din + 1)
+    DevBuf X, y, xn;          // compact rows (row stride d / din); xn: softmax only
+};
+struct Eval {
+    EvalSlot set[EVAL_MAX_SETS];
+    DevBuf w, cnt;            // a host model's device copy; the launch's counters
+    EvalOut *out = nullptr, *out_dev = nullptr;  // mapped pinned: the last workgroup's stores
+    int64_t launches = 0, calls = 0;             // bk_eval_stats
+};
+
 }  // namespace bk
 
 // the C ABI's opaque handle, hence at global scope; its field types are bk::'s
@@ -360,6 +376,14 @@ struct bk_ctx {
     int64_t block_mapped_host = bk::BLOCK_MAPPED_HOST_MAX;
     int64_t block_mapped_pinned = bk::BLOCK_MAPPED_PINNED_MAX;
     int64_t block_fin_max = bk::BLOCK_FIN_MAX;
+    // bk_eval*: the evaluation sets (bk_eval.hip), created by the first set
+    bk::Eval *eval = nullptr;
+    // bk_block_finish_eval: the evaluation queued behind the finish, both
+    // sharing one wait -- 1: where that measured ahead (the finish is a D2H
+    // copy), 2 (BK_BLOCK_EVAL_SEQ=0): everywhere, 0 (BK_BLOCK_EVAL_SEQ=1):
+    // nowhere, the finish and the evaluation one after the other.  The outputs
+    // are the same bits either way
+    int block_eval_one_wait = 1;
 };
 
 namespace bk {
@@ -431,6 +455,15 @@ int check_margin_readback(bk_ctx *c);
 int ragged_stage_slot(bk_ctx *c, size_t bytes, int *slot);
 int batch_fetch(bk_ctx *c);
 void batch_pick_record(bk_ctx *c);
+// bk_eval.hip: bk_eval in the pieces bk_block_finish_eval shares.  check_args
+// needs no context; check_sets, queue and collect run under the context mutex
+// with the device selected.  queue launches on the context stream (dw: the
+// model on the device); collect reads the mapped block once the stream is done
+void eval_destroy(Eval *e);
+int eval_check_args(const int *sets, int nsets, const double *err, const int64_t *wrong);
+int eval_check_sets(bk_ctx *c, int64_t d, const int *sets, int nsets);
+int eval_queue(bk_ctx *c, const double *dw, const int *sets, int nsets);
+void eval_collect(bk_ctx *c, int nsets, double *err, int64_t *wrong, int32_t *near_ties);
 // bk_host.hip
 int stage_host_pipelined(bk_ctx *c, const void *X, int64_t ld, int dtype, const double *noise,
                          int64_t k, int64_t noise_ld, int64_t n, int64_t d, char *dX,

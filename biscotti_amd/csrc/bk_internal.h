@@ -317,6 +317,33 @@ hipError_t launch_roni_softmax_round_batch(const float *Xv, int64_t nv, int64_t 
                                            const RoundRows &rows, int g, const int32_t *idx_dev,
                                            const RoundIdx &idx_arg, int64_t nb, unsigned int *cnt,
                                            double *scores, int32_t *near, hipStream_t st);
+// bk_eval.hip: one model scored on up to EVAL_MAX_SETS resident sets in one
+// launch (bk_eval).  A launch's workgroups index the concatenated sample tiles
+// of the sets (set i: tiles [tile0, next tile0), EVAL_SIGN_TS / EVAL_LOGITS_TS
+// samples each).  cnt: EVAL_CNT_WORDS words, zero before the launch and left
+// zero by it ([i]: set i's mismatches / correct predictions, [4 + i]: its near
+// ties, [8]: the exit counter); out: the block the last workgroup out writes
+constexpr int EVAL_MAX_SETS = 4, EVAL_CNT_WORDS = 16, EVAL_EXIT = 2 * EVAL_MAX_SETS;
+constexpr int EVAL_SIGN_TS = 256, EVAL_LOGITS_TS = 64;
+struct EvalSet {
+    const void *X, *y;  // logistic: doubles; softmax: fp32 samples, int32 labels
+    const double *xn;   // softmax: the samples' norms
+    int64_t nv, ldv;
+    int tile0;
+};
+struct EvalDesc {
+    EvalSet s[EVAL_MAX_SETS];
+    int nsets;
+};
+struct EvalOut {
+    double err[EVAL_MAX_SETS];
+    int64_t wrong[EVAL_MAX_SETS];
+    int32_t near[EVAL_MAX_SETS];
+};
+hipError_t launch_eval_sign(const EvalDesc &desc, int tiles, const double *ww, int64_t d,
+                            unsigned int *cnt, EvalOut *out, hipStream_t st);
+hipError_t launch_eval_logits(const EvalDesc &desc, int tiles, const double *ww, int64_t din, int C,
+                              unsigned int *cnt, EvalOut *out, hipStream_t st);
 // bk_i8.hip: K1i8, the Gram of fp32 rows from exact int8 digit slices
 // (BK_F32_I8): column ranges (one per XCD), digit planes [3][npad][dp] int8
 struct I8Layout {

@@ -33,6 +33,7 @@
 #include <stdlib.h>
 
 #include "bk_internal.h"
+#include "bk_roni_dev.h"
 
 namespace bk {
 
@@ -148,29 +149,7 @@ __global__ __launch_bounds__(256) void k_roni_mm_prep(const double *__restrict__
 // LDS tile, then wave w takes models w, w + 4, ... of the tile, lane l sample
 // l: np.argmax over the C logits, one ballot count and one atomic per model
 // and workgroup.
-// K8's near-tie test (oracle/roni_oracle.c softmax_eval, the same fp64
-// expression): the winning logit l1 (class a) and the best other l2 can swap
-// under torch's fp32 sgemm rounding only if
-//     !( l1 - l2 - u (|l1| + |l2|)  >  E_a + max_c E_c ),  E_c = g (|x| |w_c| + |b_c|)
-// (g = gamma_{d_in + 1}(2^-24) (1 + 2^-10), host-computed), or a logit is not
-// finite.  xn = |x| of the sample, wn / b the model's C weight-row norms and
-// biases (fp32 values), all fp64.
-__device__ inline bool softmax_near_tie(const float *lg, int C, int best, double xn,
-                                        const double *wn, const double *b, double g) {
-    double wmax = 0.0, bmax = 0.0, l2 = -__builtin_inf();
-    bool fin = true;
-    for (int c = 0; c < C; ++c) {
-        const double w = wn[c], ab = __builtin_fabs(b[c]), v = (double)lg[c];
-        wmax = w > wmax ? w : wmax;
-        bmax = ab > bmax ? ab : bmax;
-        fin = fin && __builtin_isfinite(v);
-        if (c != best && v > l2) l2 = v;
-    }
-    const double u = 0x1p-24, l1 = (double)lg[best];
-    const double ea = g * (xn * wn[best] + __builtin_fabs(b[best]));
-    const double emax = g * (xn * wmax + bmax);
-    return !fin || !(l1 - l2 - u * (__builtin_fabs(l1) + __builtin_fabs(l2)) > ea + emax);
-}
+// K8's near-tie test: softmax_near_tie (bk_roni_dev.h).
 
 // |x_s| for every sample, bit for bit the oracle's sequential sum of squares
 // in k order (every fp32 square is exact in fp64).  The sum is one dependent
@@ -1001,25 +980,7 @@ hipError_t launch_roni(const double *Xv, int64_t nv, int64_t d, int64_t ldv, con
 // gridDim.x - 1 reads the totals (atomic loads) and writes the scores.  Nobody
 // waits for anybody.  cnt: [0, G) the models' counts, [G, 2 G) the softmax near
 // ties, [2 G] the exit counter; zeroed by the host before every launch.
-constexpr int ROUND_EXIT = 2 * RONI_ROUND_G;
-static_assert(ROUND_EXIT < ROUND_CNT_WORDS, "the exit counter lies in the block");
-
-__device__ inline unsigned int round_load(const unsigned int *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// thread 0 of every workgroup, after the barrier behind the LDS counts: true
-// for the last workgroup out, which may then read every workgroup's adds
-template <int NC>
-__device__ inline bool round_exit(const unsigned int (&s_cnt)[NC], const int (&slot)[NC],
-                                  unsigned int *cnt, int exit_slot = ROUND_EXIT) {
-#pragma unroll
-    for (int q = 0; q < NC; ++q)
-        if (s_cnt[q])
-            __hip_atomic_fetch_add(cnt + slot[q], s_cnt[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    return __hip_atomic_fetch_add(cnt + exit_slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-           gridDim.x - 1u;
-}
+// (round_exit / round_load: bk_roni_dev.h.)
 
 // k_roni_round_sign: a workgroup takes 256 samples, thread t sample t.  The
 // samples go through LDS in chunks of 32 features (the global loads run along

@@ -802,6 +802,86 @@ class Engine:
         check(lib().bk_block_stats(self._ctx, out))
         return list(out)
 
+    # ---- the convergence check: resident evaluation sets (bk_eval*) ---------
+    def eval_set_logistic(self, set_index, X, y):
+        """Make (X, y) the context's evaluation set `set_index` (0 .. 3): X nv x d
+        float64 (a row stride is kept), y the nv labels (stored as float64)."""
+        X = np.asarray(X)
+        if X.ndim != 2 or X.dtype != np.float64 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("X must be a float64 matrix, nv x d")
+        if X.strides[1] != 8 or X.strides[0] % 8 or X.strides[0] < 8 * X.shape[1]:
+            X = np.ascontiguousarray(X)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.shape != (X.shape[0],):
+            raise ValueError("y must have one label per row of X")
+        check(lib().bk_eval_set_logistic(self._ctx, int(set_index), X.ctypes.data, X.shape[0],
+                                         X.shape[1], X.strides[0] // 8, y.ctypes.data))
+
+    def eval_set_softmax(self, set_index, X, y, n_classes):
+        """X nv x d_in float32, y integer labels in [0, n_classes); the model
+        scored on it has n_classes * (d_in + 1) entries (W row-major, then b)."""
+        X = np.asarray(X)
+        if X.ndim != 2 or X.dtype != np.float32 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("X must be a float32 matrix, nv x d_in")
+        if X.strides[1] != 4 or X.strides[0] % 4 or X.strides[0] < 4 * X.shape[1]:
+            X = np.ascontiguousarray(X)
+        ya = np.asarray(y)
+        if ya.shape != (X.shape[0],) or not np.issubdtype(ya.dtype, np.integer):
+            raise ValueError("y must have one integer label per row of X")
+        y32 = np.ascontiguousarray(ya, dtype=np.int32)
+        if not np.array_equal(y32, ya):
+            raise ValueError("labels do not fit int32")
+        check(lib().bk_eval_set_softmax(self._ctx, int(set_index), X.ctypes.data, X.shape[0],
+                                        X.shape[1], X.strides[0] // 4, y32.ctypes.data,
+                                        int(n_classes)))
+
+    def eval_clear(self, set_index):
+        check(lib().bk_eval_clear(self._ctx, int(set_index)))
+
+    @staticmethod
+    def _eval_outs(sets):
+        s = np.ascontiguousarray(np.atleast_1d(sets), dtype=np.intc)
+        if s.ndim != 1 or not 1 <= s.shape[0] <= _lib.BK_EVAL_MAX_SETS:
+            raise ValueError("sets must name 1 .. %d evaluation sets" % _lib.BK_EVAL_MAX_SETS)
+        n = s.shape[0]
+        return s, np.empty(n), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int32)
+
+    def eval(self, ww, sets):
+        """Score the model ww (float64 vector) on the resident sets named:
+        (err float64, wrong int64, near_ties int32), one entry per set."""
+        w = np.ascontiguousarray(ww, dtype=np.float64)
+        if w.ndim != 1 or w.shape[0] < 1:
+            raise ValueError("ww must be a float64 vector")
+        s, err, wrong, near = self._eval_outs(sets)
+        self.eval_ptr(w.ctypes.data, w.shape[0], _lib.BK_HOST, s, err, wrong, near)
+        return err, wrong, near
+
+    def eval_ptr(self, ww_ptr, d, where, sets, err, wrong, near_ties=None):
+        """The model by raw pointer (pageable, pinned or device memory); sets an
+        intc array, err / wrong / near_ties numpy outputs of its length."""
+        check(lib().bk_eval(self._ctx, _p(ww_ptr), int(d), int(where), sets.ctypes.data,
+                            int(sets.shape[0]), err.ctypes.data, wrong.ctypes.data,
+                            _ptr(near_ties)))
+
+    def eval_stats(self):
+        """[launches, calls] of bk_eval / bk_block_finish_eval since the engine
+        was made."""
+        out = (ctypes.c_int64 * 2)()
+        check(lib().bk_eval_stats(self._ctx, out))
+        return list(out)
+
+    def block_finish_eval(self, sets, want_qsum=False):
+        """block_finish and eval of the returned gradient in one call
+        (bk_block_finish_eval): (gradient[, int64 sum, float sum], err, wrong,
+        near_ties)."""
+        _, d, p = self._block_state("block_finish_eval")
+        g, q, qf = self._block_outs(want_qsum, p, d)
+        s, err, wrong, near = self._eval_outs(sets)
+        check(lib().bk_block_finish_eval(self._ctx, g.ctypes.data, _ptr(q), _ptr(qf),
+                                         s.ctypes.data, int(s.shape[0]), err.ctypes.data,
+                                         wrong.ctypes.data, near.ctypes.data))
+        return ((g, q, qf) if want_qsum else (g,)) + (err, wrong, near)
+
     def noise_apply_ptr(self, delta_ptr, n, d, ld, noise_ptr, k, noise_ld, out_ptr, out_ld):
         check(lib().bk_noise_apply_device(self._ctx, _p(delta_ptr), n, d, ld, _p(noise_ptr), k,
                                           noise_ld, _p(out_ptr), out_ld))

@@ -318,6 +318,106 @@ func createBlockGPU() []float64 {
 	return out
 }
 
+// The engine's evaluation-set slots (bk_eval_set_*): the set testModel scores
+// and the attack set testAttackRate scores.
+const (
+	bkEvalTrainSet  = 0
+	bkEvalAttackSet = 2
+)
+
+// setEvalLogisticGPU makes (X, y) the resident set `set`: X is nv x d, row-major
+// (the creditcard train set that train_error reads).  Call it once at pyInit.
+func setEvalLogisticGPU(set int, X []float64, y []float64, d int) bool {
+	nv := len(y)
+	if bkCtx == nil || nv == 0 || d == 0 || len(X) != nv*d {
+		return false
+	}
+	var xp, yp *C.double
+	xp = (*C.double)(unsafe.Pointer(&X[0]))
+	yp = (*C.double)(unsafe.Pointer(&y[0]))
+	if st := C.bk_eval_set_logistic(bkCtx, C.int(set), xp, C.int64_t(nv), C.int64_t(d), C.int64_t(d), yp); st != C.BK_OK {
+		outLog.Printf("bk_eval_set_logistic failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	return true
+}
+
+// setEvalSoftmaxGPU is the torch datasets' form: X nv x dIn float32, y the
+// labels in [0, classes) (the test set of getTestErr, the attack set of
+// get17AttackRate).
+func setEvalSoftmaxGPU(set int, X []float32, y []int32, dIn int, classes int) bool {
+	nv := len(y)
+	if bkCtx == nil || nv == 0 || dIn == 0 || len(X) != nv*dIn {
+		return false
+	}
+	var xp *C.float
+	var yp *C.int32_t
+	xp = (*C.float)(unsafe.Pointer(&X[0]))
+	yp = (*C.int32_t)(unsafe.Pointer(&y[0]))
+	if st := C.bk_eval_set_softmax(bkCtx, C.int(set), xp, C.int64_t(nv), C.int64_t(dIn), C.int64_t(dIn), yp, C.int64_t(classes)); st != C.BK_OK {
+		outLog.Printf("bk_eval_set_softmax failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	return true
+}
+
+func evalSetGPU(weights []float64, set int) float64 {
+	d := len(weights)
+	if bkCtx == nil || d == 0 {
+		return -1
+	}
+	var wp *C.double
+	wp = (*C.double)(unsafe.Pointer(&weights[0]))
+	var setC C.int
+	var errC C.double
+	var wrongC C.int64_t
+	setC = C.int(set)
+	if st := C.bk_eval(bkCtx, wp, C.int64_t(d), C.BK_HOST, &setC, 1, &errC, &wrongC, nil); st != C.BK_OK {
+		outLog.Printf("bk_eval failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return -1
+	}
+	return float64(errC)
+}
+
+// testModelGPU replaces testModel (honest.go:656-675): the model's error on the
+// resident train / test set, what train_error / getTestErr return.  -1 on an
+// engine error (the caller then falls back to the Python call).
+func testModelGPU(weights []float64) float64 {
+	return evalSetGPU(weights, bkEvalTrainSet)
+}
+
+// testAttackRateGPU replaces testAttackRate (honest.go:260-275).
+func testAttackRateGPU(weights []float64) float64 {
+	return evalSetGPU(weights, bkEvalAttackSet)
+}
+
+// createBlockEvalGPU is createBlockGPU with checkConvergence's scores of the
+// new gradient (honest.go:141-162) from the same call: the model is scored
+// where it is, on the device.  withAttack: the torch datasets' attack rate too
+// (-1 otherwise).  nil on an engine error.
+func createBlockEvalGPU(withAttack bool) ([]float64, float64, float64) {
+	if bkCtx == nil || bkBlockDim == 0 {
+		return nil, -1, -1
+	}
+	out := make([]float64, bkBlockDim)
+	var outp *C.double
+	outp = (*C.double)(unsafe.Pointer(&out[0]))
+	setsC := make([]C.int, 2)
+	errC := make([]C.double, 2)
+	wrongC := make([]C.int64_t, 2)
+	setsC[0], setsC[1] = bkEvalTrainSet, bkEvalAttackSet
+	errC[1] = -1
+	nsets := 1
+	if withAttack {
+		nsets = 2
+	}
+	if st := C.bk_block_finish_eval(bkCtx, outp, nil, nil, &setsC[0], C.int(nsets), &errC[0], &wrongC[0], nil); st != C.BK_OK {
+		outLog.Printf("bk_block_finish_eval failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return nil, -1, -1
+	}
+	return out, float64(errC[0]), float64(errC[1])
+}
+
 func noisedDeltas(updates []Update) [][]float64 {
 	deltas := make([][]float64, len(updates))
 	for i := range updates {

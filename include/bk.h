@@ -1108,6 +1108,62 @@ int bk_roni_softmax_round_score_batches(bk_ctx *ctx, const double *const *deltas
                                         int where, const int64_t *idx, int64_t nb, double *scores,
                                         int32_t *near_ties);
 
+/* The convergence check: the new model's error and attack rate.
+ * checkConvergence (DistSys/honest.go:141-162) scores the block's model with
+ * testModel (honest.go:656-675: train_error / getTestErr) and, for the torch
+ * datasets, testAttackRate (honest.go:260-275: get17AttackRate).  A context
+ * holds up to BK_EVAL_MAX_SETS resident evaluation sets, indexed 0 .. 3 and
+ * separate from RONI's validation sets: no bk_eval* call touches a validation
+ * set or a live round.
+ *   bk_eval_set_logistic  X nv x d fp64 (row stride ldv), y the nv labels as
+ *                  doubles; replaces the slot's set.
+ *   bk_eval_set_softmax   X nv x d_in fp32 (row stride ldv), y int32 labels in
+ *                  [0, n_classes), 2 <= n_classes <= 16; the model's d is
+ *                  n_classes * (d_in + 1) (bk_roni_softmax's layout).
+ *   bk_eval_clear  empties a slot.
+ *   bk_eval        scores ONE model (d doubles at `where`: BK_HOST,
+ *                  BK_HOST_PINNED or BK_DEVICE; consumed on return) on nsets
+ *                  resident sets of one kind and of the model's d, in one launch
+ *                  and one wait.  For sets[s] it writes err[s], wrong[s] and, if
+ *                  non-null, near_ties[s].  Synchronous.
+ *   bk_eval_stats  out[0]: launches, out[1]: bk_eval / bk_block_finish_eval
+ *                  calls, since bk_create.  A call is one launch: the softmax
+ *                  model's preparation is folded into it.
+ * The arithmetic is bitwise the base-model evaluation of bk_roni /
+ * bk_roni_softmax above.  Logistic: each dot the fp64 FMA chain over k
+ * ascending, numpy's sign (0 stays 0, NaN never equals a label), wrong the
+ * mismatch count, err = (double)wrong / (double)nv, near_ties 0.  Softmax: ww
+ * rounded to fp32, each logit the fp64 k-ascending sum of exact fp32 products
+ * plus the bias, rounded once to fp32; argmax takes the first maximum and NaN
+ * wins; wrong = nv - correct, err = 1.0 - (double)correct / (double)nv,
+ * near_ties by the NEAR TIES rule above.
+ * Checked in this order, before any copy or launch: BK_EINVAL for a null ctx,
+ * ww, sets, err or wrong, nsets outside [1, BK_EVAL_MAX_SETS], a set index
+ * outside [0, BK_EVAL_MAX_SETS) or a bad where; then BK_EINVAL (the set named)
+ * for an empty slot, sets of mixed kinds, d other than the set's, or a set
+ * named twice.  bk_eval_set_*: BK_EINVAL for a bad set index, nv < 1, d < 1,
+ * ldv < d, n_classes < 2, a null pointer, or a label outside [0, n_classes)
+ * (the sample named); BK_ENOTSUP for n_classes > 16.  Added without a change
+ * of BK_ABI_VERSION (14). */
+#define BK_EVAL_MAX_SETS 4
+int bk_eval_set_logistic(bk_ctx *ctx, int set, const double *X, int64_t nv, int64_t d, int64_t ldv,
+                         const double *y);
+int bk_eval_set_softmax(bk_ctx *ctx, int set, const float *X, int64_t nv, int64_t d_in, int64_t ldv,
+                        const int32_t *y, int64_t n_classes);
+int bk_eval_clear(bk_ctx *ctx, int set);
+int bk_eval(bk_ctx *ctx, const double *ww, int64_t d, int where, const int *sets, int nsets,
+            double *err, int64_t *wrong, int32_t *near_ties);
+int bk_eval_stats(bk_ctx *ctx, int64_t out[2]);
+/* bk_block_finish followed by bk_eval of the returned model on `sets`, in one
+ * call: every output is bitwise the two-call sequence's.  The model is read
+ * from the block's device buffer (it is not uploaded again); where the finish
+ * is a device-to-host copy the evaluation is queued behind it and both share
+ * one wait (DESIGN.md 5t has the measurement).  bk_block_finish's checks
+ * run first, then bk_eval's with the block's d; a refused call leaves the block
+ * as it was. */
+int bk_block_finish_eval(bk_ctx *ctx, double *global_out, int64_t *qsum_out, double *qsum_float_out,
+                         const int *sets, int nsets, double *err, int64_t *wrong, int32_t *near_ties);
+
 /* ---- measurement: per-kernel HIP-event timing on the context stream ------- */
 enum bk_kernel_id {
     BK_K_GRAM = 0,     /* K1  fp64-MFMA split-K upper-triangle Gram partials */
