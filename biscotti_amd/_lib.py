@@ -31,6 +31,7 @@ ALL_KERNELS = KERNELS + ROUND_KERNELS
 K = {name: i for i, name in enumerate(ALL_KERNELS)}
 BK_RONI_ROUND_G = 8
 BK_EVAL_MAX_SETS = 4
+BK_SHARES_MAX_POLY, BK_SHARES_MAX_POINTS = 10, 64
 
 # every symbol include/bk.h declares: name -> (restype, argtypes)
 _i = ctypes.c_int
@@ -107,6 +108,14 @@ SIGNATURES = {
     "bk_eval": (_i, [_p, _p, _i64, _i, _p, _i, _p, _p, _p]),
     "bk_eval_stats": (_i, [_p, _pi64]),
     "bk_block_finish_eval": (_i, [_p, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "bk_shares_chunks": (_i64, [_i64, _i]),
+    "bk_shares_generate": (_i, [_p, _p, _i, _i64, _i, _i, _i, _p]),
+    "bk_shares_begin": (_i, [_p, _i64, _i, _i, _i64]),
+    "bk_shares_add": (_i, [_p, _p, _i, _pi64]),
+    "bk_shares_count": (_i, [_p, _pi64]),
+    "bk_shares_sum": (_i, [_p, _p, _i64, _p]),
+    "bk_shares_recover": (_i, [_p, _p, _p, _p, _i, _i, _i64, _i, _i, _p, _p, _p, _p, _pi64]),
+    "bk_shares_stats": (_i, [_p, _pi64]),
     "bk_group_create": (_i, [ctypes.POINTER(_p), _i, _p, _i]),
     "bk_group_destroy": (None, [_p]),
     "bk_group_size": (_i, [_p]),

@@ -207,6 +207,7 @@ int bk_create(bk_ctx **out, int device) {
     // bk_block_finish_eval's two routes, bit-identical (tools/eval_bench.py)
     // (1: the sequence everywhere, 0: one wait everywhere; unset: routed)
     if (const char *v = getenv("BK_BLOCK_EVAL_SEQ")) c->block_eval_one_wait = atoi(v) ? 0 : 2;
+    if (const char *v = getenv("BK_SHARES_GEN_PER_CHUNK")) c->shares_gen_per_chunk = atoi(v) ? 1 : 0;
     e = configure_kernels();
     if (e == hipSuccess) e = configure_aggregate_kernels();
     if (e == hipSuccess) e = configure_i8_kernels();
@@ -262,6 +263,7 @@ void bk_destroy(bk_ctx *c) {
         collect_destroy(c->collect);
         block_destroy(c->block);
         eval_destroy(c->eval);
+        shares_destroy(c->shares);
         delete c->hpool;
         if (c->copy) (void)hipStreamDestroy(c->copy);
         for (void *p : c->staged) (void)hipHostFree(p);

@@ -133,6 +133,22 @@ struct Block {
     bool out_valid = false;
 };
 
+// bk_shares_*: the secure-aggregation share state of a context (DESIGN.md
+// §5u).  store: n_cap parts of `stride` int64 each (part_elems = chunks * held
+// of them used, stride the next even number: every part starts on 16 bytes);
+// own: the last bk_shares_sum's aggregate.  The other buffers stage one call's
+// host inputs and outputs.  All grow only
+struct Shares {
+    bool begun = false;
+    int64_t d = 0, chunks = 0, n_cap = 0, count = 0, part_elems = 0, stride = 0;
+    int poly = 0, held = 0;
+    bool own_valid = false;
+    DevBuf store, own, slots, in, w, out, bad;
+    // bk_shares_stats, since the context was made: launches, copy calls,
+    // calls that reached the device, bad chunks
+    int64_t stats[4] = {0, 0, 0, 0};
+};
+
 // bk_eval*: the evaluation sets of a context (bk_eval.hip),
 // buffers of their own: RONI's validation sets and rounds never see them
 enum { EVAL_EMPTY = 0, EVAL_LOGISTIC = 1, EVAL_SOFTMAX = 2 };
@@ -384,6 +400,11 @@ struct bk_ctx {
     // nowhere, the finish and the evaluation one after the other.  The outputs
     // are the same bits either way
     int block_eval_one_wait = 1;
+    // bk_shares_*: the share state (bk_shares_api.hip), created by the first call
+    bk::Shares *shares = nullptr;
+    // k_shares_gen's layout: 0 one thread per (chunk, share), 1 one thread per
+    // chunk (BK_SHARES_GEN_PER_CHUNK, for tools/shares_bench.py; the same bits)
+    int shares_gen_per_chunk = 0;
 };
 
 namespace bk {

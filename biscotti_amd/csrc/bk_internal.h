@@ -761,4 +761,33 @@ hipError_t launch_block_add(const BlockLaunch &L, int num_cu, hipStream_t st);
 struct Block;
 void block_destroy(Block *b);
 
+// bk_shares.hip: the secure-aggregation share arithmetic (bk_shares_*,
+// DESIGN.md §5u).  Parts and y are [chunk][share] int64; share s sits at
+// x = s - SHARES_X0.  Every pointer is device memory, 8-byte aligned
+constexpr int SHARES_MAX_POLY = 10;
+constexpr int SHARES_MAX_POINTS = 64;
+constexpr int SHARES_X0 = 10;
+// y[chunk][s], s < T, from the delta's d entries; per_chunk: one thread per
+// chunk looping over the shares, else one thread per (chunk, share)
+hipError_t launch_shares_gen(const double *delta, int64_t d, double scale, int P, int T,
+                             int64_t *y, bool per_chunk, hipStream_t st);
+// out[e] = sum_r store[slots[r] * stride + e], e < elems (wrapping); stride
+// even, store and out 16-byte aligned
+hipError_t launch_shares_sum(const int64_t *store, int64_t stride, int64_t elems,
+                             const int64_t *slots, int64_t count, int64_t *out, int num_cu,
+                             hipStream_t st);
+// point s of chunk c is base[s][c * stride[s]] at node x[s]
+struct SharesPoints {
+    const int64_t *base[SHARES_MAX_POINTS];
+    int stride[SHARES_MAX_POINTS];
+    int x[SHARES_MAX_POINTS];
+};
+// coef / delta nullable; *bad (zeroed by the caller) counts the bad chunks
+hipError_t launch_shares_recover(const SharesPoints &pts, int S, int P, int64_t d, double scale,
+                                 const double *w, int64_t *coef, double *delta, double *global,
+                                 unsigned long long *bad, hipStream_t st);
+// bk_shares_api.hip: a context's share state, which owns its buffers
+struct Shares;
+void shares_destroy(Shares *s);
+
 }  // namespace bk

@@ -882,6 +882,157 @@ class Engine:
                                          wrong.ctypes.data, near.ctypes.data))
         return ((g, q, qf) if want_qsum else (g,)) + (err, wrong, near)
 
+    # ---- secure aggregation: shares, their sum and recovery (bk_shares_*) ----
+    @staticmethod
+    def _shares_shape(d, poly_size, precision=0):
+        d, poly_size, precision = int(d), int(poly_size), int(precision)
+        if d < 1:
+            raise ValueError("d=%d < 1" % d)
+        if not 1 <= poly_size <= _lib.BK_SHARES_MAX_POLY:
+            raise ValueError("poly_size=%d outside [1, %d]" % (poly_size, _lib.BK_SHARES_MAX_POLY))
+        if not 0 <= precision <= 18:
+            raise ValueError("precision=%d outside [0, 18]" % precision)
+        return d, poly_size, precision, -(-d // poly_size)
+
+    @staticmethod
+    def _shares_part(a, chunks, held, what="part"):
+        a = np.asarray(a)
+        if a.dtype != np.int64 or a.shape != (chunks, held):
+            raise ValueError("%s must be an int64 array of shape (%d, %d)" % (what, chunks, held))
+        return a if a.flags.c_contiguous else np.ascontiguousarray(a)
+
+    def shares_generate(self, delta, precision=4, poly_size=10, total_shares=20):
+        """A client's shares of the float64 vector delta: int64 [chunk][share],
+        createShareAndWitness's values bit for bit (bk_shares_generate)."""
+        a = np.asarray(delta)
+        if a.dtype != np.float64 or a.ndim != 1:
+            raise ValueError("delta must be a 1-D float64 array")
+        a = a if a.flags.c_contiguous else np.ascontiguousarray(a)
+        d, P, p, chunks = self._shares_shape(a.shape[0] if a.shape[0] else 0, poly_size, precision)
+        T = int(total_shares)
+        if not P <= T <= _lib.BK_SHARES_MAX_POINTS:
+            raise ValueError("total_shares=%d outside [poly_size=%d, %d]"
+                             % (T, P, _lib.BK_SHARES_MAX_POINTS))
+        y = np.empty((chunks, T), dtype=np.int64)
+        self.shares_generate_ptr(a.ctypes.data, _lib.BK_HOST, d, p, P, T, y.ctypes.data)
+        return y
+
+    def shares_generate_ptr(self, delta_ptr, where, d, precision, poly_size, total_shares, y_ptr):
+        """delta and y by raw pointer, both pageable, pinned or device memory."""
+        check(lib().bk_shares_generate(self._ctx, _p(delta_ptr), int(where), int(d), int(precision),
+                                       int(poly_size), int(total_shares), _p(y_ptr)))
+
+    def shares_begin(self, d, poly_size, held, n_cap):
+        """The miner's store: up to n_cap parts of ceil(d / poly_size) x held int64."""
+        d, P, _, chunks = self._shares_shape(d, poly_size)
+        held, n_cap = int(held), int(n_cap)
+        if not 1 <= held <= _lib.BK_SHARES_MAX_POINTS:
+            raise ValueError("held=%d outside [1, %d]" % (held, _lib.BK_SHARES_MAX_POINTS))
+        if not 1 <= n_cap <= _lib.BK_MAX_N:
+            raise ValueError("n_cap=%d outside [1, %d]" % (n_cap, _lib.BK_MAX_N))
+        check(lib().bk_shares_begin(self._ctx, d, P, held, n_cap))
+        self._shares = (d, P, held, chunks)
+
+    def _shares_state(self, who):
+        st = getattr(self, "_shares", None)
+        if st is None:
+            raise ValueError("%s without shares_begin" % who)
+        return st
+
+    def shares_add(self, part):
+        """One client's part (int64, chunks x held, host); returns its slot."""
+        _, _, held, chunks = self._shares_state("shares_add")
+        a = self._shares_part(part, chunks, held)
+        return self.shares_add_ptr(a.ctypes.data, _lib.BK_HOST)
+
+    def shares_add_ptr(self, part_ptr, where):
+        self._shares_state("shares_add")
+        slot = ctypes.c_int64(-1)
+        check(lib().bk_shares_add(self._ctx, _p(part_ptr), int(where), ctypes.byref(slot)))
+        return slot.value
+
+    def shares_count(self):
+        n = ctypes.c_int64(0)
+        check(lib().bk_shares_count(self._ctx, ctypes.byref(n)))
+        return n.value
+
+    def shares_sum(self, slots, want=True):
+        """The wrapping sum of the listed slots' parts: kept on the device as the
+        context's own aggregate, and returned (chunks x held int64) if wanted."""
+        _, _, held, chunks = self._shares_state("shares_sum")
+        s = np.asarray(slots)
+        if s.ndim != 1 or s.shape[0] < 1 or not np.issubdtype(s.dtype, np.integer):
+            raise ValueError("slots must be a non-empty 1-D integer array")
+        s = np.ascontiguousarray(s, dtype=np.int64)
+        out = np.empty((chunks, held), dtype=np.int64) if want else None
+        check(lib().bk_shares_sum(self._ctx, s.ctypes.data, s.shape[0], _p(_ptr(out))))
+        return out
+
+    def shares_recover(self, global_w, parts, xs, precision=4, poly_size=10, want_coef=True,
+                       want_delta=True):
+        """The leader's recovery (bk_shares_recover): parts a sequence of int64
+        (chunks x held_i) host arrays, at most one of them None for the
+        context's own aggregate; xs the nodes in part order.  Returns
+        (global_w + delta, coef or None, delta or None, bad chunks)."""
+        w = np.asarray(global_w)
+        if w.dtype != np.float64 or w.ndim != 1:
+            raise ValueError("global_w must be a 1-D float64 array")
+        w = w if w.flags.c_contiguous else np.ascontiguousarray(w)
+        d, P, p, chunks = self._shares_shape(w.shape[0], poly_size, precision)
+        parts = list(parts)
+        if not 1 <= len(parts) <= _lib.BK_SHARES_MAX_POINTS:
+            raise ValueError("%d parts outside [1, %d]" % (len(parts), _lib.BK_SHARES_MAX_POINTS))
+        if sum(q is None for q in parts) > 1:
+            raise ValueError("at most one part may be None (the own aggregate)")
+        keep, held = [], []
+        for i, q in enumerate(parts):
+            if q is None:
+                held.append(self._shares_state("a None part")[2])
+                keep.append(None)
+                continue
+            a = np.asarray(q)
+            if a.ndim != 2 or a.shape[1] < 1:
+                raise ValueError("parts[%d] must be an int64 array of shape (%d, held)" % (i, chunks))
+            keep.append(self._shares_part(a, chunks, a.shape[1], "parts[%d]" % i))
+            held.append(a.shape[1])
+        x = np.asarray(xs)
+        if x.ndim != 1 or not np.issubdtype(x.dtype, np.integer) or x.shape[0] != sum(held):
+            raise ValueError("xs must hold one integer node per share: %d" % sum(held))
+        x = np.ascontiguousarray(x, dtype=np.int64)
+        if not P <= x.shape[0] <= _lib.BK_SHARES_MAX_POINTS:
+            raise ValueError("%d points outside [poly_size=%d, %d]"
+                             % (x.shape[0], P, _lib.BK_SHARES_MAX_POINTS))
+        if len(set(x.tolist())) != x.shape[0]:
+            raise ValueError("the nodes xs must differ")
+        ptrs = (ctypes.c_void_p * len(keep))(*[a.ctypes.data if a is not None else None
+                                               for a in keep])
+        h = np.ascontiguousarray(held, dtype=np.intc)
+        g = np.empty(d, dtype=np.float64)
+        coef = np.empty(d, dtype=np.int64) if want_coef else None
+        delta = np.empty(d, dtype=np.float64) if want_delta else None
+        bad = self.shares_recover_ptr(ptrs, h, x, _lib.BK_HOST, d, P, p, w.ctypes.data, _ptr(coef),
+                                      _ptr(delta), g.ctypes.data)
+        return g, coef, delta, bad
+
+    def shares_recover_ptr(self, part_ptrs, held, xs, where, d, poly_size, precision, global_ptr,
+                           coef_ptr, delta_ptr, out_ptr):
+        """Raw pointers: part_ptrs a ctypes c_void_p array (an entry None: the
+        own aggregate), held an intc array, xs an int64 array (both host); the
+        parts, global_w and the outputs at `where`.  Returns the bad chunks."""
+        bad = ctypes.c_int64(-1)
+        check(lib().bk_shares_recover(self._ctx, part_ptrs, held.ctypes.data, xs.ctypes.data,
+                                      int(held.shape[0]), int(where), int(d), int(poly_size),
+                                      int(precision), _p(global_ptr), _p(coef_ptr), _p(delta_ptr),
+                                      _p(out_ptr), ctypes.byref(bad)))
+        return bad.value
+
+    def shares_stats(self):
+        """[kernel launches, copy calls, calls, bad chunks] of bk_shares_* since
+        the engine was made."""
+        out = (ctypes.c_int64 * 4)()
+        check(lib().bk_shares_stats(self._ctx, out))
+        return list(out)
+
     def noise_apply_ptr(self, delta_ptr, n, d, ld, noise_ptr, k, noise_ld, out_ptr, out_ld):
         check(lib().bk_noise_apply_device(self._ctx, _p(delta_ptr), n, d, ld, _p(noise_ptr), k,
                                           noise_ld, _p(out_ptr), out_ld))

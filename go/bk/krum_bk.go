@@ -24,6 +24,17 @@ package main
 #include <stdlib.h>
 #include <string.h>
 #include "bk.h"
+
+// bk_shares_recover's pointer table is `const int64_t *const *`; the table is
+// C-allocated (void *), so the cast is made here
+static int sharesRecoverC(bk_ctx *ctx, void *parts, const int *held, const int64_t *xs, int nparts,
+                          int where, int64_t d, int poly_size, int precision,
+                          const double *global_w, int64_t *coef_out, double *delta_out,
+                          double *global_out, int64_t *bad_chunks) {
+    return bk_shares_recover(ctx, (const int64_t *const *)parts, held, xs, nparts, where, d,
+                             poly_size, precision, global_w, coef_out, delta_out, global_out,
+                             bad_chunks);
+}
 */
 import "C"
 
@@ -416,6 +427,140 @@ func createBlockEvalGPU(withAttack bool) ([]float64, float64, float64) {
 		return nil, -1, -1
 	}
 	return out, float64(errC[0]), float64(errC[1])
+}
+
+// ---- secure aggregation: shares, their sum and recovery (bk_shares_*) -------
+//
+// The share values only: the bn256 commitments and witnesses of
+// fillPolynomialMap / createShareAndWitness / aggregateSecret stay in Go.
+
+// bkSharesElems is the length of one part of the engine's store (chunks x the
+// shares this miner holds; 0: no store).
+var (
+	bkSharesElems int
+)
+
+// generateSharesGPU replaces the evaluatedValue arithmetic of
+// createSharesAndWitnesses for every chunk of deltaw (kyber.go:484-512,
+// :579-646, as called by fillPolynomialMap for generateMinerSecretShares,
+// kyber.go:456-482): y[chunk*totalShares+s] is the share at x = s - 10 of chunk
+// `chunk`; miner m's Secrets are [held*m, held*(m+1)) of each chunk
+// (extractMinerSecret, kyber.go:205-242).  nil on an engine error.
+func generateSharesGPU(deltaw []float64, precision int, polySize int, totalShares int) []int64 {
+	d := len(deltaw)
+	if bkCtx == nil || d == 0 || polySize < 1 || totalShares < 1 {
+		return nil
+	}
+	chunks := (d + polySize - 1) / polySize
+	y := make([]int64, chunks*totalShares)
+	var dp *C.double
+	var yp *C.int64_t
+	dp = (*C.double)(unsafe.Pointer(&deltaw[0]))
+	yp = (*C.int64_t)(unsafe.Pointer(&y[0]))
+	if st := C.bk_shares_generate(bkCtx, dp, C.BK_HOST, C.int64_t(d), C.int(precision), C.int(polySize), C.int(totalShares), yp); st != C.BK_OK {
+		outLog.Printf("bk_shares_generate failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return nil
+	}
+	return y
+}
+
+// beginSharesGPU empties the engine's store for a new iteration; call it where
+// the miner resets its secretList.  held: the shares of each chunk this miner
+// holds, nCap: the most clients that can register.
+func beginSharesGPU(d int, polySize int, held int, nCap int) bool {
+	bkSharesElems = 0
+	if bkCtx == nil || d == 0 || polySize < 1 {
+		return false
+	}
+	if st := C.bk_shares_begin(bkCtx, C.int64_t(d), C.int(polySize), C.int(held), C.int64_t(nCap)); st != C.BK_OK {
+		outLog.Printf("bk_shares_begin failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	bkSharesElems = (d + polySize - 1) / polySize * held
+	return true
+}
+
+// addSecretShareGPU replaces the append of addSecretShare (honest.go:338-342,
+// from Peer.RegisterSecret, main.go:256-286) for the share values: part is the
+// client's Secrets' Y of every chunk, [chunk][share].  Returns the part's slot,
+// which the caller keeps against the client's NodeID; -1 on an engine error.
+func addSecretShareGPU(part []int64) int {
+	if bkCtx == nil || bkSharesElems == 0 || len(part) != bkSharesElems {
+		return -1
+	}
+	var pp *C.int64_t
+	var slot C.int64_t
+	pp = (*C.int64_t)(unsafe.Pointer(&part[0]))
+	if st := C.bk_shares_add(bkCtx, pp, C.BK_HOST, &slot); st != C.BK_OK {
+		outLog.Printf("bk_shares_add failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return -1
+	}
+	return int(slot)
+}
+
+// getMinerPartGPU replaces the Y sums of the aggregateSecret loop in
+// getSecretShares (main.go:2157-2189, kyber.go:244-287; the reply of
+// Peer.GetMinerPart, main.go:459-485): the wrapping int64 sum of the parts in
+// `slots`, the slots of the agreed node list.  The sum also stays on the GPU as
+// the engine's own aggregate.  nil on an engine error.
+func getMinerPartGPU(slots []int64) []int64 {
+	if bkCtx == nil || bkSharesElems == 0 || len(slots) == 0 {
+		return nil
+	}
+	out := make([]int64, bkSharesElems)
+	ns := len(slots)
+	var sp, op *C.int64_t
+	sp = (*C.int64_t)(unsafe.Pointer(&slots[0]))
+	op = (*C.int64_t)(unsafe.Pointer(&out[0]))
+	if st := C.bk_shares_sum(bkCtx, sp, C.int64_t(ns), op); st != C.BK_OK {
+		outLog.Printf("bk_shares_sum failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return nil
+	}
+	return out
+}
+
+// recoverAggregateGPU replaces the recoverSecret loop of recoverAggregateUpdates
+// (honest.go:442-502, kyber.go:809-857), updateIntToFloat and the model update of
+// createBlockSecAgg (honest.go:408-409): parts[i] is miner i's aggregate
+// ([chunk][share], held[i] shares per chunk; a nil entry, at most one: this
+// miner's own, left on the GPU by getMinerPartGPU), xs the shares' X in part
+// order.  Returns the new model, the aggregate delta and the number of chunks
+// whose shares were inconsistent (their entries are 0); nil on an engine error.
+func recoverAggregateGPU(globalW []float64, parts [][]int64, held []int, xs []int64, polySize int, precision int) ([]float64, []float64, int) {
+	d := len(globalW)
+	np := len(parts)
+	if bkCtx == nil || d == 0 || np == 0 || len(held) != np || len(xs) == 0 {
+		return nil, nil, -1
+	}
+	var pinner runtime.Pinner
+	defer pinner.Unpin()
+	var tableC unsafe.Pointer
+	tableC = C.malloc(C.size_t(np) * C.size_t(unsafe.Sizeof(uintptr(0))))
+	defer C.free(tableC)
+	table := unsafe.Slice((*unsafe.Pointer)(tableC), np)
+	heldC := make([]C.int, np)
+	for i := range parts {
+		heldC[i] = C.int(held[i])
+		table[i] = nil
+		if parts[i] != nil {
+			pinner.Pin(&parts[i][0])
+			table[i] = unsafe.Pointer(&parts[i][0])
+		}
+	}
+	newW := make([]float64, d)
+	delta := make([]float64, d)
+	var wp, dp, gp *C.double
+	var xp *C.int64_t
+	var bad C.int64_t
+	wp = (*C.double)(unsafe.Pointer(&globalW[0]))
+	dp = (*C.double)(unsafe.Pointer(&delta[0]))
+	gp = (*C.double)(unsafe.Pointer(&newW[0]))
+	xp = (*C.int64_t)(unsafe.Pointer(&xs[0]))
+	if st := C.sharesRecoverC(bkCtx, tableC, &heldC[0], xp, C.int(np), C.BK_HOST, C.int64_t(d), C.int(polySize), C.int(precision), wp, nil, dp, gp, &bad); st != C.BK_OK {
+		outLog.Printf("bk_shares_recover failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return nil, nil, -1
+	}
+	return newW, delta, int(bad)
 }
 
 func noisedDeltas(updates []Update) [][]float64 {

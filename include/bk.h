@@ -937,6 +937,83 @@ int bk_block_add_finish(bk_ctx *ctx, const void *row, int accepted, int where, i
  * change of BK_ABI_VERSION (14), as bk_set_collect_wide was. */
 int bk_block_stats(bk_ctx *ctx, int64_t out[4]);
 
+/* ---- secure aggregation: miner shares, their sum and recovery -------------- */
+
+/* With SECURE_AGG (DistSys/main.go:151, the reference's default) a miner never
+ * holds a Delta: a client cuts its quantised Delta into polynomials of
+ * poly_size coefficients (makePolynomialMap, kyber.go:712-743; the last may be
+ * shorter) and sends each miner the polynomials' values at that miner's share
+ * points; the miner sums the parts of the agreed node list and the leader
+ * recovers the summed polynomials.  Share s sits at x = s - 10
+ * (pointToHashVal, kyber.go:677-695).  The bn256 commitments and witnesses are
+ * not part of this family.
+ *
+ * Layout: y_out and every part are int64 [chunk][share]; chunks =
+ * bk_shares_chunks(d, poly_size) = ceil(d / poly_size) (-1 for a bad d or
+ * poly_size); a miner's part holds `held` consecutive shares per chunk (shares
+ * [held m, held (m + 1)) of miner m, extractMinerSecret, kyber.go:205-242).
+ *
+ * bk_shares_generate: y_out[chunk][s], s < total_shares, is
+ * createShareAndWitness's evaluatedValue (kyber.go:579-646) bit for bit:
+ *     c_j = int64(delta[chunk poly_size + j] * 10^precision)     (Go's int64())
+ *     y   = sum_j int64(pow(x, j) * float64(c_j))                (wrapping)
+ *     y  += int64(r), r what dividePolynomial (kyber.go:768-793) leaves in
+ *           place 0 of the float coefficients, c_0 replaced by
+ *           float64(int64(float64(c_0)) - y), divided by (X - x)
+ * delta (d doubles) and y_out are both at `where`.  pow(x, j) is taken as the
+ * exact integer power (exact in fp64 for these x and j).
+ *
+ * bk_shares_begin: the miner's store of up to n_cap parts of chunks x held
+ * int64 (emptied; the own aggregate forgotten).  bk_shares_add: one part (at
+ * `where`) takes the next slot (*slot, nullable).  bk_shares_sum: the
+ * element-wise wrapping int64 sum of the listed slots (each at most once, host
+ * array) stays on the device as the context's own aggregate and is copied to
+ * sum_out (host, nullable): the reply to GetMinerPart (main.go:459-485).
+ *
+ * bk_shares_recover: parts[i] (at `where`; NULL, at most one: the own
+ * aggregate, whose d, poly_size and held must be the call's) holds held[i]
+ * shares per chunk, and xs (host) the sum(held) = S nodes in part order:
+ * distinct, each in [-10, 53], poly_size <= S <= 64.  Per chunk the integer
+ * polynomial through the first poly_size points is recovered exactly (Newton
+ * divided differences in 128-bit integers, every division exact) and checked
+ * modulo 2^64 against all S points.  A chunk is bad if a division leaves a
+ * remainder, a coefficient does not fit int64 or a point is not reproduced: its
+ * outputs are 0 and it is counted in *bad_chunks (host), the call still
+ * BK_OK.  coef_out (nullable, d int64), delta_out (nullable, d doubles:
+ * float64(coef) / 10^precision, updateIntToFloat kyber.go:745-757) and
+ * global_out (d doubles: global_w + that, honest.go:408-409) are at `where`,
+ * as global_w is; the short last chunk's surplus coefficients are dropped
+ * (honest.go:486-490).
+ *
+ * bk_shares_stats: since the context was made, out[0] kernel launches (one per
+ * generate, sum and recover), out[1] copy calls, out[2] calls that reached the
+ * device, out[3] bad chunks.
+ *
+ * Every entry is synchronous.  Device pointers are 8-byte aligned.  Errors:
+ * BK_EINVAL for a null ctx first, then (no state or GPU needed) a null required
+ * pointer, a bad where, d outside [1, 2^30], poly_size outside [1, 10],
+ * total_shares outside [poly_size, 64], precision outside [0, 18], held
+ * outside [1, 64], n_cap outside [1, BK_MAX_N], count < 1, nparts outside
+ * [1, 64], a bad held[i], S or xs[i] (named), two null parts; then add, count
+ * or sum without begin, a full store, a slot out of range or listed twice, a
+ * null part without a matching own aggregate.  A refused call changes nothing.
+ * The launches carry no timing id.  Added without a change of BK_ABI_VERSION
+ * (14), as bk_block_* was. */
+#define BK_SHARES_MAX_POLY   10
+#define BK_SHARES_MAX_POINTS 64
+int64_t bk_shares_chunks(int64_t d, int poly_size);
+int bk_shares_generate(bk_ctx *ctx, const double *delta, int where, int64_t d, int precision,
+                       int poly_size, int total_shares, int64_t *y_out);
+int bk_shares_begin(bk_ctx *ctx, int64_t d, int poly_size, int held, int64_t n_cap);
+int bk_shares_add(bk_ctx *ctx, const int64_t *part, int where, int64_t *slot);
+int bk_shares_count(bk_ctx *ctx, int64_t *count);
+int bk_shares_sum(bk_ctx *ctx, const int64_t *slots, int64_t count, int64_t *sum_out);
+int bk_shares_recover(bk_ctx *ctx, const int64_t *const *parts, const int *held, const int64_t *xs,
+                      int nparts, int where, int64_t d, int poly_size, int precision,
+                      const double *global_w, int64_t *coef_out, double *delta_out,
+                      double *global_out, int64_t *bad_chunks);
+int bk_shares_stats(bk_ctx *ctx, int64_t out[4]);   /* launches, copies, calls, bad chunks so far */
+
 /* Noise application (client DP step) -- requestNoiseFromNoisers
  * (DistSys/main.go:1606-1653: noiseVec = 0 + v_0 + ... + v_{k-1}, then
  * /= float64(k)) and NoisedDelta = Delta + noise (main.go:1524-1537), batched
