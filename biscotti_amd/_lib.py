@@ -32,6 +32,7 @@ K = {name: i for i, name in enumerate(ALL_KERNELS)}
 BK_RONI_ROUND_G = 8
 BK_EVAL_MAX_SETS = 4
 BK_SHARES_MAX_POLY, BK_SHARES_MAX_POINTS = 10, 64
+BK_GRAD_MAX_BATCH, BK_GRAD_MAX_D = 65536, 32768  # bk_grad_*: rows of a step; logistic d, softmax d_in
 
 # every symbol include/bk.h declares: name -> (restype, argtypes)
 _i = ctypes.c_int
@@ -116,6 +117,12 @@ SIGNATURES = {
     "bk_shares_sum": (_i, [_p, _p, _i64, _p]),
     "bk_shares_recover": (_i, [_p, _p, _p, _p, _i, _i, _i64, _i, _i, _p, _p, _p, _p, _pi64]),
     "bk_shares_stats": (_i, [_p, _pi64]),
+    "bk_grad_set_logistic": (_i, [_p, _p, _i64, _i64, _i64, _p]),
+    "bk_grad_set_softmax": (_i, [_p, _p, _i64, _i64, _i64, _p, _i64]),
+    "bk_grad_clear": (_i, [_p]),
+    "bk_grad_logistic": (_i, [_p, _p, _i, _p, _i64, _i64, _d, _d, _p, _i, _p, _p, _pd]),
+    "bk_grad_softmax": (_i, [_p, _p, _i, _p, _i64, _d, _p, _i, _p, _p, _pd, _pd]),
+    "bk_grad_stats": (_i, [_p, _pi64]),
     "bk_group_create": (_i, [ctypes.POINTER(_p), _i, _p, _i]),
     "bk_group_destroy": (None, [_p]),
     "bk_group_size": (_i, [_p]),

@@ -264,6 +264,7 @@ void bk_destroy(bk_ctx *c) {
         block_destroy(c->block);
         eval_destroy(c->eval);
         shares_destroy(c->shares);
+        grad_destroy(c->grad);
         delete c->hpool;
         if (c->copy) (void)hipStreamDestroy(c->copy);
         for (void *p : c->staged) (void)hipHostFree(p);

@@ -165,6 +165,63 @@ struct Eval {
     int64_t launches = 0, calls = 0;             // bk_eval_stats
 };
 
+// bk_grad*: the peer's resident training shard and the scratch of one gradient
+// step (bk_grad_api.hip, kernels bk_grad.hip), buffers of their
+// own: the eval sets, RONI's validation sets and live rounds never see them.
+// All grow only
+constexpr int GRAD_TILE = 256;             // batch positions per chain
+constexpr int64_t GRAD_MAX_BATCH = 65536;  // rows of one step
+constexpr int64_t GRAD_MAX_D = 32768;      // logistic d, softmax d_in
+constexpr int64_t GRAD_MAPPED_MAX = 784;   // host outputs up to here are stored into mapped memory
+struct GradOut {                           // the mapped block's head
+    double loss, norm;
+};
+struct Grad {
+    int kind = EVAL_EMPTY;    // EVAL_LOGISTIC / EVAL_SOFTMAX
+    int64_t nn = 0, d = 0;    // rows; the model's length
+    int64_t din = 0, C = 0;   // softmax: d = C (din + 1)
+    DevBuf X, y;              // compact rows (row stride d / din)
+    DevBuf w, noise, idx;     // a call's host inputs on the device
+    DevBuf R;                 // softmax: the batch's residuals, positions x 16
+    DevBuf part, lossp;       // per-tile partial sums; per-workgroup loss parts
+    DevBuf out;               // host outputs beyond GRAD_MAPPED_MAX: d doubles, then d int64
+    DevBuf cnt;               // the exit counter (zeroed once: every launch leaves it zero)
+    // mapped pinned: GradOut, then GRAD_MAPPED_MAX doubles and as many int64
+    char *hout = nullptr, *hout_dev = nullptr;
+    int64_t launches = 0, calls = 0;  // bk_grad_stats
+};
+void grad_destroy(Grad *g);
+// bk_grad.hip.  rows: the batch's row numbers on the device (null: 0 .. count-1);
+// noise / q nullable; out: the mapped GradOut's device address.  part holds
+// tiles x d doubles (logistic: only with more than one tile), lossp one double
+// per workgroup of the (forward) launch, cnt one zeroed word
+struct GradLogistic {
+    const double *X, *y, *ww, *noise;
+    const int64_t *rows;
+    int64_t count, d;
+    double batch, alpha, lammy, scale;
+    double *part, *lossp, *delta;
+    int64_t *q;
+    GradOut *out;
+    unsigned int *cnt;
+};
+hipError_t launch_grad_logistic(const GradLogistic &a, hipStream_t st);
+struct GradSoftmax {
+    const float *X;
+    const int32_t *y;
+    const double *ww, *noise;
+    const int64_t *rows;
+    int64_t count, din;
+    int C;
+    double max_norm, scale;
+    double *R, *part, *lossp, *delta;
+    int64_t *q;
+    GradOut *out;
+    unsigned int *cnt;
+};
+hipError_t launch_grad_softmax_fwd(const GradSoftmax &a, hipStream_t st);
+hipError_t launch_grad_softmax_bwd(const GradSoftmax &a, hipStream_t st);
+
 }  // namespace bk
 
 // the C ABI's opaque handle, hence at global scope; its field types are bk::'s
@@ -405,6 +462,9 @@ struct bk_ctx {
     // k_shares_gen's layout: 0 one thread per (chunk, share), 1 one thread per
     // chunk (BK_SHARES_GEN_PER_CHUNK, for tools/shares_bench.py; the same bits)
     int shares_gen_per_chunk = 0;
+    // bk_grad*: the training shard and a step's scratch (bk_grad_api.hip),
+    // created by the first bk_grad_set_*
+    bk::Grad *grad = nullptr;
 };
 
 namespace bk {

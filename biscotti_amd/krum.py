@@ -1033,6 +1033,129 @@ class Engine:
         check(lib().bk_shares_stats(self._ctx, out))
         return list(out)
 
+    # ---- the gradient step on the resident training shard (bk_grad_*) --------
+    def grad_set_logistic(self, X, y):
+        """Make (X, y) the context's training set: X nn x d float64 (a row stride
+        is kept), y the nn labels (stored as float64)."""
+        X = np.asarray(X)
+        if X.ndim != 2 or X.dtype != np.float64 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("X must be a float64 matrix, nn x d")
+        if X.shape[1] > _lib.BK_GRAD_MAX_D:
+            raise ValueError("d=%d exceeds %d" % (X.shape[1], _lib.BK_GRAD_MAX_D))
+        if X.strides[1] != 8 or X.strides[0] % 8 or X.strides[0] < 8 * X.shape[1]:
+            X = np.ascontiguousarray(X)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.shape != (X.shape[0],):
+            raise ValueError("y must have one label per row of X")
+        check(lib().bk_grad_set_logistic(self._ctx, X.ctypes.data, X.shape[0], X.shape[1],
+                                         X.strides[0] // 8, y.ctypes.data))
+        self._grad = ("logistic", X.shape[0], X.shape[1])
+
+    def grad_set_softmax(self, X, y, n_classes):
+        """X nn x d_in float32, y integer labels in [0, n_classes), 2 <= n_classes
+        <= 16; the model has n_classes * (d_in + 1) entries (W row-major, then b)."""
+        X = np.asarray(X)
+        if X.ndim != 2 or X.dtype != np.float32 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("X must be a float32 matrix, nn x d_in")
+        C = int(n_classes)
+        if not 2 <= C <= 16:
+            raise ValueError("n_classes=%d outside [2, 16]" % C)
+        if X.shape[1] > _lib.BK_GRAD_MAX_D:
+            raise ValueError("d_in=%d exceeds %d" % (X.shape[1], _lib.BK_GRAD_MAX_D))
+        if X.strides[1] != 4 or X.strides[0] % 4 or X.strides[0] < 4 * X.shape[1]:
+            X = np.ascontiguousarray(X)
+        ya = np.asarray(y)
+        if ya.shape != (X.shape[0],) or not np.issubdtype(ya.dtype, np.integer):
+            raise ValueError("y must have one integer label per row of X")
+        if ya.min() < 0 or ya.max() >= C:
+            raise ValueError("labels outside [0, %d)" % C)
+        y32 = np.ascontiguousarray(ya, dtype=np.int32)
+        check(lib().bk_grad_set_softmax(self._ctx, X.ctypes.data, X.shape[0], X.shape[1],
+                                        X.strides[0] // 4, y32.ctypes.data, C))
+        self._grad = ("softmax", X.shape[0], C * (X.shape[1] + 1))
+
+    def grad_clear(self):
+        check(lib().bk_grad_clear(self._ctx))
+        self._grad = None
+
+    def _grad_args(self, kind, ww, idx, noise, precision):
+        """The host arrays of a gradient call, validated: (w, idx or None, noise
+        or None, precision or -1, delta, q or None)."""
+        st = getattr(self, "_grad", None)
+        if not st or st[0] != kind:
+            raise ValueError("no resident %s training set: call grad_set_%s" % (kind, kind))
+        _, nn, d = st
+        w = np.ascontiguousarray(ww, dtype=np.float64)
+        if w.shape != (d,):
+            raise ValueError("ww must be a float64 vector of %d entries" % d)
+        ix = None
+        if idx is not None:
+            ia = np.asarray(idx)
+            if ia.ndim != 1 or ia.shape[0] < 1 or not np.issubdtype(ia.dtype, np.integer):
+                raise ValueError("idx must be a non-empty 1-D integer array")
+            if ia.min() < 0 or ia.max() >= nn:
+                raise ValueError("idx outside [0, %d)" % nn)
+            ix = np.ascontiguousarray(ia, dtype=np.int64)
+        if (nn if ix is None else ix.shape[0]) > _lib.BK_GRAD_MAX_BATCH:
+            raise ValueError("a batch of more than %d rows" % _lib.BK_GRAD_MAX_BATCH)
+        nz = None
+        if noise is not None:
+            nz = np.ascontiguousarray(noise, dtype=np.float64)
+            if nz.shape != (d,):
+                raise ValueError("noise must be a float64 vector of %d entries" % d)
+        p = -1 if precision is None else int(precision)
+        if not -1 <= p <= 18:
+            raise ValueError("precision=%d outside [0, 18]" % p)
+        return w, ix, nz, p, np.empty(d), (np.empty(d, dtype=np.int64) if p >= 0 else None)
+
+    def grad_logistic(self, ww, idx=None, batch_size=10, alpha=1e-2, lammy=0.01, noise=None,
+                      precision=None):
+        """privateFun of the logistic model on the rows idx of the resident set
+        (None: all of them): (delta, q or None, loss)."""
+        if int(batch_size) < 1:
+            raise ValueError("batch_size=%d < 1" % int(batch_size))
+        w, ix, nz, p, delta, q = self._grad_args("logistic", ww, idx, noise, precision)
+        loss = ctypes.c_double()
+        self.grad_logistic_ptr(w.ctypes.data, _lib.BK_HOST, ix, batch_size, alpha, lammy, _ptr(nz),
+                               p, delta.ctypes.data, _ptr(q), loss)
+        return delta, q, loss.value
+
+    def grad_logistic_ptr(self, ww_ptr, where, idx, batch_size, alpha, lammy, noise_ptr, precision,
+                          delta_ptr, q_ptr, loss=None):
+        """The model, noise and outputs by raw pointer (pageable, pinned or
+        device memory); idx an int64 numpy array or None; loss a ctypes.c_double."""
+        check(lib().bk_grad_logistic(self._ctx, _p(ww_ptr), int(where), _p(_ptr(idx)),
+                                     0 if idx is None else int(idx.shape[0]), int(batch_size),
+                                     float(alpha), float(lammy), _p(noise_ptr), int(precision),
+                                     _p(delta_ptr), _p(q_ptr),
+                                     ctypes.byref(loss) if loss is not None else None))
+
+    def grad_softmax(self, ww, idx=None, max_norm=100.0, noise=None, precision=None):
+        """privateFun of the torch softmax model: (delta, q or None, loss, norm
+        before clipping)."""
+        mn = float(max_norm)
+        if not (np.isfinite(mn) and mn > 0.0):
+            raise ValueError("max_norm must be a positive finite number")
+        w, ix, nz, p, delta, q = self._grad_args("softmax", ww, idx, noise, precision)
+        loss, norm = ctypes.c_double(), ctypes.c_double()
+        self.grad_softmax_ptr(w.ctypes.data, _lib.BK_HOST, ix, mn, _ptr(nz), p, delta.ctypes.data,
+                              _ptr(q), loss, norm)
+        return delta, q, loss.value, norm.value
+
+    def grad_softmax_ptr(self, ww_ptr, where, idx, max_norm, noise_ptr, precision, delta_ptr, q_ptr,
+                         loss=None, norm=None):
+        check(lib().bk_grad_softmax(self._ctx, _p(ww_ptr), int(where), _p(_ptr(idx)),
+                                    0 if idx is None else int(idx.shape[0]), float(max_norm),
+                                    _p(noise_ptr), int(precision), _p(delta_ptr), _p(q_ptr),
+                                    ctypes.byref(loss) if loss is not None else None,
+                                    ctypes.byref(norm) if norm is not None else None))
+
+    def grad_stats(self):
+        """[kernel launches, gradient calls] of bk_grad_* since the engine was made."""
+        out = (ctypes.c_int64 * 2)()
+        check(lib().bk_grad_stats(self._ctx, out))
+        return list(out)
+
     def noise_apply_ptr(self, delta_ptr, n, d, ld, noise_ptr, k, noise_ld, out_ptr, out_ld):
         check(lib().bk_noise_apply_device(self._ctx, _p(delta_ptr), n, d, ld, _p(noise_ptr), k,
                                           noise_ld, _p(out_ptr), out_ld))

@@ -563,6 +563,103 @@ func recoverAggregateGPU(globalW []float64, parts [][]int64, held []int, xs []in
 	return newW, delta, int(bad)
 }
 
+// ---- the gradient step on the peer's resident shard (bk_grad_*) -------------
+
+// The shard's model length (0: no shard), its kind and the step's constants
+// (logistic_model.py's alpha and lammy, client.py's clip_grad_norm bound).
+// bkGradNoise, when non-nil, is getNoise(iteration) as the caller computed it
+// for the next step (d entries); the engine adds it to the delta.
+var (
+	bkGradDim       int
+	bkGradSoftmax   bool
+	bkGradBatch     int
+	bkGradPrecision int
+	bkGradAlpha     float64 = 1e-2
+	bkGradLammy     float64 = 0.01
+	bkGradMaxNorm   float64 = 100.0
+	bkGradNoise     []float64
+)
+
+// initGradGPU makes the peer's training shard resident; call it once at pyInit.
+// classes == 0: the logistic model, X nn x d row-major with labels y.  Else the
+// torch softmax model, X32 nn x d float32 with labels y32 in [0, classes).
+// batchSize is the reference's this_batch_size (the logistic divisor),
+// precision the commitment's (updateFloatToInt).
+func initGradGPU(X []float64, y []float64, X32 []float32, y32 []int32, d int, classes int, batchSize int, precision int) bool {
+	bkGradDim = 0
+	if bkCtx == nil || d == 0 || batchSize < 1 {
+		return false
+	}
+	if classes == 0 {
+		nn := len(y)
+		if nn == 0 || len(X) != nn*d {
+			return false
+		}
+		var xp, yp *C.double
+		xp = (*C.double)(unsafe.Pointer(&X[0]))
+		yp = (*C.double)(unsafe.Pointer(&y[0]))
+		if st := C.bk_grad_set_logistic(bkCtx, xp, C.int64_t(nn), C.int64_t(d), C.int64_t(d), yp); st != C.BK_OK {
+			outLog.Printf("bk_grad_set_logistic failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+			return false
+		}
+		bkGradDim = d
+	} else {
+		nn := len(y32)
+		if nn == 0 || len(X32) != nn*d {
+			return false
+		}
+		var xfp *C.float
+		var yip *C.int32_t
+		xfp = (*C.float)(unsafe.Pointer(&X32[0]))
+		yip = (*C.int32_t)(unsafe.Pointer(&y32[0]))
+		if st := C.bk_grad_set_softmax(bkCtx, xfp, C.int64_t(nn), C.int64_t(d), C.int64_t(d), yip, C.int64_t(classes)); st != C.BK_OK {
+			outLog.Printf("bk_grad_set_softmax failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+			return false
+		}
+		bkGradDim = classes * (d + 1)
+	}
+	bkGradSoftmax = classes != 0
+	bkGradBatch = batchSize
+	bkGradPrecision = precision
+	return true
+}
+
+// oneGradientStepGPU replaces oneGradientStep and the updateFloatToInt behind it
+// in computeUpdate (honest.go:165-200, 284-324): the delta of the model globalW
+// on the rows idx of the shard (the mini-batch the caller drew; nil: every row)
+// and its quantisation.  nil, nil on an engine error.
+func oneGradientStepGPU(globalW []float64, idx []int64) ([]float64, []int64) {
+	d := len(globalW)
+	if bkCtx == nil || d == 0 || d != bkGradDim {
+		return nil, nil
+	}
+	delta := make([]float64, d)
+	q := make([]int64, d)
+	var wp, dp, np *C.double
+	var qp, ip *C.int64_t
+	wp = (*C.double)(unsafe.Pointer(&globalW[0]))
+	dp = (*C.double)(unsafe.Pointer(&delta[0]))
+	qp = (*C.int64_t)(unsafe.Pointer(&q[0]))
+	if len(bkGradNoise) == d {
+		np = (*C.double)(unsafe.Pointer(&bkGradNoise[0]))
+	}
+	count := len(idx)
+	if count > 0 {
+		ip = (*C.int64_t)(unsafe.Pointer(&idx[0]))
+	}
+	var st C.int
+	if bkGradSoftmax {
+		st = C.bk_grad_softmax(bkCtx, wp, C.BK_HOST, ip, C.int64_t(count), C.double(bkGradMaxNorm), np, C.int(bkGradPrecision), dp, qp, nil, nil)
+	} else {
+		st = C.bk_grad_logistic(bkCtx, wp, C.BK_HOST, ip, C.int64_t(count), C.int64_t(bkGradBatch), C.double(bkGradAlpha), C.double(bkGradLammy), np, C.int(bkGradPrecision), dp, qp, nil)
+	}
+	if st != C.BK_OK {
+		outLog.Printf("bk_grad failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return nil, nil
+	}
+	return delta, q
+}
+
 func noisedDeltas(updates []Update) [][]float64 {
 	deltas := make([][]float64, len(updates))
 	for i := range updates {

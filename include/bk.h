@@ -1014,6 +1014,68 @@ int bk_shares_recover(bk_ctx *ctx, const int64_t *const *parts, const int *held,
                       double *global_out, int64_t *bad_chunks);
 int bk_shares_stats(bk_ctx *ctx, int64_t out[4]);   /* launches, copies, calls, bad chunks so far */
 
+/* The gradient step -- computeUpdate -> oneGradientStep (DistSys/
+ * honest.go:165-200, 284-324): privateFun of ML/code/logistic_model.py:92-140
+ * (creditcard) or ML/Pytorch/client_obj.py:73-77 -> client.py:38-65 (the torch
+ * softmax model), followed by updateFloatToInt (honest.go:183).  A context
+ * holds ONE resident training set, the peer's shard, in buffers of its own: no
+ * bk_grad* call touches an evaluation set, a validation set or a live round.
+ *   bk_grad_set_logistic  X nn x d fp64 (row stride ldx), y the nn labels.
+ *   bk_grad_set_softmax   X nn x d_in fp32 (row stride ldx), y int32 labels in
+ *                         [0, n_classes), 2 <= n_classes <= 16; the model has
+ *                         d = n_classes (d_in + 1) entries (W row-major, then b).
+ *   bk_grad_clear         empties the set.
+ * The two gradient calls are synchronous.  `where` (BK_HOST, BK_HOST_PINNED or
+ * BK_DEVICE) holds for ww, noise, delta_out and q_out together, d entries
+ * each.  idx is a HOST array of count row numbers of the set, taken in the
+ * order given, repeats allowed (the caller draws them, as np.random.choice and
+ * the shuffled loader do); NULL: rows 0 .. nn-1 (count is ignored).  noise
+ * (nullable) is getNoise(iteration) as the caller computed it.  precision < 0:
+ * no quantisation (q_out must be NULL); else q_out[j] (nullable) =
+ * int64(delta_out[j] * 10^precision) by bk_quantized_sum_device's rule.
+ * loss_out / norm_out are host scalars, nullable.
+ *   bk_grad_logistic  z_i = the fp64 FMA chain over k ascending from +0.0 of
+ *     X[r_i][k] ww[k] (bk_eval's dot), t_i = y_i z_i, res_i = -y_i / (1 +
+ *     e^{t_i}); S_j = the sum over tiles of 256 batch positions, ascending, of
+ *     each tile's FMA chain over its positions ascending from +0.0 of
+ *     X[r_i][j] res_i; delta_j = -alpha (S_j / batch_size + lammy ww_j)
+ *     [+ noise_j], every operation rounded on its own.  batch_size is the
+ *     reference's divisor, independent of count.  loss = sum logaddexp(0,
+ *     -t_i) + 0.5 lammy ww.ww.
+ *   bk_grad_softmax   ww rounded to fp32 as bk_eval stages it; logits in fp64
+ *     (k ascending, plus the bias), p = softmax over c ascending, r_ic = p_ic -
+ *     [y_i = c]; G_ck = (sum over tiles of the chains of r_ic x_ik) / count,
+ *     gb_c likewise with x = 1; norm = sqrt of the sum of all squares (entry e
+ *     in lane e mod 256's sum, then a fixed tree); every entry times
+ *     max_norm / (norm + 1e-6) where that is below 1; delta = -g [+ noise].
+ *     loss = the mean cross-entropy; norm_out: the norm before clipping.
+ * A NaN in ww gives an all-NaN delta_out and BK_OK.  The results never depend
+ * on the grid or on timing.
+ *   bk_grad_stats  out[0]: kernel launches (one per logistic call, two per
+ *                  softmax call), out[1]: gradient calls, since the context
+ *                  was made.
+ * Checked in this order, before any copy or launch: BK_EINVAL for a null ctx,
+ * ww or delta_out or a bad where; for precision > 18 or q_out with precision <
+ * 0; for batch_size < 1 / a max_norm that is not finite and positive; for no
+ * resident set or one of the other kind; for count < 1 with idx; for an idx
+ * entry outside [0, nn) (its position named); BK_ENOTSUP for a batch of more
+ * than 65,536 rows.  bk_grad_set_*: BK_EINVAL for nn < 1, d < 1, ldx < d,
+ * n_classes < 2, a null X or y, a label outside [0, n_classes) (the sample
+ * named); then BK_ENOTSUP for nn > 2^31, n_classes > 16, d (d_in) > 32,768.
+ * Added without a change of BK_ABI_VERSION (14). */
+int bk_grad_set_logistic(bk_ctx *ctx, const double *X, int64_t nn, int64_t d, int64_t ldx,
+                         const double *y);
+int bk_grad_set_softmax(bk_ctx *ctx, const float *X, int64_t nn, int64_t d_in, int64_t ldx,
+                        const int32_t *y, int64_t n_classes);
+int bk_grad_clear(bk_ctx *ctx);
+int bk_grad_logistic(bk_ctx *ctx, const double *ww, int where, const int64_t *idx, int64_t count,
+                     int64_t batch_size, double alpha, double lammy, const double *noise,
+                     int precision, double *delta_out, int64_t *q_out, double *loss_out);
+int bk_grad_softmax(bk_ctx *ctx, const double *ww, int where, const int64_t *idx, int64_t count,
+                    double max_norm, const double *noise, int precision, double *delta_out,
+                    int64_t *q_out, double *loss_out, double *norm_out);
+int bk_grad_stats(bk_ctx *ctx, int64_t out[2]);   /* launches, calls so far */
+
 /* Noise application (client DP step) -- requestNoiseFromNoisers
  * (DistSys/main.go:1606-1653: noiseVec = 0 + v_0 + ... + v_{k-1}, then
  * /= float64(k)) and NoisedDelta = Delta + noise (main.go:1524-1537), batched
