@@ -117,6 +117,12 @@ SIGNATURES = {
     "bk_shares_sum": (_i, [_p, _p, _i64, _p]),
     "bk_shares_recover": (_i, [_p, _p, _p, _p, _i, _i, _i64, _i, _i, _p, _p, _p, _p, _pi64]),
     "bk_shares_stats": (_i, [_p, _pi64]),
+    "bk_commit_set_key": (_i, [_p, _p, _i64]),
+    "bk_commit_key_count": (_i, [_p, _pi64]),
+    "bk_commit_msm": (_i, [_p, _p, _i, _i64, _i64, _p]),
+    "bk_commit_verify": (_i, [_p, _p, _i, _i64, _i64, _p, ctypes.POINTER(_i)]),
+    "bk_commit_generate": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _p, _p, _p]),
+    "bk_commit_stats": (_i, [_p, _pi64]),
     "bk_grad_set_logistic": (_i, [_p, _p, _i64, _i64, _i64, _p]),
     "bk_grad_set_softmax": (_i, [_p, _p, _i64, _i64, _i64, _p, _i64]),
     "bk_grad_clear": (_i, [_p]),

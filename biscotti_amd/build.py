@@ -20,7 +20,8 @@ SOURCES = ["bk_gram.hip", "bk_small.hip", "bk_scores.hip", "bk_mean.hip", "bk_sm
            "bk_aggregate.hip", "bk_roni.hip", "bk_plan.hip", "bk_i8.hip", "bk_collect.hip", "bk_collect_batch.hip",
            "bk_collect_ragged.hip", "bk_collect_wide.hip", "bk_collect_noise.hip", "bk_collect_arrive.hip", "bk_collect_arrive_noised.hip", "bk_collect_arrive_wide.hip", "bk_collect_tiny.hip", "bk_api.hip", "bk_stage.hip", "bk_host.hip",
            "bk_comm.hip", "bk_group.hip", "bk_entries.hip", "bk_batch.hip", "bk_block.hip", "bk_block_api.hip", "bk_eval.hip",
-           "bk_shares.hip", "bk_shares_api.hip", "bk_grad.hip", "bk_grad_api.hip"]
+           "bk_shares.hip", "bk_shares_api.hip", "bk_grad.hip", "bk_grad_api.hip",
+           "bk_commit.hip", "bk_commit_api.hip"]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",

@@ -265,6 +265,7 @@ void bk_destroy(bk_ctx *c) {
         eval_destroy(c->eval);
         shares_destroy(c->shares);
         grad_destroy(c->grad);
+        commit_destroy(c->commit);
         delete c->hpool;
         if (c->copy) (void)hipStreamDestroy(c->copy);
         for (void *p : c->staged) (void)hipHostFree(p);

@@ -222,6 +222,44 @@ struct GradSoftmax {
 hipError_t launch_grad_softmax_fwd(const GradSoftmax &a, hipStream_t st);
 hipError_t launch_grad_softmax_bwd(const GradSoftmax &a, hipStream_t st);
 
+// bk_commit_*: the resident commitment key of a context and a call's scratch
+// (bk_commit_api.hip, kernels bk_commit.hip).  table: per key
+// point its multiples 1 .. 8, affine, in Montgomery form (512 bytes); replaced
+// only by a bk_commit_set_key that succeeds.  The other buffers grow only
+constexpr int64_t COMMIT_MAX_KEY = (int64_t)1 << 22;  // key points (a 2 GiB table)
+constexpr int COMMIT_MAX_GROUPS = 256;                // workgroups of one k_commit_msm
+constexpr int COMMIT_MSM_TERMS = 4;                   // terms per thread it aims at
+struct Commit {
+    uint32_t *table = nullptr;
+    int64_t count = 0;
+    DevBuf in, out;    // a call's host scalars / delta and outputs on the device
+    DevBuf part, cnt;  // the workgroups' sums; the exit counter (zeroed once: every launch leaves it zero)
+    DevBuf bad;        // set_key: the smallest invalid index
+    // bk_commit_stats: launches, copy calls, calls that reached the device
+    int64_t stats[3] = {0, 0, 0};
+    // the terms per thread k_commit_msm's grid aims at (BK_COMMIT_MSM_TERMS, read
+    // when the state is made, for tools/commit_bench.py; the same bytes)
+    int terms = COMMIT_MSM_TERMS;
+};
+void commit_destroy(Commit *cm);
+// bk_commit.hip.  Every pointer is device memory.  Exactly one of delta / q is
+// non-null: the scalars are q, or int64(delta * scale) by Go's conversion.
+// table points at the first key point's entry.  pk: count x 64 bytes, 4-byte
+// aligned; *bad (preset to all ones) takes the smallest invalid index
+hipError_t launch_commit_key(const uint8_t *pk, int64_t count, uint32_t *table,
+                             unsigned long long *bad, hipStream_t st);
+// part: commit_msm_groups(n, terms) x 24 words; cnt one zeroed word; out 64 bytes
+int commit_msm_groups(int64_t n, int terms);
+hipError_t launch_commit_msm(const double *delta, const int64_t *q, double scale, int64_t n,
+                             const uint32_t *table, uint32_t *part, unsigned int *cnt,
+                             uint8_t *out, int terms, hipStream_t st);
+// out: chunks x 64 bytes / chunks x T x 64 bytes, chunks = ceil(d / P)
+hipError_t launch_commit_chunks(const double *delta, const int64_t *q, double scale, int64_t d,
+                                int P, const uint32_t *table, uint8_t *out, hipStream_t st);
+hipError_t launch_commit_witness(const double *delta, const int64_t *q, double scale, int64_t d,
+                                 int P, int T, const uint32_t *table, uint8_t *out,
+                                 hipStream_t st);
+
 }  // namespace bk
 
 // the C ABI's opaque handle, hence at global scope; its field types are bk::'s
@@ -465,6 +503,9 @@ struct bk_ctx {
     // bk_grad*: the training shard and a step's scratch (bk_grad_api.hip),
     // created by the first bk_grad_set_*
     bk::Grad *grad = nullptr;
+    // bk_commit_*: the commitment key and a call's scratch (bk_commit_api.hip),
+    // created by the first bk_commit_set_key
+    bk::Commit *commit = nullptr;
 };
 
 namespace bk {

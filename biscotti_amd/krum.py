@@ -1033,6 +1033,103 @@ class Engine:
         check(lib().bk_shares_stats(self._ctx, out))
         return list(out)
 
+    # ---- polynomial commitments in bn256 G1 (bk_commit_*) ---------------------
+    def commit_set_key(self, points):
+        """Make PKG1 the context's resident key: count x 64 marshalled bytes
+        (bytes, or a uint8 array of shape (count, 64))."""
+        a = np.frombuffer(points, dtype=np.uint8) if isinstance(points, (bytes, bytearray)) \
+            else np.asarray(points)
+        if a.dtype != np.uint8 or a.size < 64 or a.size % 64 or a.ndim > 2 or \
+                (a.ndim == 2 and a.shape[1] != 64):
+            raise ValueError("the key must be count x 64 bytes")
+        a = np.ascontiguousarray(a)
+        check(lib().bk_commit_set_key(self._ctx, a.ctypes.data, a.size // 64))
+        self._commit_key = a.size // 64
+
+    def commit_key_count(self):
+        n = ctypes.c_int64(-1)
+        check(lib().bk_commit_key_count(self._ctx, ctypes.byref(n)))
+        return n.value
+
+    def _commit_scalars(self, scalars, first):
+        s = np.asarray(scalars)
+        if s.ndim != 1 or s.shape[0] < 1 or s.dtype != np.int64:
+            raise ValueError("the scalars must be a non-empty 1-D int64 array")
+        first = int(first)
+        count = getattr(self, "_commit_key", None)
+        if count is None:
+            raise ValueError("no commitment key: commit_set_key first")
+        if first < 0 or first + s.shape[0] > count:
+            raise ValueError("key points [%d, %d) outside the key's %d"
+                             % (first, first + s.shape[0], count))
+        return np.ascontiguousarray(s), first
+
+    def commit_msm(self, scalars, first=0):
+        """createCommitment(scalars, PKG1[first:first + n]): 64 bytes."""
+        s, first = self._commit_scalars(scalars, first)
+        out = np.empty(64, dtype=np.uint8)
+        self.commit_msm_ptr(s.ctypes.data, _lib.BK_HOST, s.shape[0], first, out.ctypes.data)
+        return out.tobytes()
+
+    def commit_msm_ptr(self, scalars_ptr, where, n, first, out_ptr):
+        """scalars and the 64 output bytes by raw pointer, both at `where`."""
+        check(lib().bk_commit_msm(self._ctx, _p(scalars_ptr), int(where), int(n), int(first),
+                                  _p(out_ptr)))
+
+    def commit_verify(self, scalars, committed, first=0):
+        """verifyCommitment: whether the commitment's bytes equal `committed`."""
+        s, first = self._commit_scalars(scalars, first)
+        c = np.frombuffer(bytes(committed), dtype=np.uint8)
+        if c.shape[0] != 64:
+            raise ValueError("a committed point is 64 bytes")
+        ok = ctypes.c_int(-1)
+        check(lib().bk_commit_verify(self._ctx, s.ctypes.data, _lib.BK_HOST, s.shape[0], first,
+                                     c.ctypes.data, ctypes.byref(ok)))
+        return bool(ok.value)
+
+    def commit_generate(self, update, precision=4, poly_size=10, total_shares=20, want_commit=True,
+                        want_chunks=True, want_witnesses=True):
+        """generateMinerSecretShares' commitments of a 1-D update: float64 (a
+        delta, quantised with `precision`) or int64 (taken as it is).  Returns
+        (commitment: 64 uint8, chunk commitments: chunks x 64, witnesses:
+        chunks x total_shares x 64), None for what was not wanted."""
+        a = np.asarray(update)
+        if a.ndim != 1 or a.dtype not in (np.float64, np.int64):
+            raise ValueError("the update must be a 1-D float64 or int64 array")
+        a = a if a.flags.c_contiguous else np.ascontiguousarray(a)
+        d, P, p, chunks = self._shares_shape(a.shape[0] if a.shape[0] else 0, poly_size, precision)
+        T = int(total_shares)
+        if not P <= T <= _lib.BK_SHARES_MAX_POINTS:
+            raise ValueError("total_shares=%d outside [poly_size=%d, %d]"
+                             % (T, P, _lib.BK_SHARES_MAX_POINTS))
+        if not (want_commit or want_chunks or want_witnesses):
+            raise ValueError("no output requested")
+        count = getattr(self, "_commit_key", None)
+        if count is None:
+            raise ValueError("no commitment key: commit_set_key first")
+        if d > count:
+            raise ValueError("d=%d exceeds the key's %d points" % (d, count))
+        com = np.empty(64, dtype=np.uint8) if want_commit else None
+        chk = np.empty((chunks, 64), dtype=np.uint8) if want_chunks else None
+        wit = np.empty((chunks, T, 64), dtype=np.uint8) if want_witnesses else None
+        is_q = a.dtype == np.int64
+        self.commit_generate_ptr(None if is_q else a.ctypes.data, a.ctypes.data if is_q else None,
+                                 _lib.BK_HOST, d, p, P, T, _ptr(com), _ptr(chk), _ptr(wit))
+        return com, chk, wit
+
+    def commit_generate_ptr(self, delta_ptr, q_ptr, where, d, precision, poly_size, total_shares,
+                            commit_ptr, chunk_ptr, witness_ptr):
+        """Raw pointers, all at `where`; exactly one of delta_ptr / q_ptr."""
+        check(lib().bk_commit_generate(self._ctx, _p(delta_ptr), _p(q_ptr), int(where), int(d),
+                                       int(precision), int(poly_size), int(total_shares),
+                                       _p(commit_ptr), _p(chunk_ptr), _p(witness_ptr)))
+
+    def commit_stats(self):
+        """[kernel launches, copy calls, calls, key points] of bk_commit_*."""
+        out = (ctypes.c_int64 * 4)()
+        check(lib().bk_commit_stats(self._ctx, out))
+        return list(out)
+
     # ---- the gradient step on the resident training shard (bk_grad_*) --------
     def grad_set_logistic(self, X, y):
         """Make (X, y) the context's training set: X nn x d float64 (a row stride

@@ -43,6 +43,8 @@ import (
 	"runtime"
 	"strconv"
 	"unsafe"
+
+	"github.com/dedis/kyber"
 )
 
 var (
@@ -431,8 +433,9 @@ func createBlockEvalGPU(withAttack bool) ([]float64, float64, float64) {
 
 // ---- secure aggregation: shares, their sum and recovery (bk_shares_*) -------
 //
-// The share values only: the bn256 commitments and witnesses of
-// fillPolynomialMap / createShareAndWitness / aggregateSecret stay in Go.
+// The share values only: the G1 commitments and witnesses of fillPolynomialMap /
+// createShareAndWitness are the bk_commit_* section's below; aggregateSecret's
+// point sums stay in Go.
 
 // bkSharesElems is the length of one part of the engine's store (chunks x the
 // shares this miner holds; 0: no store).
@@ -561,6 +564,140 @@ func recoverAggregateGPU(globalW []float64, parts [][]int64, held []int, xs []in
 		return nil, nil, -1
 	}
 	return newW, delta, int(bad)
+}
+
+// ---- polynomial commitments in bn256 G1 (bk_commit_*) -----------------------
+//
+// The G1 side only: aggregateSecret's point sums, verifySecret's pairings and the
+// Schnorr signatures stay in Go.  A point crosses as its MarshalBinary bytes.
+
+// bkCommitKey is the number of key points resident in the engine (0: none).
+var (
+	bkCommitKey int
+)
+
+// pointFromBytesGPU is UnmarshalBinary of one 64-byte point (nil on an error).
+func pointFromBytesGPU(buf []byte) kyber.Point {
+	p := suite.G1().Point()
+	if err := p.UnmarshalBinary(buf); err != nil {
+		outLog.Printf("bn256 point from the engine does not unmarshal: %s", err)
+		return nil
+	}
+	return p
+}
+
+// setCommitKeyGPU makes pkG1 the engine's resident key; call it once where the
+// peer loads its PublicKey (extractKeys, before the first computeUpdate).
+func setCommitKeyGPU(pkG1 []kyber.Point) bool {
+	bkCommitKey = 0
+	count := len(pkG1)
+	if bkCtx == nil || count == 0 {
+		return false
+	}
+	raw := make([]byte, 0, 64*count)
+	for _, p := range pkG1 {
+		b, err := p.MarshalBinary()
+		if err != nil || len(b) != 64 {
+			return false
+		}
+		raw = append(raw, b...)
+	}
+	var rp *C.uint8_t
+	rp = (*C.uint8_t)(unsafe.Pointer(&raw[0]))
+	if st := C.bk_commit_set_key(bkCtx, rp, C.int64_t(count)); st != C.BK_OK {
+		outLog.Printf("bk_commit_set_key failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	bkCommitKey = count
+	return true
+}
+
+// createCommitmentGPU replaces createCommitment(update, pkey.PKG1[first:first+len(update)])
+// (kyber.go:533-562): computeUpdate's `createCommitment(deltasInt, pkey.PKG1)`
+// (honest.go:186) becomes createCommitmentGPU(deltasInt, 0).  nil on an error.
+func createCommitmentGPU(update []int64, first int) kyber.Point {
+	n := len(update)
+	if bkCtx == nil || n == 0 || first < 0 || first+n > bkCommitKey {
+		return nil
+	}
+	out := make([]byte, 64)
+	var up *C.int64_t
+	var op *C.uint8_t
+	up = (*C.int64_t)(unsafe.Pointer(&update[0]))
+	op = (*C.uint8_t)(unsafe.Pointer(&out[0]))
+	if st := C.bk_commit_msm(bkCtx, up, C.BK_HOST, C.int64_t(n), C.int64_t(first), op); st != C.BK_OK {
+		outLog.Printf("bk_commit_msm failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return nil
+	}
+	return pointFromBytesGPU(out)
+}
+
+// verifyCommitmentGPU replaces verifyCommitment (kyber.go:564-577) over
+// pkey.PKG1[first:first+len(update)].
+func verifyCommitmentGPU(update []int64, first int, committedUpdate kyber.Point) bool {
+	n := len(update)
+	if bkCtx == nil || n == 0 || first < 0 || first+n > bkCommitKey {
+		return false
+	}
+	want, err := committedUpdate.MarshalBinary()
+	if err != nil || len(want) != 64 {
+		return false
+	}
+	var up *C.int64_t
+	var wp *C.uint8_t
+	var ok C.int
+	up = (*C.int64_t)(unsafe.Pointer(&update[0]))
+	wp = (*C.uint8_t)(unsafe.Pointer(&want[0]))
+	if st := C.bk_commit_verify(bkCtx, up, C.BK_HOST, C.int64_t(n), C.int64_t(first), wp, &ok); st != C.BK_OK {
+		outLog.Printf("bk_commit_verify failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	return ok == 1
+}
+
+// fillPolynomialMapGPU replaces the G1 arithmetic of generateMinerSecretShares
+// (kyber.go:456-482): its CommitmentUpdate (the first result), and for
+// fillPolynomialMap (kyber.go:172-202) each chunk's Commitment (the second,
+// [chunk]) and Witnesses (the third, [chunk][share]; createShareAndWitness,
+// kyber.go:579-646).  The Secrets come from generateSharesGPU.  nil on an error.
+func fillPolynomialMapGPU(deltaw []float64, precision int, polySize int, totalShares int) (kyber.Point, []kyber.Point, [][]kyber.Point) {
+	d := len(deltaw)
+	if bkCtx == nil || d == 0 || d > bkCommitKey || polySize < 1 || totalShares < 1 {
+		return nil, nil, nil
+	}
+	chunks := (d + polySize - 1) / polySize
+	whole := make([]byte, 64)
+	chunkRaw := make([]byte, 64*chunks)
+	witRaw := make([]byte, 64*chunks*totalShares)
+	var dp *C.double
+	var cp, kp, wp *C.uint8_t
+	dp = (*C.double)(unsafe.Pointer(&deltaw[0]))
+	cp = (*C.uint8_t)(unsafe.Pointer(&whole[0]))
+	kp = (*C.uint8_t)(unsafe.Pointer(&chunkRaw[0]))
+	wp = (*C.uint8_t)(unsafe.Pointer(&witRaw[0]))
+	if st := C.bk_commit_generate(bkCtx, dp, nil, C.BK_HOST, C.int64_t(d), C.int(precision), C.int(polySize), C.int(totalShares), cp, kp, wp); st != C.BK_OK {
+		outLog.Printf("bk_commit_generate failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return nil, nil, nil
+	}
+	commitment := pointFromBytesGPU(whole)
+	if commitment == nil {
+		return nil, nil, nil
+	}
+	chunkPoints := make([]kyber.Point, chunks)
+	witnesses := make([][]kyber.Point, chunks)
+	for c := 0; c < chunks; c++ {
+		if chunkPoints[c] = pointFromBytesGPU(chunkRaw[64*c : 64*c+64]); chunkPoints[c] == nil {
+			return nil, nil, nil
+		}
+		witnesses[c] = make([]kyber.Point, totalShares)
+		for s := 0; s < totalShares; s++ {
+			o := 64 * (c*totalShares + s)
+			if witnesses[c][s] = pointFromBytesGPU(witRaw[o : o+64]); witnesses[c][s] == nil {
+				return nil, nil, nil
+			}
+		}
+	}
+	return commitment, chunkPoints, witnesses
 }
 
 // ---- the gradient step on the peer's resident shard (bk_grad_*) -------------

@@ -1014,6 +1014,71 @@ int bk_shares_recover(bk_ctx *ctx, const int64_t *const *parts, const int *held,
                       double *global_out, int64_t *bad_chunks);
 int bk_shares_stats(bk_ctx *ctx, int64_t out[4]);   /* launches, copies, calls, bad chunks so far */
 
+/* ---- polynomial commitments in bn256 G1 ----------------------------------- */
+
+/* The commitments a peer computes in an iteration (DistSys/kyber.go): the
+ * curve is y^2 = x^3 + 3 over GF(p), p =
+ * 65000549695646603732796438742359905742825358107623003571877145026864184071783,
+ * of prime order n =
+ * 65000549695646603732796438742359905742570406053903786389881062969044166799969.
+ * A point is the 64 bytes of pointG1.MarshalBinary: affine x, then y, 32 bytes
+ * each, big-endian; infinity is 64 zero bytes.  The arithmetic is in integers,
+ * so every output is the reference's bit for bit whatever the order of the
+ * additions.
+ *
+ * bk_commit_set_key: the context's resident key PKG1 (pk: count x 64 bytes,
+ * host).  Every point is unmarshalled and validated on the device -- a
+ * coordinate >= p or a point off the curve refuses the key (BK_EINVAL,
+ * bk_last_error names the smallest such index) and leaves the resident key as
+ * it was -- and kept with its multiples 1 .. 8 (512 bytes per point).
+ * bk_commit_key_count: the resident key's points (0: none).
+ *
+ * bk_commit_msm: createCommitment(scalars, PKG1[key_first : key_first + n])
+ * (kyber.go:533-562) = sum_i SetInt64(scalars[i]) PK[key_first + i], where
+ * SetInt64(v) = v mod n.  scalars (n int64) and out64 are at `where`.
+ * bk_commit_verify: verifyCommitment (kyber.go:564-577): *ok (host) = 1 if that
+ * sum's 64 bytes equal committed64 (at `where`), else 0.
+ *
+ * bk_commit_generate: the commitments of generateMinerSecretShares
+ * (kyber.go:456-482) for an update of d entries given as delta (d doubles,
+ * quantised as bk_shares_generate quantises: int64(delta * 10^precision) by
+ * Go's conversion) or as q (d int64 taken as they are, e.g. q_out of
+ * bk_grad_*); exactly one of the two is non-NULL.  With chunks =
+ * bk_shares_chunks(d, poly_size):
+ *   commit_out   64 bytes: createCommitment(update, PKG1)
+ *   chunk_out    chunks x 64: fillPolynomialMap's commitment (kyber.go:172-202)
+ *                of chunk c, its coefficient j on PK[c poly_size + j]
+ *   witness_out  chunks x total_shares x 64: createShareAndWitness's witness
+ *                (kyber.go:579-646) of chunk c at share s (x = s - 10): the
+ *                commitment, on the chunk's key points, of the int64 quotient
+ *                of the chunk's float polynomial by (X - x) as
+ *                dividePolynomial leaves it
+ * Each output may be NULL, not all three; inputs and outputs are at `where`.
+ *
+ * bk_commit_stats: since the context was made, out[0] kernel launches, out[1]
+ * copy calls, out[2] calls that reached the device; out[3] the resident key's
+ * points.
+ *
+ * Every entry is synchronous.  Device pointers are 8-byte aligned (points: any
+ * alignment).  Errors, checked in this order: BK_EINVAL for a null ctx, a null
+ * required pointer (both or neither of delta and q), a bad where, count, n or d
+ * outside [1, 2^22], key_first outside [0, 2^22]; BK_ENOTSUP for precision
+ * outside [0, 18], poly_size outside [1, BK_SHARES_MAX_POLY], total_shares
+ * outside [poly_size, 64]; BK_EINVAL for no output requested; then BK_EINVAL
+ * for no resident key, key_first + n or d past the key, an invalid key point.
+ * A refused call changes nothing.  The launches carry no timing id.  Added
+ * without a change of BK_ABI_VERSION (14), as bk_shares_* was. */
+int bk_commit_set_key(bk_ctx *ctx, const uint8_t *pk, int64_t count);
+int bk_commit_key_count(bk_ctx *ctx, int64_t *count);
+int bk_commit_msm(bk_ctx *ctx, const int64_t *scalars, int where, int64_t n, int64_t key_first,
+                  uint8_t *out64);
+int bk_commit_verify(bk_ctx *ctx, const int64_t *scalars, int where, int64_t n, int64_t key_first,
+                     const uint8_t *committed64, int *ok);
+int bk_commit_generate(bk_ctx *ctx, const double *delta, const int64_t *q, int where, int64_t d,
+                       int precision, int poly_size, int total_shares, uint8_t *commit_out,
+                       uint8_t *chunk_out, uint8_t *witness_out);
+int bk_commit_stats(bk_ctx *ctx, int64_t out[4]);   /* launches, copies, calls, key points */
+
 /* The gradient step -- computeUpdate -> oneGradientStep (DistSys/
  * honest.go:165-200, 284-324): privateFun of ML/code/logistic_model.py:92-140
  * (creditcard) or ML/Pytorch/client_obj.py:73-77 -> client.py:38-65 (the torch
