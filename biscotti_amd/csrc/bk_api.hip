@@ -266,6 +266,7 @@ void bk_destroy(bk_ctx *c) {
         shares_destroy(c->shares);
         grad_destroy(c->grad);
         commit_destroy(c->commit);
+        commit_points_destroy(c->points);
         delete c->hpool;
         if (c->copy) (void)hipStreamDestroy(c->copy);
         for (void *p : c->staged) (void)hipHostFree(p);

@@ -260,6 +260,37 @@ hipError_t launch_commit_witness(const double *delta, const int64_t *q, double s
                                  int P, int T, const uint32_t *table, uint8_t *out,
                                  hipStream_t st);
 
+// bk_commit_points_*: the miner's store of the clients' G1 points and their sums
+// (bk_commit_points_api.hip, kernels bk_commit_points.hip).
+// store: n_cap rows of np = 1 + chunks (1 + held) affine points in Montgomery
+// form, 64 bytes each.  in / out stage a call's host part and host outputs as
+// [commitment | chunk commitments | witnesses].  All grow only
+constexpr int COMMIT_POINTS_AUTO_LANES = 4;   // the widest lane group commit_points_lanes picks
+constexpr int COMMIT_POINTS_WG_PER_CU = 2;    // the grid it lets a wider group reach
+constexpr int64_t COMMIT_POINTS_MAX_N = 4096;
+struct CommitPoints {
+    bool begun = false;
+    int64_t chunks = 0, np = 0, n_cap = 0, count = 0;
+    int held = 0;
+    int lanes = 0;  // bk_commit_points_set_lanes (0: commit_points_lanes chooses)
+    DevBuf store, slots, in, out, bad;
+    // bk_commit_points_stats: launches, copy calls, calls that reached the device
+    int64_t stats[3] = {0, 0, 0};
+};
+void commit_points_destroy(CommitPoints *cp);
+// bk_commit_points.hip.  Every pointer is device memory; the three arrays of a
+// part or of a sum's outputs at any alignment, an output nullable.  row: np x 16
+// words; *bad (preset to all ones) takes the smallest invalid point index
+hipError_t launch_commit_points_in(const uint8_t *commit, const uint8_t *chunk,
+                                   const uint8_t *witness, int held, int64_t np, uint32_t *row,
+                                   unsigned long long *bad, hipStream_t st);
+int commit_points_lanes(int64_t np, int64_t count, int num_cu);
+// lanes in {1, 2, 4, 8, 16}; slots: count slot numbers below the rows stored
+hipError_t launch_commit_points_sum(const uint32_t *store, int64_t np, int held,
+                                    const int64_t *slots, int64_t count, int lanes,
+                                    uint8_t *commit_out, uint8_t *chunk_out, uint8_t *witness_out,
+                                    hipStream_t st);
+
 }  // namespace bk
 
 // the C ABI's opaque handle, hence at global scope; its field types are bk::'s
@@ -506,6 +537,9 @@ struct bk_ctx {
     // bk_commit_*: the commitment key and a call's scratch (bk_commit_api.hip),
     // created by the first bk_commit_set_key
     bk::Commit *commit = nullptr;
+    // bk_commit_points_*: the miner's point store (bk_commit_points_api.hip),
+    // created by the first bk_commit_points_begin or _set_lanes
+    bk::CommitPoints *points = nullptr;
 };
 
 namespace bk {

@@ -1130,6 +1130,102 @@ class Engine:
         check(lib().bk_commit_stats(self._ctx, out))
         return list(out)
 
+    # ---- the miner's G1 point sums (bk_commit_points_*) -----------------------
+    def commit_points_begin(self, chunks, held, n_cap):
+        """The miner's point store: up to n_cap parts of 1 + chunks (1 + held)
+        points each."""
+        chunks, held, n_cap = int(chunks), int(held), int(n_cap)
+        if chunks < 1:
+            raise ValueError("chunks=%d < 1" % chunks)
+        if not 1 <= held <= _lib.BK_SHARES_MAX_POINTS:
+            raise ValueError("held=%d outside [1, %d]" % (held, _lib.BK_SHARES_MAX_POINTS))
+        if not 1 <= n_cap <= 4096:
+            raise ValueError("n_cap=%d outside [1, 4096]" % n_cap)
+        check(lib().bk_commit_points_begin(self._ctx, chunks, held, n_cap))
+        self._points = (chunks, held)
+
+    def _points_state(self, who):
+        st = getattr(self, "_points", None)
+        if st is None:
+            raise ValueError("%s without commit_points_begin" % who)
+        return st
+
+    @staticmethod
+    def _points_array(a, shape, what):
+        if isinstance(a, (bytes, bytearray)):
+            a = np.frombuffer(a, dtype=np.uint8)
+            a = a.reshape(-1, 64) if a.size % 64 == 0 else a
+        a = np.asarray(a)
+        if a.dtype != np.uint8 or a.shape[-1:] != (64,) or a.size != 64 * int(np.prod(shape)):
+            raise ValueError("%s must be a uint8 array of shape %s" % (what, shape + (64,)))
+        return np.ascontiguousarray(a)
+
+    def commit_points_add(self, commit, chunk_pts, witness_pts):
+        """One client's part (host): its commitment (64 bytes), chunk commitments
+        (chunks x 64) and this miner's witnesses (chunks x held x 64), as
+        MarshalBinary bytes; returns its slot."""
+        chunks, held = self._points_state("commit_points_add")
+        a = np.frombuffer(commit, dtype=np.uint8) if isinstance(commit, (bytes, bytearray)) \
+            else np.asarray(commit)
+        if a.dtype != np.uint8 or a.shape != (64,):
+            raise ValueError("commit must be 64 uint8 bytes")
+        a = np.ascontiguousarray(a)
+        b = self._points_array(chunk_pts, (chunks,), "chunk_pts")
+        w = self._points_array(witness_pts, (chunks, held), "witness_pts")
+        return self.commit_points_add_ptr(a.ctypes.data, b.ctypes.data, w.ctypes.data, _lib.BK_HOST)
+
+    def commit_points_add_ptr(self, commit_ptr, chunk_ptr, witness_ptr, where):
+        """The three arrays by raw pointer, all at `where`."""
+        self._points_state("commit_points_add")
+        slot = ctypes.c_int64(-1)
+        check(lib().bk_commit_points_add(self._ctx, _p(commit_ptr), _p(chunk_ptr), _p(witness_ptr),
+                                         int(where), ctypes.byref(slot)))
+        return slot.value
+
+    def commit_points_count(self):
+        n = ctypes.c_int64(0)
+        check(lib().bk_commit_points_count(self._ctx, ctypes.byref(n)))
+        return n.value
+
+    def commit_points_set_lanes(self, lanes):
+        """The lanes sharing one point's sum in k_commit_points_sum: 1, 2, 4, 8 or
+        16, or 0 for the library's choice.  The same bytes either way."""
+        lanes = int(lanes)
+        if lanes not in (0, 1, 2, 4, 8, 16):
+            raise ValueError("lanes=%d outside {0, 1, 2, 4, 8, 16}" % lanes)
+        check(lib().bk_commit_points_set_lanes(self._ctx, lanes))
+
+    def commit_points_sum(self, slots, want_commit=True, want_chunks=True, want_witnesses=True):
+        """The point-wise group sum of the listed slots' parts: (commitment: 64
+        uint8, chunk commitments: chunks x 64, witnesses: chunks x held x 64),
+        None for what was not wanted."""
+        chunks, held = self._points_state("commit_points_sum")
+        s = np.asarray(slots)
+        if s.ndim != 1 or s.shape[0] < 1 or not np.issubdtype(s.dtype, np.integer):
+            raise ValueError("slots must be a non-empty 1-D integer array")
+        if not (want_commit or want_chunks or want_witnesses):
+            raise ValueError("no output requested")
+        s = np.ascontiguousarray(s, dtype=np.int64)
+        com = np.empty(64, dtype=np.uint8) if want_commit else None
+        chk = np.empty((chunks, 64), dtype=np.uint8) if want_chunks else None
+        wit = np.empty((chunks, held, 64), dtype=np.uint8) if want_witnesses else None
+        self.commit_points_sum_ptr(s, _lib.BK_HOST, _ptr(com), _ptr(chk), _ptr(wit))
+        return com, chk, wit
+
+    def commit_points_sum_ptr(self, slots, where, commit_ptr, chunk_ptr, witness_ptr):
+        """slots a host int64 array; the outputs by raw pointer (None: not
+        wanted), all at `where`."""
+        self._points_state("commit_points_sum")
+        check(lib().bk_commit_points_sum(self._ctx, slots.ctypes.data, int(slots.shape[0]),
+                                         int(where), _p(commit_ptr), _p(chunk_ptr),
+                                         _p(witness_ptr)))
+
+    def commit_points_stats(self):
+        """[kernel launches, copy calls, calls, points held] of bk_commit_points_*."""
+        out = (ctypes.c_int64 * 4)()
+        check(lib().bk_commit_points_stats(self._ctx, out))
+        return list(out)
+
     # ---- the gradient step on the resident training shard (bk_grad_*) --------
     def grad_set_logistic(self, X, y):
         """Make (X, y) the context's training set: X nn x d float64 (a row stride

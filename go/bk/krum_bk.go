@@ -568,8 +568,8 @@ func recoverAggregateGPU(globalW []float64, parts [][]int64, held []int, xs []in
 
 // ---- polynomial commitments in bn256 G1 (bk_commit_*) -----------------------
 //
-// The G1 side only: aggregateSecret's point sums, verifySecret's pairings and the
-// Schnorr signatures stay in Go.  A point crosses as its MarshalBinary bytes.
+// The G1 side only: verifySecret's pairings and the Schnorr signatures stay in
+// Go.  A point crosses as its MarshalBinary bytes.
 
 // bkCommitKey is the number of key points resident in the engine (0: none).
 var (
@@ -698,6 +698,82 @@ func fillPolynomialMapGPU(deltaw []float64, precision int, polySize int, totalSh
 		}
 	}
 	return commitment, chunkPoints, witnesses
+}
+
+// ---- the miner's G1 point sums (bk_commit_points_*) --------------------------
+
+// bkPointsChunks and bkPointsHeld are the shape of one part of the engine's
+// point store (0: no store).
+var (
+	bkPointsChunks int
+	bkPointsHeld   int
+)
+
+// beginPointsGPU empties the engine's point store for a new iteration; call it
+// beside beginSharesGPU.  chunks: the chunks of an update, held: the witnesses
+// of each chunk this miner holds, nCap: the most clients that can register.
+func beginPointsGPU(chunks int, held int, nCap int) bool {
+	bkPointsChunks = 0
+	bkPointsHeld = 0
+	if bkCtx == nil || chunks < 1 || held < 1 {
+		return false
+	}
+	if st := C.bk_commit_points_begin(bkCtx, C.int64_t(chunks), C.int(held), C.int64_t(nCap)); st != C.BK_OK {
+		outLog.Printf("bk_commit_points_begin failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	bkPointsChunks = chunks
+	bkPointsHeld = held
+	return true
+}
+
+// addMinerPointsGPU keeps the points of one client's MinerPart as they arrive in
+// MinerPartRPC (converttoMinerPart): commitUpdate is CommitmentUpdate's 64 bytes,
+// chunkPts each PolyMap[i].Commitment's in index order, witnessPts each
+// PolyMap[i].Witnesses' in [chunk][share] order.  A point that does not
+// unmarshal refuses the part.  Returns the part's slot, which the caller keeps
+// against the client's NodeID as it keeps addSecretShareGPU's; -1 on an error.
+func addMinerPointsGPU(commitUpdate []byte, chunkPts []byte, witnessPts []byte) int {
+	if bkCtx == nil || bkPointsChunks == 0 || len(commitUpdate) != 64 || len(chunkPts) != 64*bkPointsChunks || len(witnessPts) != 64*bkPointsChunks*bkPointsHeld {
+		return -1
+	}
+	var cp, kp, wp *C.uint8_t
+	var slot C.int64_t
+	cp = (*C.uint8_t)(unsafe.Pointer(&commitUpdate[0]))
+	kp = (*C.uint8_t)(unsafe.Pointer(&chunkPts[0]))
+	wp = (*C.uint8_t)(unsafe.Pointer(&witnessPts[0]))
+	if st := C.bk_commit_points_add(bkCtx, cp, kp, wp, C.BK_HOST, &slot); st != C.BK_OK {
+		outLog.Printf("bk_commit_points_add failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return -1
+	}
+	return int(slot)
+}
+
+// getMinerPointsGPU replaces the point additions of the aggregateSecret loop in
+// getSecretShares (main.go:2157-2189, kyber.go:244-287): CommitmentUpdate.Add,
+// and per chunk Commitment.Add and every Witnesses[j].Add, over the parts in
+// `slots`.  Returns the sums' bytes for UnmarshalBinary: the update's commitment
+// (64), the chunks' ([chunk]) and the witnesses' ([chunk][share]); nil on an
+// error.  The share values of the same reply come from getMinerPartGPU.
+func getMinerPointsGPU(slots []int64) ([]byte, []byte, []byte) {
+	if bkCtx == nil || bkPointsChunks == 0 || len(slots) == 0 {
+		return nil, nil, nil
+	}
+	whole := make([]byte, 64)
+	chunkRaw := make([]byte, 64*bkPointsChunks)
+	witRaw := make([]byte, 64*bkPointsChunks*bkPointsHeld)
+	ns := len(slots)
+	var sp *C.int64_t
+	var cp, kp, wp *C.uint8_t
+	sp = (*C.int64_t)(unsafe.Pointer(&slots[0]))
+	cp = (*C.uint8_t)(unsafe.Pointer(&whole[0]))
+	kp = (*C.uint8_t)(unsafe.Pointer(&chunkRaw[0]))
+	wp = (*C.uint8_t)(unsafe.Pointer(&witRaw[0]))
+	if st := C.bk_commit_points_sum(bkCtx, sp, C.int64_t(ns), C.BK_HOST, cp, kp, wp); st != C.BK_OK {
+		outLog.Printf("bk_commit_points_sum failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return nil, nil, nil
+	}
+	return whole, chunkRaw, witRaw
 }
 
 // ---- the gradient step on the peer's resident shard (bk_grad_*) -------------

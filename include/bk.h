@@ -1079,6 +1079,58 @@ int bk_commit_generate(bk_ctx *ctx, const double *delta, const int64_t *q, int w
                        uint8_t *chunk_out, uint8_t *witness_out);
 int bk_commit_stats(bk_ctx *ctx, int64_t out[4]);   /* launches, copies, calls, key points */
 
+/* The miner's G1 point sums -- the other half of aggregateSecret
+ * (DistSys/kyber.go:244-287) beside bk_shares_sum's share values: over the
+ * agreed node list, the sum of the clients' CommitmentUpdate, of every chunk's
+ * Commitment and of each of its held Witnesses.
+ *
+ * A part is what one client sent this miner, as MarshalBinary bytes in the
+ * shapes bk_commit_generate writes: commit64 (64 bytes), chunk_pts (chunks x
+ * 64) and witness_pts (chunks x held x 64: the miner's slice [held m,
+ * held (m + 1)) of each chunk's witnesses, extractMinerSecret kyber.go:205-242).
+ * All three are required and lie at `where`.  A part has NP = 1 + chunks (1 +
+ * held) points, numbered: the update's commitment, then per chunk its
+ * commitment followed by its witnesses.
+ *
+ * bk_commit_points_begin: the store of up to n_cap parts (emptied; a second
+ * begin restarts it and reuses a buffer that is large enough).
+ * bk_commit_points_add: the part is unmarshalled and validated on the device and
+ * takes the next slot (*slot, host, nullable).  A coordinate >= p or a point off
+ * the curve refuses the part: BK_EINVAL, bk_last_error names the smallest such
+ * point number, no slot is taken and the earlier slots are untouched.  (The
+ * reference ignores UnmarshalBinary's error in converttoMinerPart; this entry
+ * refuses instead.)  64 zero bytes are infinity.
+ * bk_commit_points_count: the parts held.
+ * bk_commit_points_set_lanes: the lanes of a wave that share one point number's
+ * sum, 1, 2, 4, 8 or 16; 0 (the default) leaves the choice to the library.  The
+ * outputs are the same bytes for every value.
+ * bk_commit_points_sum: slots (host) lists count slots, each at most once.
+ * Output point k is the group sum of the listed parts' point k, as the 64
+ * bytes of MarshalBinary (infinity: 64 zero bytes), whatever the list's order:
+ * commit_out 64 bytes, chunk_out chunks x 64, witness_out chunks x held x 64,
+ * each nullable, not all three, at `where`.  The store is not consumed.
+ * bk_commit_points_stats: since the context was made, out[0] kernel launches,
+ * out[1] copy calls, out[2] calls that reached the device; out[3] the points
+ * held now.
+ *
+ * Every entry is synchronous.  Errors: BK_EINVAL for a null ctx first, then (no
+ * state or GPU needed) chunks < 1, held outside [1, 64], n_cap outside
+ * [1, 4096], a null required pointer, a bad where, count < 1, no output
+ * requested, lanes outside {0, 1, 2, 4, 8, 16}; BK_ENOMEM where NP n_cap 64
+ * bytes cannot be allocated (the state stays as it was); then BK_EINVAL for add,
+ * count or sum without begin, a full store, count above the parts held, a slot
+ * out of range or listed twice, an invalid point.  A refused call changes
+ * nothing.  The launches carry no timing id.  Added without a change of
+ * BK_ABI_VERSION (14), as bk_commit_* was. */
+int bk_commit_points_begin(bk_ctx *ctx, int64_t chunks, int held, int64_t n_cap);
+int bk_commit_points_add(bk_ctx *ctx, const uint8_t *commit64, const uint8_t *chunk_pts,
+                         const uint8_t *witness_pts, int where, int64_t *slot);
+int bk_commit_points_count(bk_ctx *ctx, int64_t *count);
+int bk_commit_points_set_lanes(bk_ctx *ctx, int lanes);   /* 0: the library's choice */
+int bk_commit_points_sum(bk_ctx *ctx, const int64_t *slots, int64_t count, int where,
+                         uint8_t *commit_out, uint8_t *chunk_out, uint8_t *witness_out);
+int bk_commit_points_stats(bk_ctx *ctx, int64_t out[4]);   /* launches, copies, calls, points held */
+
 /* The gradient step -- computeUpdate -> oneGradientStep (DistSys/
  * honest.go:165-200, 284-324): privateFun of ML/code/logistic_model.py:92-140
  * (creditcard) or ML/Pytorch/client_obj.py:73-77 -> client.py:38-65 (the torch

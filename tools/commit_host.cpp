@@ -10,6 +10,12 @@
 //       ALGO 0 plain double-and-add on the reduced scalar (254 bits for v < 0),
 //       1 double-and-add on |v|, 2 the signed 4-bit windows over the key's
 //       table (built outside the timed part).  Prints the best of REPS in ms.
+//   commit_host sum NP N THREADS REPS
+//       the time of the miner's point sums (bk_commit_points_sum's work): NP
+//       point numbers, each the sum over N parts of an affine point, by complete
+//       mixed additions into a Jacobian sum, one inversion per point number and
+//       its 64 bytes; the point numbers are split among THREADS.  Prints the
+//       best of REPS in ms and a digest of the bytes.
 //
 // tests/test_commit_host.py builds and runs it (plainly, and with the address
 // and undefined-behaviour sanitizers); tools/commit_bench.py uses bench.
@@ -260,10 +266,53 @@ static int bench(size_t n, int threads, int algo, int reps) {
     return 0;
 }
 
+static int sum_bench(size_t np, size_t n, int threads, int reps) {
+    if (np < 1 || n < 1 || threads < 1 || threads > 256 || reps < 1) return 2;
+    // a pool of 64 points (2^i G and their negations) drawn per (part, number)
+    Aff pool[64];
+    Jac g = Jac{fp_one(), fp_neg(fp_dbl(fp_one())), fp_one()};
+    for (int i = 0; i < 32; ++i) {
+        pool[i] = jac_to_aff(g);
+        pool[32 + i] = aff_neg(pool[i]);
+        g = jac_dbl(g);
+    }
+    std::vector<Aff> store(n * np);
+    uint64_t x = 0x9e3779b97f4a7c15ull;
+    for (size_t i = 0; i < n * np; ++i) {
+        x = x * 6364136223846793005ull + 1442695040888963407ull;
+        store[i] = pool[x >> 58];
+    }
+    std::vector<uint8_t> out(np * 64);
+    double best = 1e300;
+    for (int r = 0; r < reps; ++r) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<std::thread> workers;
+        for (int t = 0; t < threads; ++t)
+            workers.emplace_back([&, t] {
+                const size_t lo = np * (size_t)t / (size_t)threads, hi = np * (size_t)(t + 1) / (size_t)threads;
+                for (size_t k = lo; k < hi; ++k) {
+                    Jac acc = jac_inf();
+                    for (size_t s = 0; s < n; ++s) acc = jac_add_aff(acc, store[s * np + k]);
+                    aff_marshal(jac_to_aff(acc), &out[k * 64]);
+                }
+            });
+        for (auto &th : workers) th.join();
+        const double ms =
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (ms < best) best = ms;
+    }
+    uint64_t h = 1469598103934665603ull;
+    for (uint8_t b : out) h = (h ^ b) * 1099511628211ull;
+    printf("%.6f %016llx\n", best, (unsigned long long)h);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc == 3 && !strcmp(argv[1], "run")) return run(argv[2]);
     if (argc == 6 && !strcmp(argv[1], "bench"))
         return bench((size_t)atoll(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]));
-    fprintf(stderr, "usage: commit_host run FILE | bench N THREADS ALGO REPS\n");
+    if (argc == 6 && !strcmp(argv[1], "sum"))
+        return sum_bench((size_t)atoll(argv[2]), (size_t)atoll(argv[3]), atoi(argv[4]), atoi(argv[5]));
+    fprintf(stderr, "usage: commit_host run FILE | bench N THREADS ALGO REPS | sum NP N THREADS REPS\n");
     return 1;
 }
