@@ -21,7 +21,8 @@ SOURCES = ["bk_gram.hip", "bk_small.hip", "bk_scores.hip", "bk_mean.hip", "bk_sm
            "bk_collect_ragged.hip", "bk_collect_wide.hip", "bk_collect_noise.hip", "bk_collect_arrive.hip", "bk_collect_arrive_noised.hip", "bk_collect_arrive_wide.hip", "bk_collect_tiny.hip", "bk_api.hip", "bk_stage.hip", "bk_host.hip",
            "bk_comm.hip", "bk_group.hip", "bk_entries.hip", "bk_batch.hip", "bk_block.hip", "bk_block_api.hip", "bk_eval.hip",
            "bk_shares.hip", "bk_shares_api.hip", "bk_grad.hip", "bk_grad_api.hip",
-           "bk_commit.hip", "bk_commit_api.hip", "bk_commit_points.hip", "bk_commit_points_api.hip"]
+           "bk_commit.hip", "bk_commit_api.hip", "bk_commit_points.hip", "bk_commit_points_api.hip",
+           "bk_cnn.hip", "bk_cnn_api.hip"]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -40,7 +41,8 @@ FLAGS = [
 # instructions off (their code is integer-only; nothing in it may be fused into
 # a v_pk_* form)
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-SOURCE_FLAGS = {"bk_commit_points.hip": NO_PACKED_FP32, "bk_commit_points_api.hip": NO_PACKED_FP32}
+SOURCE_FLAGS = {"bk_commit_points.hip": NO_PACKED_FP32, "bk_commit_points_api.hip": NO_PACKED_FP32,
+                "bk_cnn.hip": NO_PACKED_FP32, "bk_cnn_api.hip": NO_PACKED_FP32}
 LIBS = ["-L" + os.path.join(ROCM, "lib"), "-lrccl", "-Wl,-rpath," + os.path.join(ROCM, "lib")]
 
 

@@ -151,11 +151,12 @@ struct Shares {
 
 // bk_eval*: the evaluation sets of a context (bk_eval.hip),
 // buffers of their own: RONI's validation sets and rounds never see them
-enum { EVAL_EMPTY = 0, EVAL_LOGISTIC = 1, EVAL_SOFTMAX = 2 };
+enum { EVAL_EMPTY = 0, EVAL_LOGISTIC = 1, EVAL_SOFTMAX = 2, EVAL_CNN = 3 };
 struct EvalSlot {
     int kind = EVAL_EMPTY;
     int64_t nv = 0, d = 0;    // samples; the model's length
-    int64_t din = 0, C = 0;   // softmax: d = C (din + 1)
+    int64_t din = 0, C = 0;   // softmax: d = C (din + 1); CNN: din = h w
+    CnnDims cnn = {};         // CNN: the shape (d = cnn.d)
     DevBuf X, y, xn;          // compact rows (row stride d / din); xn: softmax only
 };
 struct Eval {
@@ -374,6 +375,13 @@ struct bk_ctx {
     // labels; bk_roni_softmax_set_validation) and the prepared models
     DevBuf rmc_X, rmc_y, rmc_ws, rmc_xn, rmc_idx, rmc_nt;
     int64_t rmc_nv = 0, rmc_din = 0, rmc_C = 0;
+    // the CNN RONI (bk_roni_cnn_*, bk_cnn_api.hip): its validation set (compact
+    // h w fp32 rows, int32 labels) and the launch's 4 n + 1 counters (zeroed
+    // when they grow: every launch leaves them zero); a call's other scratch
+    // is the softmax form's (roni_w, roni_d, roni_s, rmc_idx, rmc_nt)
+    DevBuf cnn_X, cnn_y, cnn_cnt;
+    int64_t cnn_nv = 0;
+    CnnDims cnn_dims = {};
     // RONI rounds (bk_roni*_round_*): the iteration's model, its evaluation's
     // counts (logistic: mismatches; softmax: correct, near ties) and the begin's
     // prepared columns (softmax: the widened fp32 weights and their norms), kept
@@ -620,6 +628,10 @@ int eval_check_args(const int *sets, int nsets, const double *err, const int64_t
 int eval_check_sets(bk_ctx *c, int64_t d, const int *sets, int nsets);
 int eval_queue(bk_ctx *c, const double *dw, const int *sets, int nsets);
 void eval_collect(bk_ctx *c, int nsets, double *err, int64_t *wrong, int32_t *near_ties);
+int eval_state(bk_ctx *c);
+int check_set_index(int set);
+// bk_cnn_api.hip: bk.h's limits (BK_EINVAL for a null shape, BK_ENOTSUP outside them)
+int cnn_check_shape(const bk_cnn_shape *shape, CnnDims *out);
 // bk_host.hip
 int stage_host_pipelined(bk_ctx *c, const void *X, int64_t ld, int dtype, const double *noise,
                          int64_t k, int64_t noise_ld, int64_t n, int64_t d, char *dX,

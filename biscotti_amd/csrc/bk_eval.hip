@@ -302,14 +302,14 @@ void eval_destroy(Eval *e) {
     delete e;
 }
 
-static int eval_state(bk_ctx *c) {
+int eval_state(bk_ctx *c) {
     if (c->eval) return BK_OK;
     c->eval = new (std::nothrow) Eval();
     if (!c->eval) return fail(BK_ENOMEM, "host allocation of the evaluation sets failed");
     return BK_OK;
 }
 
-static int check_set_index(int set) {
+int check_set_index(int set) {
     if (set < 0 || set >= EVAL_MAX_SETS)
         return fail(BK_EINVAL, "set=%d outside [0, %d)", set, EVAL_MAX_SETS);
     return BK_OK;
@@ -345,6 +345,10 @@ int eval_check_sets(bk_ctx *c, int64_t d, const int *sets, int nsets) {
         if (s->d != d)
             return fail(BK_EINVAL, "d=%lld != evaluation set %d's %lld", (long long)d, sets[i],
                         (long long)s->d);
+        // two CNN shapes may share a d: one launch serves one shape
+        if (kind == EVAL_CNN && memcmp(&s->cnn, &c->eval->set[sets[0]].cnn, sizeof(CnnDims)) != 0)
+            return fail(BK_EINVAL, "evaluation set %d is of another CNN shape than set %d", sets[i],
+                        sets[0]);
         for (int j = 0; j < i; ++j)
             if (sets[j] == sets[i]) return fail(BK_EINVAL, "evaluation set %d is named twice", sets[i]);
     }
@@ -376,17 +380,30 @@ int eval_queue(bk_ctx *c, const double *dw, const int *sets, int nsets) {
     Eval *e = c->eval;
     CHK(ensure_eval_out(c, e));
     const EvalSlot &first = e->set[sets[0]];
-    const bool softmax = first.kind == EVAL_SOFTMAX;
-    const int ts = softmax ? EVAL_LOGITS_TS : EVAL_SIGN_TS;
+    const bool softmax = first.kind == EVAL_SOFTMAX, cnn = first.kind == EVAL_CNN;
+    const int ts = cnn ? first.cnn.ts : softmax ? EVAL_LOGITS_TS : EVAL_SIGN_TS;
     EvalDesc desc = {};
     desc.nsets = nsets;
     int64_t tiles = 0;
     for (int i = 0; i < nsets; ++i) {
         const EvalSlot &s = e->set[sets[i]];
-        desc.s[i] = {s.X.p, s.y.p, (const double *)s.xn.p, s.nv, softmax ? s.din : s.d, (int)tiles};
+        desc.s[i] = {s.X.p, s.y.p, (const double *)s.xn.p, s.nv, softmax || cnn ? s.din : s.d,
+                     (int)tiles};
         tiles += (s.nv + ts - 1) / ts;
         if (tiles > 0x7fffffff) return fail(BK_ENOTSUP, "the sets' %lld tiles exceed the grid",
                                             (long long)tiles);
+    }
+    if (cnn) {  // k_cnn (bk_cnn.hip): the same descriptor table, counters and mapped block
+        CnnLaunch a = {};
+        a.desc = desc;
+        a.m = first.cnn;
+        a.ww = dw;
+        a.cnt = (unsigned int *)e->cnt.p;
+        a.out = e->out_dev;
+        const hipError_t he = launch_cnn(a, tiles, c->stream);
+        if (he != hipSuccess) return fail(BK_EHIP, "k_cnn launch: %s", hipGetErrorString(he));
+        ++e->launches;
+        return BK_OK;
     }
     const hipError_t he =
         softmax ? launch_eval_logits(desc, (int)tiles, dw, first.din, (int)first.C,

@@ -344,6 +344,39 @@ hipError_t launch_eval_sign(const EvalDesc &desc, int tiles, const double *ww, i
                             unsigned int *cnt, EvalOut *out, hipStream_t st);
 hipError_t launch_eval_logits(const EvalDesc &desc, int tiles, const double *ww, int64_t din, int C,
                               unsigned int *cnt, EvalOut *out, hipStream_t st);
+// bk_cnn.hip: the one-layer CNN's forward pass (bk.h bk_cnn_shape), one launch
+// for either addressing.  Sets (idx null): desc's sets as for launch_eval_*,
+// tiles of dims.ts samples, groups = desc.nsets; cnt / out as there.  Batches
+// (idx non-null): desc.s[0] is the validation set, evaluation e of 2 n scores
+// model ww (e even) or ww + deltas[(e >> 1) ld] (e odd) on the nb samples
+// idx[e nb ..]; cnt: 4 n + 1 zeroed words, left zero; the last workgroup out
+// writes scores (n) and near (nullable, 2 n)
+struct CnnDims {
+    int h, w, k, pad, co, C;
+    int oh, ow, ph, pw;  // the output plane; the padded input plane
+    int ps, ts;          // a plane's LDS stride (floats); samples per tile (<= 16)
+    int64_t F, d;        // features co oh ow; the flat model's length
+};
+// false: outside bk.h's limits
+bool cnn_dims(int h, int w, int k, int pad, int co, int C, CnnDims *out);
+// the near-tie bound's two factors (bk.h): g_F on the activation, g_e on the tap magnitudes
+void cnn_gammas(const CnnDims &m, double *gF, double *ge);
+struct CnnLaunch {
+    EvalDesc desc;
+    CnnDims m;
+    const double *ww, *deltas;
+    int64_t ld;
+    const int64_t *idx;
+    int64_t nb, n;
+    unsigned int *cnt;
+    EvalOut *out;
+    double *scores;
+    int32_t *near;
+};
+__host__ __device__ inline int cnn_tiles(const CnnDims &m, int64_t samples) {
+    return (int)((samples + m.ts - 1) / m.ts);
+}
+hipError_t launch_cnn(const CnnLaunch &a, int64_t tiles, hipStream_t st);
 // bk_i8.hip: K1i8, the Gram of fp32 rows from exact int8 digit slices
 // (BK_F32_I8): column ranges (one per XCD), digit planes [3][npad][dp] int8
 struct I8Layout {

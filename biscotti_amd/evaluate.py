@@ -26,13 +26,23 @@ class ModelEvaluator:
     """train / test / attack: (X, y) pairs, any of them None.  n_classes None:
     the logistic model (X float64, labels as numbers, a model of d weights);
     otherwise the softmax model (X float32, integer labels, a model of
-    n_classes * (d_in + 1) entries: W row-major, then b).
+    n_classes * (d_in + 1) entries: W row-major, then b).  cnn_shape = (h, w, k,
+    pad, c_out, n_classes): the one-layer CNN model instead (set_cnn).
 
     One evaluator per engine at a time: the sets live in the engine's context
     (slots TRAIN, TEST, ATTACK)."""
 
     def __init__(self, train=None, test=None, attack=None, n_classes: Optional[int] = None,
-                 engine: Optional[Engine] = None):
+                 engine: Optional[Engine] = None, cnn_shape=None):
+        if cnn_shape is not None:  # the one-layer CNN model (bk.h bk_cnn_shape)
+            self._engine = engine if engine is not None else default_engine(0)
+            self._slots, self.near_ties = [], {}
+            for slot, s in ((TRAIN, train), (TEST, test), (ATTACK, attack)):
+                if s is not None:
+                    self.set_cnn(slot, s[0], s[1], cnn_shape)
+            if not self._slots:
+                raise ValueError("an evaluator needs a train, test or attack set")
+            return
         given = [(slot, s) for slot, s in ((TRAIN, train), (TEST, test), (ATTACK, attack))
                  if s is not None]
         if not given:
@@ -68,6 +78,18 @@ class ModelEvaluator:
                 self._engine.eval_set_softmax(slot, X, y, self.n_classes)
             self._slots.append(slot)
         self.near_ties = {}  # slot -> the last evaluation's near-tie count (softmax)
+
+    def set_cnn(self, slot, X, y, shape):
+        """Make (X, y) the slot's set for the CNN model of `shape` = (h, w, k,
+        pad, c_out, n_classes): X nv x (h w) float32 images.  test_error,
+        attack_rate and check_convergence then score MNISTCNNModel's flat model."""
+        h, w, k, pad, co, C = (int(v) for v in shape)
+        X = np.ascontiguousarray(X, dtype=np.float32).reshape(len(y), -1)
+        self._engine.eval_set_cnn(slot, X, y, (h, w, k, pad, co, C))
+        F = co * (h + 2 * pad - k + 1) * (w + 2 * pad - k + 1)
+        self.n_classes, self.d_in, self.d = C, h * w, co * k * k + co + C * F + C
+        if slot not in self._slots:
+            self._slots.append(slot)
 
     def _has(self, slot):
         return slot in self._slots

@@ -835,6 +835,24 @@ class Engine:
                                         X.shape[1], X.strides[0] // 4, y32.ctypes.data,
                                         int(n_classes)))
 
+    def eval_set_cnn(self, set_index, X, y, shape):
+        """X nv x (h w) float32 images, y integer labels in [0, n_classes), shape
+        (h, w, k, pad, c_out, n_classes): a set for the one-layer CNN model
+        (bk.h bk_cnn_shape); the model scored on it is MNISTCNNModel's flat layout."""
+        X = np.asarray(X)
+        if X.ndim != 2 or X.dtype != np.float32 or X.shape[0] < 1:
+            raise ValueError("X must be a float32 matrix, nv x (h w)")
+        if X.strides[1] != 4 or X.strides[0] % 4 or X.strides[0] < 4 * X.shape[1]:
+            X = np.ascontiguousarray(X)
+        y32 = np.ascontiguousarray(y, dtype=np.int32)
+        if y32.shape != (X.shape[0],) or not np.array_equal(y32, np.asarray(y)):
+            raise ValueError("y must have one int32 label per row of X")
+        sh = (ctypes.c_int32 * 6)(*[int(v) for v in shape])
+        if X.shape[1] != sh[0] * sh[1]:
+            raise ValueError("X must have h * w = %d columns" % (sh[0] * sh[1]))
+        check(lib().bk_eval_set_cnn(self._ctx, int(set_index), X.ctypes.data, X.shape[0],
+                                    X.strides[0] // 4, y32.ctypes.data, sh))
+
     def eval_clear(self, set_index):
         check(lib().bk_eval_clear(self._ctx, int(set_index)))
 

@@ -25,7 +25,7 @@ import numpy as np
 from ._lib import BK_HOST, check, lib
 from .krum import Engine, Update, default_engine
 
-__all__ = ["RONI_THRESHOLD", "RONIValidator", "SoftmaxRONIValidator", "set_validation", "roni"]
+__all__ = ["RONI_THRESHOLD", "RONIValidator", "SoftmaxRONIValidator", "CNNRONIValidator", "set_validation", "roni"]
 
 RONI_THRESHOLD = 0.02  # main.go:213
 
@@ -262,6 +262,54 @@ class SoftmaxRONIValidator(RONIValidator):
                                             self.d, idx.ctypes.data, idx.shape[2],
                                             out.ctypes.data, nt.ctypes.data))
         self.last_near_ties = nt
+        return out
+
+
+class CNNRONIValidator(SoftmaxRONIValidator):
+    """The torch-path verifier for the one-layer CNN model (MNISTCNNModel; bk.h
+    bk_cnn_shape): SoftmaxRONIValidator's mini-batch semantics -- `original` and
+    `after` each on a freshly drawn last batch of batch_size samples (draw_batches,
+    last_idx, seed) -- scored by bk_roni_cnn_batches.  shape = (h, w, k, pad,
+    c_out, n_classes); Xvalid nv x (h w) float32 images.  No rounds."""
+
+    def __init__(self, Xvalid, yvalid, shape, engine: Optional[Engine] = None,
+                 priv_prob: float = 0.0, batch_size: int = 10, seed=None):
+        self._engine = engine if engine is not None else default_engine(0)
+        h, w, k, pad, co, C = (int(v) for v in shape)
+        y = np.ascontiguousarray(yvalid, dtype=np.int32)
+        X = np.ascontiguousarray(Xvalid, dtype=np.float32).reshape(len(y), -1)
+        if X.shape[1] != h * w:
+            raise ValueError("Xvalid must be (nv, h * w)")
+        self.nv, self.d_in, self.n_classes = X.shape[0], h * w, C
+        self.d = co * k * k + co + C * co * (h + 2 * pad - k + 1) * (w + 2 * pad - k + 1) + C
+        self.priv_prob = priv_prob
+        self.batch_size = max(1, min(int(batch_size), self.nv))
+        self.round_batches = False
+        self._rng = np.random.default_rng(seed)
+        self.last_near_ties = None
+        self.last_idx = None
+        sh = (ctypes.c_int32 * 6)(h, w, k, pad, co, C)
+        check(lib().bk_roni_cnn_set_validation(self._engine.ctx, X.ctypes.data, self.nv, h * w,
+                                               y.ctypes.data, sh))
+
+    def begin_round(self, ww):
+        raise ValueError("the CNN verifier has no rounds")
+
+    def scores(self, ww, deltas, idx=None) -> np.ndarray:
+        ww = np.ascontiguousarray(ww, dtype=np.float64)
+        D = np.ascontiguousarray(np.atleast_2d(deltas), dtype=np.float64)
+        if ww.shape != (self.d,) or D.shape[1] != self.d:
+            raise ValueError("ww must be (d,) and deltas (n, d) with d = %d" % self.d)
+        n = D.shape[0]
+        idx = self.draw_batches(n) if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        if idx.ndim != 3 or idx.shape[:2] != (n, 2):
+            raise ValueError("idx must be (n, 2, nb)")
+        out = np.empty(n, dtype=np.float64)
+        nt = np.empty((n, 2), dtype=np.int32)
+        check(lib().bk_roni_cnn_batches(self._engine.ctx, ww.ctypes.data, D.ctypes.data, n, self.d,
+                                        idx.ctypes.data, idx.shape[2], out.ctypes.data,
+                                        nt.ctypes.data))
+        self.last_idx, self.last_near_ties = idx, nt
         return out
 
 

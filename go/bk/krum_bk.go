@@ -374,6 +374,53 @@ func setEvalSoftmaxGPU(set int, X []float32, y []int32, dIn int, classes int) bo
 	return true
 }
 
+// setEvalCNNGPU is the form for MNISTCNNModel (the one-layer CNN, bk.h
+// bk_cnn_shape): X nv x (h w) float32 images, y the labels.  testModelGPU and
+// testAttackRateGPU then score the CNN's flat model on the slot.
+func setEvalCNNGPU(set int, X []float32, y []int32, shape [6]int32) bool {
+	nv := len(y)
+	dIn := int(shape[0] * shape[1])
+	if bkCtx == nil || nv == 0 || dIn == 0 || len(X) != nv*dIn {
+		return false
+	}
+	var xp *C.float
+	var yp *C.int32_t
+	var sh C.bk_cnn_shape
+	xp = (*C.float)(unsafe.Pointer(&X[0]))
+	yp = (*C.int32_t)(unsafe.Pointer(&y[0]))
+	sh = C.bk_cnn_shape{h: C.int32_t(shape[0]), w: C.int32_t(shape[1]), k: C.int32_t(shape[2]),
+		pad: C.int32_t(shape[3]), c_out: C.int32_t(shape[4]), n_classes: C.int32_t(shape[5])}
+	if st := C.bk_eval_set_cnn(bkCtx, C.int(set), xp, C.int64_t(nv), C.int64_t(dIn), yp, &sh); st != C.BK_OK {
+		outLog.Printf("bk_eval_set_cnn failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	return true
+}
+
+// verifyUpdateCNNGPU replaces the Python roni call of verifyUpdate
+// (honest.go:598-629) for MNISTCNNModel: the update's score, after - original
+// on the two drawn mini-batches idx[0:nb] and idx[nb:2 nb] of the validation
+// set given once to bk_roni_cnn_set_validation.  ok is false on an engine error
+// (the caller then falls back to the Python call).
+func verifyUpdateCNNGPU(globalW []float64, delta []float64, idx []int64) (float64, bool) {
+	d := len(globalW)
+	nb := len(idx) / 2
+	if bkCtx == nil || d == 0 || len(delta) != d || nb == 0 {
+		return 0, false
+	}
+	var wp, dp *C.double
+	var ip *C.int64_t
+	var score C.double
+	wp = (*C.double)(unsafe.Pointer(&globalW[0]))
+	dp = (*C.double)(unsafe.Pointer(&delta[0]))
+	ip = (*C.int64_t)(unsafe.Pointer(&idx[0]))
+	if st := C.bk_roni_cnn_batches(bkCtx, wp, dp, 1, C.int64_t(d), ip, C.int64_t(nb), &score, nil); st != C.BK_OK {
+		outLog.Printf("bk_roni_cnn_batches failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return 0, false
+	}
+	return float64(score), true
+}
+
 func evalSetGPU(weights []float64, set int) float64 {
 	d := len(weights)
 	if bkCtx == nil || d == 0 {

@@ -1420,6 +1420,78 @@ int bk_eval_stats(bk_ctx *ctx, int64_t out[2]);
 int bk_block_finish_eval(bk_ctx *ctx, double *global_out, int64_t *qsum_out, double *qsum_float_out,
                          const int *sets, int nsets, double *err, int64_t *wrong, int32_t *near_ties);
 
+/* The one-layer CNN (the reference's mnist model, ML/Pytorch/mnist_cnn_model.py,
+ * its "ONE LAYER" form): Conv2d(1, c_out, k, stride 1, padding pad) on an h x w
+ * single-channel fp32 image, ReLU, MaxPool2d(1) (the identity), then
+ * Linear(F, n_classes) with F = c_out oh ow, oh = h + 2 pad - k + 1, ow
+ * likewise.  The flat model of d = c_out k k + c_out + n_classes F + n_classes
+ * doubles is laid out as MNISTCNNModel.reshape cuts it: the conv weight
+ * (c_out x 1 x k x k, row-major), the conv bias, the fc weight (n_classes x F,
+ * the feature index running (channel, y, x)), the fc bias.  mnist is
+ * {28, 28, 5, 4, 16, 10}: F = 16,384, d = 164,266.
+ * BK_ENOTSUP outside 1 <= h, w <= 64, 1 <= k <= 5, 0 <= pad < k,
+ * k <= h + 2 pad, k <= w + 2 pad, 1 <= c_out <= 16, 2 <= n_classes <= 16.
+ *
+ * THE ARITHMETIC, whatever the grid.  ww (the RONI `after` model: ww + delta,
+ * added in fp64) is rounded to fp32.  The pre-activation of (ch, y, x) is one
+ * fp64 FMA chain from +0.0 over the taps (ky, kx) row-major ascending, of exact
+ * products of fp32 operands, a tap in the padding contributing x = 0; then the
+ * bias is added in fp64 and the sum rounded once to fp32.  The activation is
+ * s < 0 ? 0 : s (a NaN stays NaN).  The logit of class c is the fp64 chain over
+ * the flat feature index ascending of exact fp32 products, plus the bias,
+ * rounded once to fp32: the softmax entries' rule with the activations as x.
+ * argmax takes the first maximum and NaN wins; wrong, err and the RONI score
+ * are formed as in the softmax entries.
+ *
+ * NEAR TIES: torch's fp32 convolution and sgemm, in any summation order and
+ * with or without FMA, can pick another class only on samples for which
+ *     !( l1 - l2 - u (|l1| + |l2|) > E_a + max_c E_c ),  u = 2^-24,
+ *     E_c = sum_k |W_ck| t_k + g_F |b_c|,
+ *     t_k = fp32_up( g_F a_k + g_e m_k ),   m_k = sum_taps |w| |x| + |b_ch|,
+ * or any logit is not finite (l1: the winning logit, class a; l2: the best
+ * other).  a_k is this library's activation of feature k, m_k its taps'
+ * magnitudes (an fp64 chain like the pre-activation's, then + |b_ch|), T = k k,
+ *     g_F = gamma_{F+1}(u) (1 + 2^-10),
+ *     g_e = (gamma_{T+1}(u) + 1.001 u) (1 + gamma_{F+1}(u)) (1 + 2^-20),
+ * gamma_n(u) = n u / (1 - n u), fp32_up(t) = fp32(t (1 + 2^-22) + 2^-126) (not
+ * below t), and the sum over k is an fp64 chain over k ascending of exact
+ * products.  E_c carries both error terms: the fc sum's gamma_{F+1} (sum_k
+ * |W_ck| a_k + |b_c|), and the activations' error through the fc weights,
+ * sum_k |W_ck| e_k with e_k = gamma_{T+1}(u) m_k -- widened by 1.001 u m_k for
+ * this library's own rounding of a_k and by gamma_{F+1} e_k for torch's sum
+ * running over its activations, not these.  fp32 underflow is not modelled, as
+ * in the softmax rule.  A score can differ from the reference's only if one of
+ * its two evaluations has a near tie, and then by at most (near ties) / nb.
+ *
+ *   bk_eval_set_cnn  a resident evaluation set of a third kind: X nv x (h w)
+ *                  fp32 images (row stride ldv), y int32 labels in
+ *                  [0, n_classes).  bk_eval, bk_block_finish_eval and
+ *                  bk_eval_clear take it as they take the others (d is the
+ *                  shape's d; all sets of a call of one shape, else BK_EINVAL).
+ *   bk_roni_cnn_set_validation  the CNN verifier's resident validation set.
+ *   bk_roni_cnn_batches  bk_roni_softmax_batches' semantics and idx layout:
+ *                  update j scored as after - original on its two drawn
+ *                  batches idx[(2 j) nb ..] (model ww; the delta is not read)
+ *                  and idx[(2 j + 1) nb ..] (model ww + delta_j); near_ties
+ *                  (nullable) 2 n counts.  Synchronous.
+ * Checked in this order, before any copy: BK_EINVAL for a null ctx (or a bad
+ * set index); BK_EINVAL for a null shape, BK_ENOTSUP for one outside the
+ * limits; BK_EINVAL for nv < 1, ldv < h w, a null X / y or a label outside
+ * [0, n_classes) (the sample named).  bk_roni_cnn_batches: BK_EINVAL for a
+ * null ctx, null idx (n > 0) or no validation set, n < 0 or ld < d; BK_ENOTSUP
+ * for n > 262139; BK_EINVAL for a null ww / deltas / scores, nb < 1, or an
+ * index outside [0, nv) (named).  A refused call leaves the state as it was.
+ * Added without a change of BK_ABI_VERSION (14). */
+typedef struct bk_cnn_shape {
+    int32_t h, w, k, pad, c_out, n_classes;
+} bk_cnn_shape;
+int bk_eval_set_cnn(bk_ctx *ctx, int set, const float *X, int64_t nv, int64_t ldv, const int32_t *y,
+                    const bk_cnn_shape *shape);
+int bk_roni_cnn_set_validation(bk_ctx *ctx, const float *Xv, int64_t nv, int64_t ldv,
+                               const int32_t *yv, const bk_cnn_shape *shape);
+int bk_roni_cnn_batches(bk_ctx *ctx, const double *ww, const double *deltas, int64_t n, int64_t ld,
+                        const int64_t *idx, int64_t nb, double *scores, int32_t *near_ties);
+
 /* ---- measurement: per-kernel HIP-event timing on the context stream ------- */
 enum bk_kernel_id {
     BK_K_GRAM = 0,     /* K1  fp64-MFMA split-K upper-triangle Gram partials */
