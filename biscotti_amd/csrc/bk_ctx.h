@@ -177,10 +177,25 @@ constexpr int64_t GRAD_MAPPED_MAX = 784;   // host outputs up to here are stored
 struct GradOut {                           // the mapped block's head
     double loss, norm;
 };
+// the one-layer CNN's step (bk_grad_cnn_api.hip, kernels bk_grad_cnn.hip,
+// DESIGN.md §5z): the shape, its tiling and the partial buffers of a call
+struct GradCnnTiling {
+    int ts, as, rs, J;        // positions per tile; LDS strides of a feature / a position's rows; co ow
+    size_t lds_fwd, lds_bwd;  // dynamic LDS bytes of the two kernels
+};
+struct GradCnn {
+    CnnDims m = {};
+    GradCnnTiling t = {};
+    DevBuf Rp;                // oh x count x 16: the output rows' logit parts
+    DevBuf Tp;                // tiles x oh x co x (k k + 1): the conv gradient's parts
+    DevBuf ssq;               // oh: the workgroups' sums of squares
+    DevBuf scal;              // the loss sum, the norm, coef
+};
 struct Grad {
-    int kind = EVAL_EMPTY;    // EVAL_LOGISTIC / EVAL_SOFTMAX
+    int kind = EVAL_EMPTY;    // EVAL_LOGISTIC / EVAL_SOFTMAX / EVAL_CNN
     int64_t nn = 0, d = 0;    // rows; the model's length
-    int64_t din = 0, C = 0;   // softmax: d = C (din + 1)
+    int64_t din = 0, C = 0;   // softmax: d = C (din + 1); CNN: din = h w
+    GradCnn cnn;              // CNN: the shape (d = cnn.m.d) and its buffers
     DevBuf X, y;              // compact rows (row stride d / din)
     DevBuf w, noise, idx;     // a call's host inputs on the device
     DevBuf R;                 // softmax: the batch's residuals, positions x 16
@@ -222,6 +237,48 @@ struct GradSoftmax {
 };
 hipError_t launch_grad_softmax_fwd(const GradSoftmax &a, hipStream_t st);
 hipError_t launch_grad_softmax_bwd(const GradSoftmax &a, hipStream_t st);
+// bk_grad_cnn.hip.  G: the d gradient entries; the buffers as in GradCnn; R:
+// count x 16; cnt: one zeroed word, used by the forward and then by the backward
+// (serial on one stream), left zero by each
+constexpr int64_t GRAD_CNN_MAX_BATCH = 4096;
+struct GradCnnArgs {
+    const float *X;
+    const int32_t *y;
+    const double *ww, *noise;
+    const int64_t *rows;
+    int64_t count, nn;
+    CnnDims m;
+    GradCnnTiling t;
+    double max_norm, scale;
+    double *Rp, *R, *Tp, *G, *ssq, *scal, *delta;
+    int64_t *q;
+    GradOut *out;
+    unsigned int *cnt;
+};
+// the tiling of bk.h (a function of the shape alone)
+GradCnnTiling grad_cnn_tiling(const CnnDims &m);
+hipError_t launch_grad_cnn_fwd(const GradCnnArgs &a, hipStream_t st);
+hipError_t launch_grad_cnn_bwd(const GradCnnArgs &a, hipStream_t st);
+hipError_t launch_grad_cnn_tail(const GradCnnArgs &a, hipStream_t st);
+// bk_grad_api.hip: what every gradient call shares.  GradIO: where a call's
+// kernels read and write
+struct GradIO {
+    const double *ww = nullptr, *noise = nullptr;
+    const int64_t *rows = nullptr;
+    double *delta = nullptr;
+    int64_t *q = nullptr;
+    bool mapped = false, copied = false;
+};
+int grad_state(bk_ctx *c);
+double grad_scale_of(int precision);
+int grad_check_call(const bk_ctx *c, const double *ww, int where, int precision,
+                    const double *delta_out, const int64_t *q_out);
+int grad_check_batch(const bk_ctx *c, int kind, const int64_t *idx, int64_t count, int64_t max_batch,
+                     int64_t *n);
+int grad_stage_call(bk_ctx *c, Grad *g, const double *ww, int where, const int64_t *idx, int64_t n,
+                    const double *noise, double *delta_out, int64_t *q_out, GradIO *io);
+int grad_finish_call(bk_ctx *c, Grad *g, const GradIO &io, double *delta_out, int64_t *q_out,
+                     double *loss_out, double *norm_out);
 
 // bk_commit_*: the resident commitment key of a context and a call's scratch
 // (bk_commit_api.hip, kernels bk_commit.hip).  table: per key

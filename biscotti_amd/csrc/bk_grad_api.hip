@@ -23,15 +23,11 @@ namespace bk {
 void grad_destroy(Grad *g) {
     if (!g) return;
     for (DevBuf *b : {&g->X, &g->y, &g->w, &g->noise, &g->idx, &g->R, &g->part, &g->lossp, &g->out,
-                      &g->cnt})
+                      &g->cnt, &g->cnn.Rp, &g->cnn.Tp, &g->cnn.ssq, &g->cnn.scal})
         if (b->p) (void)hipFree(b->p);
     if (g->hout) (void)hipHostFree(g->hout);
     delete g;
 }
-
-}  // namespace bk
-
-namespace {
 
 constexpr size_t GRAD_HOUT_HEAD = 64;  // GradOut, padded
 constexpr size_t GRAD_HOUT_BYTES = GRAD_HOUT_HEAD + 2 * (size_t)GRAD_MAPPED_MAX * 8;
@@ -43,7 +39,7 @@ int grad_state(bk_ctx *c) {
     return BK_OK;
 }
 
-int check_set_shape(int64_t nn, int64_t d, int64_t ldx) {
+static int check_set_shape(int64_t nn, int64_t d, int64_t ldx) {
     if (nn < 1 || d < 1)
         return fail(BK_EINVAL, "need nn >= 1 and d >= 1 (nn=%lld, d=%lld)", (long long)nn, (long long)d);
     if (ldx < d) return fail(BK_EINVAL, "ldx=%lld < d=%lld", (long long)ldx, (long long)d);
@@ -51,15 +47,15 @@ int check_set_shape(int64_t nn, int64_t d, int64_t ldx) {
 }
 
 // 10^p, exact for p <= 22 (what Go's math.Pow(10, p) returns)
-double scale_of(int precision) {
+double grad_scale_of(int precision) {
     double s = 1.0;
     for (int i = 0; i < precision; ++i) s *= 10.0;
     return s;
 }
 
 // checks 1 and 2 of a gradient call: no context field is read
-int check_call(const bk_ctx *c, const double *ww, int where, int precision, const double *delta_out,
-               const int64_t *q_out) {
+int grad_check_call(const bk_ctx *c, const double *ww, int where, int precision,
+                    const double *delta_out, const int64_t *q_out) {
     if (!c) return fail(BK_EINVAL, "null context");
     if (!ww) return fail(BK_EINVAL, "null ww");
     if (!delta_out) return fail(BK_EINVAL, "null delta_out");
@@ -71,13 +67,14 @@ int check_call(const bk_ctx *c, const double *ww, int where, int precision, cons
 }
 
 // checks 4 to 7, under the context mutex; *n: the batch's rows
-int check_batch(const bk_ctx *c, int kind, const int64_t *idx, int64_t count, int64_t *n) {
+int grad_check_batch(const bk_ctx *c, int kind, const int64_t *idx, int64_t count, int64_t max_batch,
+                     int64_t *n) {
     const Grad *g = c->grad;
     if (!g || g->kind == EVAL_EMPTY)
         return fail(BK_EINVAL, "no resident training set: call bk_grad_set_*");
     if (g->kind != kind)
         return fail(BK_EINVAL, "the resident training set is a %s one",
-                    g->kind == EVAL_SOFTMAX ? "softmax" : "logistic");
+                    g->kind == EVAL_CNN ? "CNN" : g->kind == EVAL_SOFTMAX ? "softmax" : "logistic");
     if (idx && count < 1) return fail(BK_EINVAL, "count=%lld < 1", (long long)count);
     if (idx)
         for (int64_t i = 0; i < count; ++i)
@@ -85,15 +82,14 @@ int check_batch(const bk_ctx *c, int kind, const int64_t *idx, int64_t count, in
                 return fail(BK_EINVAL, "idx[%lld]=%lld outside [0, %lld)", (long long)i,
                             (long long)idx[i], (long long)g->nn);
     *n = idx ? count : g->nn;
-    if (*n > GRAD_MAX_BATCH)
-        return fail(BK_ENOTSUP, "a batch of %lld rows exceeds %lld", (long long)*n,
-                    (long long)GRAD_MAX_BATCH);
+    if (*n > max_batch)
+        return fail(BK_ENOTSUP, "a batch of %lld rows exceeds %lld", (long long)*n, (long long)max_batch);
     return BK_OK;
 }
 
 // the exit counter (zeroed once: every launch leaves it zero) and the mapped
 // block the last workgroup writes
-int ensure_out(bk_ctx *c, Grad *g) {
+static int ensure_out(bk_ctx *c, Grad *g) {
     if (!g->cnt.p) {
         CHK(ensure(g->cnt, 64));
         HIPCHK(hipMemsetAsync(g->cnt.p, 0, 64, c->stream));
@@ -112,17 +108,8 @@ int ensure_out(bk_ctx *c, Grad *g) {
     return BK_OK;
 }
 
-// where a call's kernels read and write
-struct GradIO {
-    const double *ww = nullptr, *noise = nullptr;
-    const int64_t *rows = nullptr;
-    double *delta = nullptr;
-    int64_t *q = nullptr;
-    bool mapped = false, copied = false;
-};
-
-int stage_call(bk_ctx *c, Grad *g, const double *ww, int where, const int64_t *idx, int64_t n,
-               const double *noise, double *delta_out, int64_t *q_out, GradIO *io) {
+int grad_stage_call(bk_ctx *c, Grad *g, const double *ww, int where, const int64_t *idx, int64_t n,
+                    const double *noise, double *delta_out, int64_t *q_out, GradIO *io) {
     const size_t db = (size_t)g->d * 8;
     const hipStream_t st = c->stream;
     CHK(ensure_out(c, g));
@@ -158,8 +145,8 @@ int stage_call(bk_ctx *c, Grad *g, const double *ww, int where, const int64_t *i
 }
 
 // behind the launches: the outputs' way back, the wait, the scalars
-int finish_call(bk_ctx *c, Grad *g, const GradIO &io, double *delta_out, int64_t *q_out,
-                double *loss_out, double *norm_out) {
+int grad_finish_call(bk_ctx *c, Grad *g, const GradIO &io, double *delta_out, int64_t *q_out,
+                     double *loss_out, double *norm_out) {
     const size_t db = (size_t)g->d * 8;
     if (io.copied) {
         HIPCHK(hipMemcpyAsync(delta_out, io.delta, db, hipMemcpyDeviceToHost, c->stream));
@@ -177,7 +164,7 @@ int finish_call(bk_ctx *c, Grad *g, const GradIO &io, double *delta_out, int64_t
     return BK_OK;
 }
 
-}  // namespace
+}  // namespace bk
 
 int bk_grad_set_logistic(bk_ctx *c, const double *X, int64_t nn, int64_t d, int64_t ldx,
                          const double *y) {
@@ -251,16 +238,16 @@ int bk_grad_clear(bk_ctx *c) {
 int bk_grad_logistic(bk_ctx *c, const double *ww, int where, const int64_t *idx, int64_t count,
                      int64_t batch_size, double alpha, double lammy, const double *noise,
                      int precision, double *delta_out, int64_t *q_out, double *loss_out) {
-    CHK(check_call(c, ww, where, precision, delta_out, q_out));
+    CHK(grad_check_call(c, ww, where, precision, delta_out, q_out));
     if (batch_size < 1) return fail(BK_EINVAL, "batch_size=%lld < 1", (long long)batch_size);
     std::lock_guard<std::mutex> lk(c->mu);
     int64_t n = 0;
-    CHK(check_batch(c, EVAL_LOGISTIC, idx, count, &n));
+    CHK(grad_check_batch(c, EVAL_LOGISTIC, idx, count, GRAD_MAX_BATCH, &n));
     Grad *g = c->grad;
     DeviceGuard dg(c->device);
     HostDrain drain{c};  // error returns: the queued copies may still read the caller's memory
     GradIO io;
-    CHK(stage_call(c, g, ww, where, idx, n, noise, delta_out, q_out, &io));
+    CHK(grad_stage_call(c, g, ww, where, idx, n, noise, delta_out, q_out, &io));
     const int64_t tiles = (n + GRAD_TILE - 1) / GRAD_TILE;
     if (tiles > 1) {
         CHK(ensure(g->part, (size_t)tiles * g->d * 8));
@@ -277,7 +264,7 @@ int bk_grad_logistic(bk_ctx *c, const double *ww, int where, const int64_t *idx,
     a.batch = (double)batch_size;
     a.alpha = alpha;
     a.lammy = lammy;
-    a.scale = scale_of(precision);
+    a.scale = grad_scale_of(precision);
     a.part = (double *)g->part.p;
     a.lossp = (double *)g->lossp.p;
     a.delta = io.delta;
@@ -287,7 +274,7 @@ int bk_grad_logistic(bk_ctx *c, const double *ww, int where, const int64_t *idx,
     const hipError_t e = launch_grad_logistic(a, c->stream);
     if (e != hipSuccess) return fail(BK_EHIP, "k_grad_logistic launch: %s", hipGetErrorString(e));
     ++g->launches;
-    CHK(finish_call(c, g, io, delta_out, a.q ? q_out : nullptr, loss_out, nullptr));
+    CHK(grad_finish_call(c, g, io, delta_out, a.q ? q_out : nullptr, loss_out, nullptr));
     drain.armed = false;
     return BK_OK;
 }
@@ -295,17 +282,17 @@ int bk_grad_logistic(bk_ctx *c, const double *ww, int where, const int64_t *idx,
 int bk_grad_softmax(bk_ctx *c, const double *ww, int where, const int64_t *idx, int64_t count,
                     double max_norm, const double *noise, int precision, double *delta_out,
                     int64_t *q_out, double *loss_out, double *norm_out) {
-    CHK(check_call(c, ww, where, precision, delta_out, q_out));
+    CHK(grad_check_call(c, ww, where, precision, delta_out, q_out));
     if (!isfinite(max_norm) || !(max_norm > 0.0))
         return fail(BK_EINVAL, "max_norm=%g is not a positive finite number", max_norm);
     std::lock_guard<std::mutex> lk(c->mu);
     int64_t n = 0;
-    CHK(check_batch(c, EVAL_SOFTMAX, idx, count, &n));
+    CHK(grad_check_batch(c, EVAL_SOFTMAX, idx, count, GRAD_MAX_BATCH, &n));
     Grad *g = c->grad;
     DeviceGuard dg(c->device);
     HostDrain drain{c};
     GradIO io;
-    CHK(stage_call(c, g, ww, where, idx, n, noise, delta_out, q_out, &io));
+    CHK(grad_stage_call(c, g, ww, where, idx, n, noise, delta_out, q_out, &io));
     CHK(ensure(g->R, (size_t)n * 16 * 8));
     CHK(ensure(g->part, (size_t)g->d * 8));
     CHK(ensure(g->lossp, (size_t)((n + 63) / 64) * 8));
@@ -319,7 +306,7 @@ int bk_grad_softmax(bk_ctx *c, const double *ww, int where, const int64_t *idx, 
     a.din = g->din;
     a.C = (int)g->C;
     a.max_norm = max_norm;
-    a.scale = scale_of(precision);
+    a.scale = grad_scale_of(precision);
     a.R = (double *)g->R.p;
     a.part = (double *)g->part.p;
     a.lossp = (double *)g->lossp.p;
@@ -333,7 +320,7 @@ int bk_grad_softmax(bk_ctx *c, const double *ww, int where, const int64_t *idx, 
     e = launch_grad_softmax_bwd(a, c->stream);
     if (e != hipSuccess) return fail(BK_EHIP, "k_grad_softmax_bwd launch: %s", hipGetErrorString(e));
     ++g->launches;
-    CHK(finish_call(c, g, io, delta_out, a.q ? q_out : nullptr, loss_out, norm_out));
+    CHK(grad_finish_call(c, g, io, delta_out, a.q ? q_out : nullptr, loss_out, norm_out));
     drain.armed = false;
     return BK_OK;
 }

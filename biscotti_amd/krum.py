@@ -1285,6 +1285,27 @@ class Engine:
                                         X.strides[0] // 4, y32.ctypes.data, C))
         self._grad = ("softmax", X.shape[0], C * (X.shape[1] + 1))
 
+    def grad_set_cnn(self, X, y, shape):
+        """X nn x (h w) float32 images, y integer labels in [0, n_classes), shape
+        (h, w, k, pad, c_out, n_classes): the training set of a peer running the
+        one-layer CNN (bk.h bk_cnn_shape); the model is MNISTCNNModel's flat layout."""
+        X = np.asarray(X)
+        if X.ndim != 2 or X.dtype != np.float32 or X.shape[0] < 1:
+            raise ValueError("X must be a float32 matrix, nn x (h w)")
+        if X.strides[1] != 4 or X.strides[0] % 4 or X.strides[0] < 4 * X.shape[1]:
+            X = np.ascontiguousarray(X)
+        y32 = np.ascontiguousarray(y, dtype=np.int32)
+        if y32.shape != (X.shape[0],) or not np.array_equal(y32, np.asarray(y)):
+            raise ValueError("y must have one int32 label per row of X")
+        sh = (ctypes.c_int32 * 6)(*[int(v) for v in shape])
+        h, w, k, pad, co, C = list(sh)
+        if X.shape[1] != h * w:
+            raise ValueError("X must have h * w = %d columns" % (h * w))
+        check(lib().bk_grad_set_cnn(self._ctx, X.ctypes.data, X.shape[0], X.strides[0] // 4,
+                                    y32.ctypes.data, sh))
+        F = co * (h + 2 * pad - k + 1) * (w + 2 * pad - k + 1)
+        self._grad = ("cnn", X.shape[0], co * k * k + co + C * F + C)
+
     def grad_clear(self):
         check(lib().bk_grad_clear(self._ctx))
         self._grad = None
@@ -1307,8 +1328,9 @@ class Engine:
             if ia.min() < 0 or ia.max() >= nn:
                 raise ValueError("idx outside [0, %d)" % nn)
             ix = np.ascontiguousarray(ia, dtype=np.int64)
-        if (nn if ix is None else ix.shape[0]) > _lib.BK_GRAD_MAX_BATCH:
-            raise ValueError("a batch of more than %d rows" % _lib.BK_GRAD_MAX_BATCH)
+        cap = _lib.BK_GRAD_CNN_MAX_BATCH if kind == "cnn" else _lib.BK_GRAD_MAX_BATCH
+        if (nn if ix is None else ix.shape[0]) > cap:
+            raise ValueError("a batch of more than %d rows" % cap)
         nz = None
         if noise is not None:
             nz = np.ascontiguousarray(noise, dtype=np.float64)
@@ -1360,6 +1382,26 @@ class Engine:
                                     _p(noise_ptr), int(precision), _p(delta_ptr), _p(q_ptr),
                                     ctypes.byref(loss) if loss is not None else None,
                                     ctypes.byref(norm) if norm is not None else None))
+
+    def grad_cnn(self, ww, idx=None, max_norm=100.0, noise=None, precision=None):
+        """privateFun of the one-layer CNN model: (delta, q or None, loss, norm
+        before clipping)."""
+        mn = float(max_norm)
+        if not (np.isfinite(mn) and mn > 0.0):
+            raise ValueError("max_norm must be a positive finite number")
+        w, ix, nz, p, delta, q = self._grad_args("cnn", ww, idx, noise, precision)
+        loss, norm = ctypes.c_double(), ctypes.c_double()
+        self.grad_cnn_ptr(w.ctypes.data, _lib.BK_HOST, ix, mn, _ptr(nz), p, delta.ctypes.data,
+                          _ptr(q), loss, norm)
+        return delta, q, loss.value, norm.value
+
+    def grad_cnn_ptr(self, ww_ptr, where, idx, max_norm, noise_ptr, precision, delta_ptr, q_ptr,
+                     loss=None, norm=None):
+        check(lib().bk_grad_cnn(self._ctx, _p(ww_ptr), int(where), _p(_ptr(idx)),
+                                0 if idx is None else int(idx.shape[0]), float(max_norm),
+                                _p(noise_ptr), int(precision), _p(delta_ptr), _p(q_ptr),
+                                ctypes.byref(loss) if loss is not None else None,
+                                ctypes.byref(norm) if norm is not None else None))
 
     def grad_stats(self):
         """[kernel launches, gradient calls] of bk_grad_* since the engine was made."""

@@ -7,6 +7,7 @@ the peer's Python model every iteration, on the peer's shard held on the device.
     SoftmaxStepper    privateFun of ML/Pytorch/client_obj.py:73-77:
                       -Client.getGrad() (client.py:38-65: mean cross-entropy,
                       clip_grad_norm(., 100), W then b flattened)
+    CNNStepper        the same privateFun on MNISTCNNModel (the one-layer CNN)
 
 Drawing the mini-batch (np.random.choice, the shuffled loader's first batch)
 and pre-sampling the noise stay the caller's: both steppers take the batch's row
@@ -16,12 +17,12 @@ import numpy as np
 
 from .krum import Engine, default_engine
 
-__all__ = ["LogisticStepper", "SoftmaxStepper"]
+__all__ = ["LogisticStepper", "SoftmaxStepper"]  # the §5v surface; CNNStepper is imported by name
 
 
 class _Stepper:
     loss = None   # the last step's loss (the reference's f / Client.loss)
-    norm = None   # softmax: the last step's gradient norm before clipping
+    norm = None   # softmax, CNN: the last step's gradient norm before clipping
 
     def _result(self, delta, q, precision):
         return delta if precision is None else (delta, q)
@@ -86,4 +87,25 @@ class SoftmaxStepper(_Stepper):
     def private_fun(self, ww, idx=None, noise=None, precision=None):
         delta, q, self.loss, self.norm = self.engine.grad_softmax(ww, idx, self.max_norm, noise,
                                                                   precision)
+        return self._result(delta, q, precision)
+
+
+class CNNStepper(_Stepper):
+    """One peer's one-layer CNN (MNISTCNNModel; bk.h bk_cnn_shape): X nn x (h w)
+    float32 images, y integer labels in [0, n_classes), shape (h, w, k, pad,
+    c_out, n_classes); the model is the flat layout bk_eval_set_cnn scores."""
+
+    def __init__(self, X, y, shape, max_norm=100.0, engine: Engine = None):
+        self.shape = tuple(int(v) for v in shape)
+        if len(self.shape) != 6:
+            raise ValueError("shape must be (h, w, k, pad, c_out, n_classes)")
+        self.max_norm = float(max_norm)
+        if not (np.isfinite(self.max_norm) and self.max_norm > 0.0):
+            raise ValueError("max_norm must be a positive finite number")
+        self.engine = engine or default_engine()
+        self.engine.grad_set_cnn(X, y, self.shape)
+        _, self.nn, self.d = self.engine._grad
+
+    def private_fun(self, ww, idx=None, noise=None, precision=None):
+        delta, q, self.loss, self.norm = self.engine.grad_cnn(ww, idx, self.max_norm, noise, precision)
         return self._result(delta, q, precision)

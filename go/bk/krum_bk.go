@@ -832,6 +832,7 @@ func getMinerPointsGPU(slots []int64) ([]byte, []byte, []byte) {
 var (
 	bkGradDim       int
 	bkGradSoftmax   bool
+	bkGradCNN       bool
 	bkGradBatch     int
 	bkGradPrecision int
 	bkGradAlpha     float64 = 1e-2
@@ -879,7 +880,40 @@ func initGradGPU(X []float64, y []float64, X32 []float32, y32 []int32, d int, cl
 		bkGradDim = classes * (d + 1)
 	}
 	bkGradSoftmax = classes != 0
+	bkGradCNN = false
 	bkGradBatch = batchSize
+	bkGradPrecision = precision
+	return true
+}
+
+// initGradCNNGPU makes the shard of a peer running the one-layer CNN
+// (MNISTCNNModel) resident: X32 nn x (h w) float32 images with labels y32,
+// shape = {h, w, k, pad, c_out, n_classes} (bk.h bk_cnn_shape; mnist:
+// {28, 28, 5, 4, 16, 10}).  oneGradientStepGPU then steps that model.
+func initGradCNNGPU(X32 []float32, y32 []int32, shape [6]int, precision int) bool {
+	bkGradDim = 0
+	nn := len(y32)
+	dIn := shape[0] * shape[1]
+	if bkCtx == nil || nn == 0 || dIn == 0 || len(X32) != nn*dIn {
+		return false
+	}
+	var xfp *C.float
+	var yip *C.int32_t
+	var sh C.bk_cnn_shape
+	xfp = (*C.float)(unsafe.Pointer(&X32[0]))
+	yip = (*C.int32_t)(unsafe.Pointer(&y32[0]))
+	sh = C.bk_cnn_shape{h: C.int32_t(shape[0]), w: C.int32_t(shape[1]), k: C.int32_t(shape[2]),
+		pad: C.int32_t(shape[3]), c_out: C.int32_t(shape[4]), n_classes: C.int32_t(shape[5])}
+	if st := C.bk_grad_set_cnn(bkCtx, xfp, C.int64_t(nn), C.int64_t(dIn), yip, &sh); st != C.BK_OK {
+		outLog.Printf("bk_grad_set_cnn failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	oh := shape[0] + 2*shape[3] - shape[2] + 1
+	ow := shape[1] + 2*shape[3] - shape[2] + 1
+	f := shape[4] * oh * ow
+	bkGradDim = shape[4]*shape[2]*shape[2] + shape[4] + shape[5]*f + shape[5]
+	bkGradSoftmax = false
+	bkGradCNN = true
 	bkGradPrecision = precision
 	return true
 }
@@ -908,9 +942,12 @@ func oneGradientStepGPU(globalW []float64, idx []int64) ([]float64, []int64) {
 		ip = (*C.int64_t)(unsafe.Pointer(&idx[0]))
 	}
 	var st C.int
-	if bkGradSoftmax {
+	switch {
+	case bkGradCNN:
+		st = C.bk_grad_cnn(bkCtx, wp, C.BK_HOST, ip, C.int64_t(count), C.double(bkGradMaxNorm), np, C.int(bkGradPrecision), dp, qp, nil, nil)
+	case bkGradSoftmax:
 		st = C.bk_grad_softmax(bkCtx, wp, C.BK_HOST, ip, C.int64_t(count), C.double(bkGradMaxNorm), np, C.int(bkGradPrecision), dp, qp, nil, nil)
-	} else {
+	default:
 		st = C.bk_grad_logistic(bkCtx, wp, C.BK_HOST, ip, C.int64_t(count), C.int64_t(bkGradBatch), C.double(bkGradAlpha), C.double(bkGradLammy), np, C.int(bkGradPrecision), dp, qp, nil)
 	}
 	if st != C.BK_OK {

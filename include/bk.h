@@ -1492,6 +1492,71 @@ int bk_roni_cnn_set_validation(bk_ctx *ctx, const float *Xv, int64_t nv, int64_t
 int bk_roni_cnn_batches(bk_ctx *ctx, const double *ww, const double *deltas, int64_t n, int64_t ld,
                         const int64_t *idx, int64_t nb, double *scores, int32_t *near_ties);
 
+/* The one-layer CNN's gradient step -- privateFun of a peer running
+ * MNISTCNNModel (ML/Pytorch/client_obj.py:73-77 -> client.py:38-65: autograd,
+ * clip_grad_norm(., 100), the flatten), followed by updateFloatToInt.
+ *   bk_grad_set_cnn  makes the context's ONE resident training set (bk_grad_*
+ *                  above) a set of a third kind: X nn x (h w) fp32 images (row
+ *                  stride ldx), y int32 labels in [0, n_classes).  The shape's
+ *                  limits and the flat model layout are bk_eval_set_cnn's;
+ *                  bk_grad_clear empties it.
+ *   bk_grad_cnn    bk_grad_softmax's semantics for every argument (`where` for
+ *                  ww, noise, delta_out and q_out; host idx, repeats allowed,
+ *                  NULL: every row; precision; nullable outputs; synchronous).
+ *
+ * THE ARITHMETIC, whatever the grid or timing.  N = count; the batch is cut into
+ * tiles of TS consecutive positions, TS = the largest t <= 16 with
+ *     4 t rs + 12 c_out ow (t + 1) <= 131,072,
+ * rs = k (w + 2 pad) rounded up to the next number that is 4 mod 64 (16 at
+ * mnist's shape, 8 at the largest; a function of the shape alone).  Features are
+ * k = (ch, y, x); a segment is one output row y of one channel.
+ *  1. ww is rounded to fp32 as bk_eval stages it; the pre-activation and the
+ *     activation a are exactly the forward's above (the fp64 tap chain from
+ *     +0.0, plus the bias, rounded once to fp32, s < 0 ? 0 : s).
+ *  2. The logits stay fp64: S[ch][y][s][c] = the FMA chain over x ascending
+ *     from +0.0 of W[c][k] a[s][k]; R_y[s][c] = the chain of plain adds over ch
+ *     ascending from +0.0; l[s][c] = ((0 + R_0) + R_1 + ...) over y ascending,
+ *     then + b_c.  This is NOT bk_eval's single chain over k: the split over
+ *     rows is what makes the forward parallel, and it rounds differently.
+ *  3. bk_grad_softmax's rule: the maximum, e^{l - max} summed over c ascending,
+ *     r[s][c] = p - [y_s = c]; the loss part log sum + max - l_y, added over
+ *     groups of 64 positions by a fixed tree, the groups in order; loss = the
+ *     mean cross-entropy.
+ *  4. GW[c][k] = (the sum over tiles, in tile order, of each tile's FMA chain
+ *     over its positions ascending from +0.0 of r[s][c] a[s][k]) / N; gb_c the
+ *     same with a = 1.
+ *  5. dA[s][k] = the FMA chain over c ascending from +0.0 of W[c][k] r[s][c];
+ *     g[s][k] = a[s][k] > 0 ? dA[s][k] : 0 (a NaN activation gives NaN).
+ *  6. Per tile and output row y, T_y[ch][tap] = one FMA chain from +0.0 over
+ *     (s ascending, x ascending) of g[s][ch,y,x] xpad[s][y+ky][x+kx]; the
+ *     conv-bias term is the same chain with x = 1.  A tile's value is the chain
+ *     of adds over y ascending from +0.0; Gw[ch][tap] and Gcb[ch] are the tiles'
+ *     values added in tile order, divided by N.
+ *  7. norm = sqrt(((P_0 + P_1) + ... + P_{oh-1}) + P_last).  P_y covers the fc
+ *     weights of output row y: entry c (c_out ow) + ch ow + x, ascending, in
+ *     lane (entry mod 256)'s sum, the 256 sums by bk_grad_softmax's tree.
+ *     P_last covers the list [conv weights, conv biases, fc biases] the same
+ *     way.  coef = max_norm / (norm + 1e-6) scales every entry where it is
+ *     below 1 -- or NaN, so that a NaN anywhere makes every entry NaN;
+ *     delta = -g [+ noise], quantised by bk_quantized_sum_device's rule.
+ *     norm_out: the norm before clipping.
+ * A NaN in ww gives an all-NaN delta_out and BK_OK.
+ *   bk_grad_stats  counts a CNN call's three launches in out[0].
+ * Checked in this order, before any copy or launch.  bk_grad_set_cnn: BK_EINVAL
+ * for a null ctx or shape, BK_ENOTSUP for a shape outside the limits; BK_EINVAL
+ * for nn < 1 or ldx < h w; BK_ENOTSUP for nn > 2^31; BK_EINVAL for a null X /
+ * y or a label outside [0, n_classes) (the sample named).  bk_grad_cnn:
+ * bk_grad_softmax's checks; bk_grad_logistic and bk_grad_softmax on a CNN set,
+ * and bk_grad_cnn on a set of another kind, are BK_EINVAL (one of the other
+ * kind); BK_ENOTSUP for a batch of more than 4,096 rows (the partial buffers
+ * are sized by the batch; the deployed batch is 10).
+ * Added without a change of BK_ABI_VERSION (14). */
+int bk_grad_set_cnn(bk_ctx *ctx, const float *X, int64_t nn, int64_t ldx, const int32_t *y,
+                    const bk_cnn_shape *shape);
+int bk_grad_cnn(bk_ctx *ctx, const double *ww, int where, const int64_t *idx, int64_t count,
+                double max_norm, const double *noise, int precision, double *delta_out,
+                int64_t *q_out, double *loss_out, double *norm_out);
+
 /* ---- measurement: per-kernel HIP-event timing on the context stream ------- */
 enum bk_kernel_id {
     BK_K_GRAM = 0,     /* K1  fp64-MFMA split-K upper-triangle Gram partials */
