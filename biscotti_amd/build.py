@@ -22,7 +22,8 @@ SOURCES = ["bk_gram.hip", "bk_small.hip", "bk_scores.hip", "bk_mean.hip", "bk_sm
            "bk_comm.hip", "bk_group.hip", "bk_entries.hip", "bk_batch.hip", "bk_block.hip", "bk_block_api.hip", "bk_eval.hip",
            "bk_shares.hip", "bk_shares_api.hip", "bk_grad.hip", "bk_grad_api.hip",
            "bk_commit.hip", "bk_commit_api.hip", "bk_commit_points.hip", "bk_commit_points_api.hip",
-           "bk_cnn.hip", "bk_cnn_api.hip", "bk_grad_cnn.hip", "bk_grad_cnn_api.hip"]
+           "bk_cnn.hip", "bk_cnn_api.hip", "bk_grad_cnn.hip", "bk_grad_cnn_api.hip",
+           "bk_cnn_round.hip", "bk_cnn_round_api.hip"]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -43,7 +44,8 @@ FLAGS = [
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"bk_commit_points.hip": NO_PACKED_FP32, "bk_commit_points_api.hip": NO_PACKED_FP32,
                 "bk_cnn.hip": NO_PACKED_FP32, "bk_cnn_api.hip": NO_PACKED_FP32,
-                "bk_grad_cnn.hip": NO_PACKED_FP32, "bk_grad_cnn_api.hip": NO_PACKED_FP32}
+                "bk_grad_cnn.hip": NO_PACKED_FP32, "bk_grad_cnn_api.hip": NO_PACKED_FP32,
+                "bk_cnn_round.hip": NO_PACKED_FP32, "bk_cnn_round_api.hip": NO_PACKED_FP32}
 LIBS = ["-L" + os.path.join(ROCM, "lib"), "-lrccl", "-Wl,-rpath," + os.path.join(ROCM, "lib")]
 
 

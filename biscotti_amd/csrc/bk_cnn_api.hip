@@ -82,6 +82,7 @@ int bk_roni_cnn_set_validation(bk_ctx *c, const float *Xv, int64_t nv, int64_t l
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard dg(c->device);
     c->cnn_nv = 0;  // invalid until the new set has landed
+    c->cr_live = 0;  // a round's held verdicts were the old set's
     HostDrain drain{c};
     CHK(upload_samples(c, m, c->cnn_X, c->cnn_y, Xv, nv, ldv, yv));
     drain.armed = false;

@@ -1,0 +1,175 @@
+// bk_cnn_round_api.hip -- the CNN verifier's rounds (include/bk.h
+// bk_roni_cnn_round_*): the iteration's model held on the
+// device as fp64 with its per-sample verdicts over the whole validation set, and
+// each update scored against it -- its `original` from the held verdicts, its
+// `after` by one forward pass.  The kernel is k_cnn_round (bk_cnn_round.hip).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <mutex>
+
+#include "bk_ctx.h"
+
+namespace bk {
+namespace {
+
+int check_where(int where) {
+    if (where != BK_HOST && where != BK_HOST_PINNED && where != BK_DEVICE)
+        return fail(BK_EINVAL, "bad where=%d", where);
+    return BK_OK;
+}
+
+// chunks per conv item: about two workgroups per CU over the launch, an item
+// no shorter than four chunks (it stages the whole tile's planes)
+int pick_rc(const bk_ctx *c, int nch, int64_t tiles) {
+    const int64_t cus = c->num_cu > 0 ? c->num_cu : 256;
+    int64_t rc = ((int64_t)nch * tiles + 2 * cus - 1) / (2 * cus);
+    if (rc < 4) rc = 4;
+    return (int)(rc < nch ? rc : nch);
+}
+
+// the scratch of a launch of `tiles` tiles and the zeroed counters
+int ensure_launch_state(bk_ctx *c, int64_t tiles) {
+    const int64_t t = tiles < CNN_ROUND_TILES ? tiles : CNN_ROUND_TILES;
+    CHK(ensure(c->cr_scratch, (size_t)t * cnn_round_tile_floats(c->cnn_dims) * sizeof(float)));
+    const size_t had = c->cr_cnt.bytes;
+    CHK(ensure(c->cr_cnt, CNN_ROUND_CNT_WORDS * sizeof(unsigned int)));
+    if (c->cr_cnt.bytes != had)  // new: zero once, every group of launches leaves it zero
+        HIPCHK(hipMemsetAsync(c->cr_cnt.p, 0, c->cr_cnt.bytes, c->stream));
+    return BK_OK;
+}
+
+// the launches of one linear tile space (the begin's set, or a score group), at
+// most CNN_ROUND_TILES tiles each; the last one finishes
+int launch_space(bk_ctx *c, CnnRoundLaunch &a, int64_t space) {
+    const int nch = cnn_round_chunks(a.m);
+    for (int64_t lo = 0; lo < space; lo += CNN_ROUND_TILES) {
+        a.tile_lo = (int)lo;
+        a.tiles = (int)(space - lo < CNN_ROUND_TILES ? space - lo : CNN_ROUND_TILES);
+        a.rc = pick_rc(c, nch, a.tiles);
+        a.finish = a.g > 0 && lo + a.tiles == space;
+        const hipError_t he = launch_cnn_round(a, c->stream);
+        if (he != hipSuccess) return fail(BK_EHIP, "k_cnn_round launch: %s", hipGetErrorString(he));
+    }
+    return BK_OK;
+}
+
+CnnRoundLaunch base_launch(bk_ctx *c) {
+    CnnRoundLaunch a = {};
+    a.m = c->cnn_dims;
+    a.X = (const float *)c->cnn_X.p;
+    a.y = (const int32_t *)c->cnn_y.p;
+    a.nv = c->cnn_nv;
+    a.ww = (const double *)c->cr_w.p;
+    a.flags = (uint8_t *)c->cr_flags.p;
+    a.scratch = (float *)c->cr_scratch.p;
+    a.cnt = (unsigned int *)c->cr_cnt.p;
+    return a;
+}
+
+}  // namespace
+}  // namespace bk
+
+int bk_roni_cnn_round_begin(bk_ctx *c, const double *ww, int where) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->cnn_nv < 1) return fail(BK_EINVAL, "no validation set: call bk_roni_cnn_set_validation");
+    if (!ww) return fail(BK_EINVAL, "null pointer argument");
+    CHK(check_where(where));
+    const CnnDims &m = c->cnn_dims;
+    const int64_t nv = c->cnn_nv, space = cnn_tiles(m, nv);
+    DeviceGuard dg(c->device);
+    HostDrain drain{c};
+    c->cr_live = 0;  // no round until the new one's evaluation is queued
+    CHK(ensure(c->cr_w, (size_t)m.d * sizeof(double)));
+    CHK(ensure(c->cr_flags, (size_t)nv));
+    CHK(ensure_launch_state(c, space));
+    if (!c->ev_round) HIPCHK(hipEventCreateWithFlags(&c->ev_round, hipEventDisableTiming));
+    HIPCHK(hipMemcpyAsync(c->cr_w.p, ww, (size_t)m.d * sizeof(double),
+                          where == BK_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                          c->stream));
+    HIPCHK(hipEventRecord(c->ev_round, c->stream));
+    CnnRoundLaunch a = base_launch(c);
+    CHK(launch_space(c, a, space));  // runs on behind the return
+    HIPCHK(hipEventSynchronize(c->ev_round));  // ww is consumed
+    drain.armed = false;
+    c->cr_live = 1;
+    return BK_OK;
+}
+
+int bk_roni_cnn_round_score_batches(bk_ctx *c, const double *const *deltas, int64_t count, int where,
+                                    const int64_t *idx, int64_t nb, double *scores,
+                                    int32_t *near_ties) {
+    if (!c) return fail(BK_EINVAL, "null context");
+    if (!deltas || !idx || !scores) return fail(BK_EINVAL, "null pointer argument");
+    if (count < 1) return fail(BK_EINVAL, "count=%lld < 1", (long long)count);
+    if (nb < 1) return fail(BK_EINVAL, "need a batch of nb >= 1 samples (nb=%lld)", (long long)nb);
+    CHK(check_where(where));
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->cnn_nv < 1) return fail(BK_EINVAL, "no validation set: call bk_roni_cnn_set_validation");
+    if (!c->cr_live) return fail(BK_EINVAL, "no round: call bk_roni_cnn_round_begin");
+    const CnnDims &m = c->cnn_dims;
+    const int64_t nv = c->cnn_nv, d = m.d;
+    if (count > 262139) return fail(BK_ENOTSUP, "RONI n=%lld exceeds 262139", (long long)count);
+    if (nb > ((int64_t)1 << 31))
+        return fail(BK_ENOTSUP, "the batches' %lld tiles exceed the grid", (long long)cnn_tiles(m, nb));
+    for (int64_t i = 0; i < count; ++i)
+        if (!deltas[i]) return fail(BK_EINVAL, "null row deltas[%lld]", (long long)i);
+    for (int64_t j = 0; j < count; ++j)
+        for (int e = 0; e < 2; ++e)
+            for (int64_t s = 0; s < nb; ++s) {
+                const int64_t v = idx[(2 * j + e) * nb + s];
+                if (v < 0 || v >= nv)
+                    return fail(BK_EINVAL,
+                                "batch index %lld outside [0, %lld): update %lld, evaluation %d "
+                                "(%s), position %lld",
+                                (long long)v, (long long)nv, (long long)j, e,
+                                e ? "after" : "original", (long long)s);
+            }
+    DeviceGuard dg(c->device);
+    HostDrain drain{c};  // error returns: queued copies and launches may still read the rows
+    const int64_t tpe = cnn_tiles(m, nb);
+    const int64_t g0 = count < RONI_ROUND_G ? count : RONI_ROUND_G;  // the largest group
+    CHK(ensure_launch_state(c, g0 * tpe));
+    CHK(ensure_round_out(c, count, 2 * count));
+    const double *staged = nullptr;
+    if (where != BK_DEVICE) {  // only the rows go up
+        CHK(ensure(c->round_rows, (size_t)count * d * sizeof(double)));
+        double *dst = (double *)c->round_rows.p;
+        for (int64_t i = 0; i < count; ++i)
+            HIPCHK(hipMemcpyAsync(dst + i * d, deltas[i], (size_t)d * sizeof(double),
+                                  hipMemcpyHostToDevice, c->stream));
+        staged = dst;
+    }
+    // a group's indices ride in its launch's arguments when they fit
+    const bool in_args = 2 * g0 * nb <= ROUND_IDX_ARGS;
+    if (!in_args) {
+        const size_t bytes = (size_t)2 * count * nb * sizeof(int64_t);
+        CHK(ensure(c->round_idx, bytes));
+        HIPCHK(hipMemcpyAsync(c->round_idx.p, idx, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    double *dsc = (double *)c->round_out_dev;
+    int32_t *dnt = (int32_t *)(dsc + count);
+    for (int64_t q0 = 0; q0 < count; q0 += RONI_ROUND_G) {
+        const int g = (int)(count - q0 < RONI_ROUND_G ? count - q0 : RONI_ROUND_G);
+        CnnRoundLaunch a = base_launch(c);
+        a.g = g;
+        a.nb = nb;
+        for (int q = 0; q < g; ++q) a.rows.p[q] = staged ? staged + (q0 + q) * d : deltas[q0 + q];
+        if (in_args)
+            for (int64_t i = 0; i < 2 * g * nb; ++i) a.idx_arg.v[i] = (int32_t)idx[2 * q0 * nb + i];
+        else
+            a.idx_dev = (const int64_t *)c->round_idx.p + 2 * q0 * nb;
+        a.scores = dsc + q0;
+        a.near = dnt + 2 * q0;
+        CHK(launch_space(c, a, g * tpe));
+    }
+    HIPCHK(wait_stream(c));
+    drain.armed = false;
+    const char *h = (const char *)c->round_out;
+    memcpy(scores, h, (size_t)count * sizeof(double));
+    if (near_ties)
+        memcpy(near_ties, h + (size_t)count * sizeof(double), (size_t)2 * count * sizeof(int32_t));
+    return BK_OK;
+}

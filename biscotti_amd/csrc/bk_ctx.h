@@ -439,6 +439,15 @@ struct bk_ctx {
     DevBuf cnn_X, cnn_y, cnn_cnt;
     int64_t cnn_nv = 0;
     CnnDims cnn_dims = {};
+    // the CNN verifier's round (bk_roni_cnn_round_*, bk_cnn_round_api.hip): the
+    // held model (fp64), its verdict on every validation sample (one byte: bit 0
+    // wrong, bit 1 near tie), the conv items' scratch of one launch (at most
+    // CNN_ROUND_TILES tiles) and the launches' counters (zeroed once: every
+    // group of launches leaves them zero); live until the next begin or
+    // bk_roni_cnn_set_validation.  A score call's rows, indices and outputs go
+    // through the other rounds' round_rows, round_idx and round_out
+    DevBuf cr_w, cr_flags, cr_scratch, cr_cnt;
+    int cr_live = 0;
     // RONI rounds (bk_roni*_round_*): the iteration's model, its evaluation's
     // counts (logistic: mismatches; softmax: correct, near ties) and the begin's
     // prepared columns (softmax: the widened fp32 weights and their norms), kept
@@ -689,6 +698,9 @@ int eval_state(bk_ctx *c);
 int check_set_index(int set);
 // bk_cnn_api.hip: bk.h's limits (BK_EINVAL for a null shape, BK_ENOTSUP outside them)
 int cnn_check_shape(const bk_cnn_shape *shape, CnnDims *out);
+// bk_entries.hip: the mapped pinned block a round's score kernels write (count
+// scores, then nnt near-tie counts), shared with bk_cnn_round_api.hip
+int ensure_round_out(bk_ctx *c, int64_t count, int64_t nnt);
 // bk_host.hip
 int stage_host_pipelined(bk_ctx *c, const void *X, int64_t ld, int dtype, const double *noise,
                          int64_t k, int64_t noise_ld, int64_t n, int64_t d, char *dX,

@@ -390,7 +390,7 @@ static int round_upload_ww(bk_ctx *c, DevBuf &w, const double *ww, int64_t d, in
 
 // the mapped pinned block a score call's kernels write: count scores, then
 // nnt near-tie counts (1 + count; the mini-batch form: 2 count)
-static int ensure_round_out(bk_ctx *c, int64_t count, int64_t nnt) {
+int bk::ensure_round_out(bk_ctx *c, int64_t count, int64_t nnt) {
     const size_t bytes = (size_t)count * sizeof(double) + (size_t)nnt * sizeof(int32_t);
     if (bytes <= c->round_out_bytes) return BK_OK;
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -377,6 +377,48 @@ __host__ __device__ inline int cnn_tiles(const CnnDims &m, int64_t samples) {
     return (int)((samples + m.ts - 1) / m.ts);
 }
 hipError_t launch_cnn(const CnnLaunch &a, int64_t tiles, hipStream_t st);
+// bk_cnn_round.hip: the CNN verifier's rounds (bk_roni_cnn_round_*, DESIGN.md
+// §5aa).  One launch runs `tiles` sample tiles (dims.ts samples each) of a
+// linear tile space, from tile_lo on: the begin's (g = 0) is the validation set
+// under the held model ww, a score group's is g evaluations `after` of
+// cnn_tiles(nb) tiles each, evaluation q on the samples idx[(2 q + 1) nb ..]
+// under fp32(ww + rows.p[q]).  Every tile is cut into conv items of rc ring
+// chunks (CNN_ROUND_KC features each): the grid is tiles x ceil(chunks / rc)
+// workgroups, and the tile's last item out runs its two chains.  idx: the
+// group's 2 g nb range-checked indices, on the device or (idx_dev null) in
+// idx_arg.  scratch: tiles x cnn_round_tile_floats floats.  cnt:
+// CNN_ROUND_CNT_WORDS words, zero before a group's first launch and left zero
+// by its last (finish != 0), whose last workgroup out writes scores (g) and
+// near (2 g).  flags: one byte per validation sample (bit 0 wrong, bit 1 near
+// tie), written by the begin, read by a finish
+constexpr int CNN_ROUND_TILES = 128, CNN_ROUND_KC = 64;
+constexpr int CNN_ROUND_CNT_WORDS = 2 * RONI_ROUND_G + CNN_ROUND_TILES + 1;
+struct CnnRoundLaunch {
+    CnnDims m;
+    const float *X;
+    const int32_t *y;
+    int64_t nv;
+    const double *ww;
+    RoundRows rows;
+    int g;
+    const int64_t *idx_dev;
+    RoundIdx idx_arg;
+    int64_t nb;
+    int tile_lo, tiles, rc, finish;
+    uint8_t *flags;
+    float *scratch;
+    unsigned int *cnt;
+    double *scores;
+    int32_t *near;
+};
+__host__ __device__ inline int cnn_round_chunks(const CnnDims &m) {
+    return (int)((m.F + CNN_ROUND_KC - 1) / CNN_ROUND_KC);
+}
+// a tile's activations, then its bound operands: per feature 16 samples, fp32
+inline size_t cnn_round_tile_floats(const CnnDims &m) {
+    return (size_t)2 * cnn_round_chunks(m) * CNN_ROUND_KC * 16;
+}
+hipError_t launch_cnn_round(const CnnRoundLaunch &a, hipStream_t st);
 // bk_i8.hip: K1i8, the Gram of fp32 rows from exact int8 digit slices
 // (BK_F32_I8): column ranges (one per XCD), digit planes [3][npad][dp] int8
 struct I8Layout {

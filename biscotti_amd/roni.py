@@ -270,10 +270,19 @@ class CNNRONIValidator(SoftmaxRONIValidator):
     bk_cnn_shape): SoftmaxRONIValidator's mini-batch semantics -- `original` and
     `after` each on a freshly drawn last batch of batch_size samples (draw_batches,
     last_idx, seed) -- scored by bk_roni_cnn_batches.  shape = (h, w, k, pad,
-    c_out, n_classes); Xvalid nv x (h w) float32 images.  No rounds."""
+    c_out, n_classes); Xvalid nv x (h w) float32 images.
+
+    Rounds (bk_roni_cnn_round_*): begin_round(ww) holds the model on the GPU with
+    its verdict on every validation sample; score_round(deltas, idx=None) scores
+    each update on its own two freshly drawn last batches -- `original` from the
+    held verdicts, `after` by one forward pass -- bitwise scores(ww, deltas, idx)
+    of a same-seed validator; verify_update(..., round=True) drives both.  They
+    are always the mini-batch form; round_batches is taken for symmetry with
+    SoftmaxRONIValidator."""
 
     def __init__(self, Xvalid, yvalid, shape, engine: Optional[Engine] = None,
-                 priv_prob: float = 0.0, batch_size: int = 10, seed=None):
+                 priv_prob: float = 0.0, batch_size: int = 10, seed=None,
+                 round_batches: bool = True):
         self._engine = engine if engine is not None else default_engine(0)
         h, w, k, pad, co, C = (int(v) for v in shape)
         y = np.ascontiguousarray(yvalid, dtype=np.int32)
@@ -284,7 +293,7 @@ class CNNRONIValidator(SoftmaxRONIValidator):
         self.d = co * k * k + co + C * co * (h + 2 * pad - k + 1) * (w + 2 * pad - k + 1) + C
         self.priv_prob = priv_prob
         self.batch_size = max(1, min(int(batch_size), self.nv))
-        self.round_batches = False
+        self.round_batches = bool(round_batches)
         self._rng = np.random.default_rng(seed)
         self.last_near_ties = None
         self.last_idx = None
@@ -292,8 +301,40 @@ class CNNRONIValidator(SoftmaxRONIValidator):
         check(lib().bk_roni_cnn_set_validation(self._engine.ctx, X.ctypes.data, self.nv, h * w,
                                                y.ctypes.data, sh))
 
+    def _begin(self, ww):
+        check(lib().bk_roni_cnn_round_begin(self._engine.ctx, ww.ctypes.data, BK_HOST))
+
     def begin_round(self, ww):
-        raise ValueError("the CNN verifier has no rounds")
+        if not self.round_batches:
+            raise ValueError("this validator was built with round_batches=False")
+        RONIValidator.begin_round(self, ww)
+
+    def score_round(self, deltas, idx=None) -> np.ndarray:
+        """Each update against the held model on its two drawn batches (or idx,
+        (n, 2, nb)): bitwise scores(ww, deltas, idx)
+        (bk_roni_cnn_round_score_batches)."""
+        if self._round_ww is None:
+            raise ValueError("no round: call begin_round(ww) first")
+        rows = [np.ascontiguousarray(r, dtype=np.float64) for r in deltas]
+        n = len(rows)
+        if not rows or any(r.shape != (self.d,) for r in rows):
+            raise ValueError("deltas must be a non-empty sequence of (d,) rows with d = %d" % self.d)
+        idx = self.draw_batches(n) if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        if idx.ndim != 3 or idx.shape[:2] != (n, 2) or idx.shape[2] < 1:
+            raise ValueError("idx must be (n, 2, nb)")
+        out = np.empty(n, dtype=np.float64)
+        nt = np.empty((n, 2), dtype=np.int32)
+        table = (ctypes.c_void_p * n)(*[r.ctypes.data for r in rows])
+        check(lib().bk_roni_cnn_round_score_batches(self._engine.ctx, table, n, BK_HOST,
+                                                    idx.ctypes.data, idx.shape[2],
+                                                    out.ctypes.data, nt.ctypes.data))
+        self.last_idx, self.last_near_ties = idx, nt
+        return out
+
+    def verify_update(self, update: Update, latest_gradient, round: bool = False) -> bool:
+        if round and not self.round_batches:
+            raise ValueError("round=True needs round_batches=True")
+        return RONIValidator.verify_update(self, update, latest_gradient, round)
 
     def scores(self, ww, deltas, idx=None) -> np.ndarray:
         ww = np.ascontiguousarray(ww, dtype=np.float64)

@@ -1491,6 +1491,48 @@ int bk_roni_cnn_set_validation(bk_ctx *ctx, const float *Xv, int64_t nv, int64_t
                                const int32_t *yv, const bk_cnn_shape *shape);
 int bk_roni_cnn_batches(bk_ctx *ctx, const double *ww, const double *deltas, int64_t n, int64_t ld,
                         const int64_t *idx, int64_t nb, double *scores, int32_t *near_ties);
+/* The CNN verifier's round (RONI rounds above: one update per RPC, every update
+ * of an iteration against the same model).
+ *   bk_roni_cnn_round_begin  needs bk_roni_cnn_set_validation.  ww (the shape's
+ *                  d doubles) is at `where` (BK_HOST, BK_HOST_PINNED or
+ *                  BK_DEVICE) and is consumed on return.  The model is kept on
+ *                  the device as fp64 (an `after` model is fp32(ww + delta), the
+ *                  sum taken in fp64: THE ARITHMETIC above), and its verdict on
+ *                  every sample of the validation set as one byte (bit 0 wrong,
+ *                  bit 1 near tie); that evaluation runs on asynchronously on
+ *                  the context stream.  The round lives until the next begin or
+ *                  the next bk_roni_cnn_set_validation, which invalidates it.
+ *   bk_roni_cnn_round_score_batches  rows as for
+ *                  bk_roni_softmax_round_score_batches: count >= 1 separately
+ *                  allocated rows of d doubles at `where`, 8-byte aligned, no
+ *                  pointer retained on return.  idx is a HOST array in
+ *                  bk_roni_cnn_batches' layout, count x 2 x nb; any nb >= 1; a
+ *                  repeated index counts as often as it occurs.  Update j's
+ *                  `original` reads no image and no model: its wrong and
+ *                  near-tie counts are the sums of the held bytes over
+ *                  idx[(2 j) nb ..].  Its `after` is one forward pass of
+ *                  idx[(2 j + 1) nb ..] under fp32(ww + delta_j).  Writes
+ *                  scores[j] and near_ties (nullable, 2 count: update j's
+ *                  original, then its after).  Synchronous.  Every score and
+ *                  near-tie count is bitwise what one bk_roni_cnn_batches call
+ *                  on the same ww, rows and idx returns.  Only the rows go up;
+ *                  groups of up to BK_RONI_ROUND_G updates share one launch (a
+ *                  group of more than 128 sample tiles takes several).
+ * Checked in this order, before any copy, launch or state change (a refused
+ * call leaves the round as it was).  Begin: BK_EINVAL for a null ctx, no
+ * validation set, a null ww or a bad where.  Score: BK_EINVAL for a null ctx,
+ * deltas, idx or scores, count < 1, nb < 1 or a bad where; BK_EINVAL for no
+ * validation set or no live round; BK_ENOTSUP for a count beyond
+ * bk_roni_cnn_batches' n; BK_EINVAL for a null row (named); BK_EINVAL for an
+ * index outside [0, nv) (the update, the evaluation and the position named).
+ * Added without a change of BK_ABI_VERSION (14); the launches carry no timing
+ * id.  bk_row_table names the rows' pointer-table type for callers whose
+ * language wants a named type to convert to (cgo: (C.bk_row_table)(p)). */
+typedef const double *const *bk_row_table;
+int bk_roni_cnn_round_begin(bk_ctx *ctx, const double *ww, int where);
+int bk_roni_cnn_round_score_batches(bk_ctx *ctx, const double *const *deltas, int64_t count,
+                                    int where, const int64_t *idx, int64_t nb, double *scores,
+                                    int32_t *near_ties);
 
 /* The one-layer CNN's gradient step -- privateFun of a peer running
  * MNISTCNNModel (ML/Pytorch/client_obj.py:73-77 -> client.py:38-65: autograd,
