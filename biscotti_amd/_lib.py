@@ -113,6 +113,9 @@ SIGNATURES = {
     "bk_eval_set_cnn": (_i, [_p, _i, _p, _i64, _i64, _p, _p]),
     "bk_roni_cnn_set_validation": (_i, [_p, _p, _i64, _i64, _p, _p]),
     "bk_roni_cnn_batches": (_i, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _p]),
+    "bk_eval_set_cnn2": (_i, [_p, _i, _p, _i64, _i64, _p, _p]),
+    "bk_roni_cnn2_set_validation": (_i, [_p, _p, _i64, _i64, _p, _p]),
+    "bk_roni_cnn2_batches": (_i, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _p]),
     "bk_roni_cnn_round_begin": (_i, [_p, _p, _i]),
     "bk_roni_cnn_round_score_batches": (_i, [_p, _p, _i64, _i, _p, _i64, _p, _p]),
     "bk_shares_chunks": (_i64, [_i64, _i]),

@@ -151,12 +151,13 @@ struct Shares {
 
 // bk_eval*: the evaluation sets of a context (bk_eval.hip),
 // buffers of their own: RONI's validation sets and rounds never see them
-enum { EVAL_EMPTY = 0, EVAL_LOGISTIC = 1, EVAL_SOFTMAX = 2, EVAL_CNN = 3 };
+enum { EVAL_EMPTY = 0, EVAL_LOGISTIC = 1, EVAL_SOFTMAX = 2, EVAL_CNN = 3, EVAL_CNN2 = 4 };
 struct EvalSlot {
     int kind = EVAL_EMPTY;
     int64_t nv = 0, d = 0;    // samples; the model's length
     int64_t din = 0, C = 0;   // softmax: d = C (din + 1); CNN: din = h w
     CnnDims cnn = {};         // CNN: the shape (d = cnn.d)
+    Cnn2Dims cnn2 = {};       // two-layer CNN: the shape (d = cnn2.d; din = c_in h w)
     DevBuf X, y, xn;          // compact rows (row stride d / din); xn: softmax only
 };
 struct Eval {
@@ -439,6 +440,14 @@ struct bk_ctx {
     DevBuf cnn_X, cnn_y, cnn_cnt;
     int64_t cnn_nv = 0;
     CnnDims cnn_dims = {};
+    // the two-layer CNN (bk_cnn2_api.hip): its RONI validation set (compact
+    // c_in h w fp32 rows, int32 labels), and what a launch of k_cnn2 needs for
+    // bk_eval and the RONI alike: the tiles' feature scratch and their hand-off
+    // counters (zeroed when they grow: every launch leaves them zero).  The
+    // RONI's counters are cnn_cnt, its other scratch the softmax form's
+    DevBuf c2_X, c2_y, c2_scratch, c2_tcnt;
+    int64_t c2_nv = 0;
+    Cnn2Dims c2_dims = {};
     // the CNN verifier's round (bk_roni_cnn_round_*, bk_cnn_round_api.hip): the
     // held model (fp64), its verdict on every validation sample (one byte: bit 0
     // wrong, bit 1 near tie), the conv items' scratch of one launch (at most
@@ -698,6 +707,8 @@ int eval_state(bk_ctx *c);
 int check_set_index(int set);
 // bk_cnn_api.hip: bk.h's limits (BK_EINVAL for a null shape, BK_ENOTSUP outside them)
 int cnn_check_shape(const bk_cnn_shape *shape, CnnDims *out);
+// bk_cnn2_api.hip: a launch's tile scratch and hand-off counters for `tiles` tiles
+int cnn2_scratch(bk_ctx *c, const Cnn2Dims &m, int64_t tiles);
 // bk_entries.hip: the mapped pinned block a round's score kernels write (count
 // scores, then nnt near-tie counts), shared with bk_cnn_round_api.hip
 int ensure_round_out(bk_ctx *c, int64_t count, int64_t nnt);

@@ -349,6 +349,9 @@ int eval_check_sets(bk_ctx *c, int64_t d, const int *sets, int nsets) {
         if (kind == EVAL_CNN && memcmp(&s->cnn, &c->eval->set[sets[0]].cnn, sizeof(CnnDims)) != 0)
             return fail(BK_EINVAL, "evaluation set %d is of another CNN shape than set %d", sets[i],
                         sets[0]);
+        if (kind == EVAL_CNN2 && memcmp(&s->cnn2, &c->eval->set[sets[0]].cnn2, sizeof(Cnn2Dims)) != 0)
+            return fail(BK_EINVAL, "evaluation set %d is of another CNN shape than set %d", sets[i],
+                        sets[0]);
         for (int j = 0; j < i; ++j)
             if (sets[j] == sets[i]) return fail(BK_EINVAL, "evaluation set %d is named twice", sets[i]);
     }
@@ -381,6 +384,32 @@ int eval_queue(bk_ctx *c, const double *dw, const int *sets, int nsets) {
     CHK(ensure_eval_out(c, e));
     const EvalSlot &first = e->set[sets[0]];
     const bool softmax = first.kind == EVAL_SOFTMAX, cnn = first.kind == EVAL_CNN;
+    if (first.kind == EVAL_CNN2) {  // k_cnn2 (bk_cnn2.hip): a workgroup per sample, fc tiles of 16
+        EvalDesc desc = {};
+        desc.nsets = nsets;
+        int64_t samples = 0, tiles = 0;
+        for (int i = 0; i < nsets; ++i) {
+            const EvalSlot &s = e->set[sets[i]];
+            desc.s[i] = {s.X.p, s.y.p, nullptr, s.nv, s.din, (int)samples};
+            samples += s.nv;
+            tiles += cnn2_tiles(s.nv);
+            if (samples > 0x7fffffff) return fail(BK_ENOTSUP, "the sets' %lld samples exceed the grid",
+                                                  (long long)samples);
+        }
+        CHK(cnn2_scratch(c, first.cnn2, tiles));
+        Cnn2Launch a = {};
+        a.desc = desc;
+        a.m = first.cnn2;
+        a.ww = dw;
+        a.cnt = (unsigned int *)e->cnt.p;
+        a.tcnt = (unsigned int *)c->c2_tcnt.p;
+        a.scratch = (float *)c->c2_scratch.p;
+        a.out = e->out_dev;
+        const hipError_t he = launch_cnn2(a, samples, c->stream);
+        if (he != hipSuccess) return fail(BK_EHIP, "k_cnn2 launch: %s", hipGetErrorString(he));
+        ++e->launches;
+        return BK_OK;
+    }
     const int ts = cnn ? first.cnn.ts : softmax ? EVAL_LOGITS_TS : EVAL_SIGN_TS;
     EvalDesc desc = {};
     desc.nsets = nsets;

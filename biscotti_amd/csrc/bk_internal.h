@@ -377,6 +377,47 @@ __host__ __device__ inline int cnn_tiles(const CnnDims &m, int64_t samples) {
     return (int)((samples + m.ts - 1) / m.ts);
 }
 hipError_t launch_cnn(const CnnLaunch &a, int64_t tiles, hipStream_t st);
+// bk_cnn2.hip: the two-layer CNN's forward pass (bk.h bk_cnn2_shape, DESIGN.md
+// §5ab), one launch for either addressing, as launch_cnn's -- but a workgroup
+// is ONE sample: desc.s[i].tile0 is the set's first workgroup (the samples
+// before it), the grid the samples of all sets (batches: 2 n nb).  scratch:
+// per tile of 16 samples 2 x F4 x 16 floats (the pooled features, then their
+// bound operands, the fc MFMA's B operand); tcnt: one zeroed word per tile,
+// left zero.  cnt / out / scores / near as for launch_cnn
+struct Cnn2Dims {
+    int c_in, h, w, k, pad, c1, c2, C;
+    int ph1, pw1;        // the first pooled map
+    int P1h, P1w, ps1;   // the same zero-padded by pad: conv2's source in LDS; its plane stride
+    int ph2, pw2, np2;   // the second pooled map and its positions
+    int T1, T2;          // taps per pre-activation: c_in k k, c1 k k
+    int st2, ws;         // conv2's MFMA steps; a conv2 weight row's LDS stride (floats)
+    int lds;             // dynamic LDS bytes
+    int64_t F, F4, d;    // features c2 np2; F rounded up to 4; the flat model's length
+};
+// false: outside bk.h's limits
+bool cnn2_dims(int c_in, int h, int w, int k, int pad, int c1, int c2, int C, Cnn2Dims *out);
+// the near-tie bound's factors (bk.h), in the order of fp64 operations tests/cnn2_ref.py repeats
+struct Cnn2Gammas {
+    double g1, g2, h2, gF, hF;
+};
+Cnn2Gammas cnn2_gammas(const Cnn2Dims &m);
+struct Cnn2Launch {
+    EvalDesc desc;
+    Cnn2Dims m;
+    const double *ww, *deltas;
+    int64_t ld;
+    const int64_t *idx;
+    int64_t nb, n;
+    unsigned int *cnt, *tcnt;
+    float *scratch;
+    EvalOut *out;
+    double *scores;
+    int32_t *near;
+};
+constexpr int CNN2_TS = 16;  // samples per fc tile: the MFMA's columns
+inline int64_t cnn2_tiles(int64_t samples) { return (samples + CNN2_TS - 1) / CNN2_TS; }
+__host__ __device__ inline size_t cnn2_tile_floats(const Cnn2Dims &m) { return (size_t)2 * m.F4 * CNN2_TS; }
+hipError_t launch_cnn2(const Cnn2Launch &a, int64_t samples, hipStream_t st);
 // bk_cnn_round.hip: the CNN verifier's rounds (bk_roni_cnn_round_*, DESIGN.md
 // §5aa).  One launch runs `tiles` sample tiles (dims.ts samples each) of a
 // linear tile space, from tile_lo on: the begin's (g = 0) is the validation set

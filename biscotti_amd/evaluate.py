@@ -15,7 +15,7 @@ from typing import Optional
 
 import numpy as np
 
-from .krum import Engine, default_engine
+from .krum import Engine, cnn2_model_length, default_engine
 
 __all__ = ["ModelEvaluator", "TRAIN", "TEST", "ATTACK"]
 
@@ -27,18 +27,22 @@ class ModelEvaluator:
     the logistic model (X float64, labels as numbers, a model of d weights);
     otherwise the softmax model (X float32, integer labels, a model of
     n_classes * (d_in + 1) entries: W row-major, then b).  cnn_shape = (h, w, k,
-    pad, c_out, n_classes): the one-layer CNN model instead (set_cnn).
+    pad, c_out, n_classes): the one-layer CNN model instead (set_cnn);
+    cnn2_shape = (c_in, h, w, k, pad, c1, c2, n_classes): the two-layer one
+    (set_cnn2).
 
     One evaluator per engine at a time: the sets live in the engine's context
     (slots TRAIN, TEST, ATTACK)."""
 
     def __init__(self, train=None, test=None, attack=None, n_classes: Optional[int] = None,
-                 engine: Optional[Engine] = None, cnn_shape=None):
-        if cnn_shape is not None:  # the one-layer CNN model (bk.h bk_cnn_shape)
+                 engine: Optional[Engine] = None, cnn_shape=None, cnn2_shape=None):
+        if cnn_shape is not None or cnn2_shape is not None:  # the CNN models (bk.h bk_cnn*_shape)
             self._engine = engine if engine is not None else default_engine(0)
             self._slots, self.near_ties = [], {}
             for slot, s in ((TRAIN, train), (TEST, test), (ATTACK, attack)):
-                if s is not None:
+                if s is not None and cnn2_shape is not None:
+                    self.set_cnn2(slot, s[0], s[1], cnn2_shape)
+                elif s is not None:
                     self.set_cnn(slot, s[0], s[1], cnn_shape)
             if not self._slots:
                 raise ValueError("an evaluator needs a train, test or attack set")
@@ -88,6 +92,18 @@ class ModelEvaluator:
         self._engine.eval_set_cnn(slot, X, y, (h, w, k, pad, co, C))
         F = co * (h + 2 * pad - k + 1) * (w + 2 * pad - k + 1)
         self.n_classes, self.d_in, self.d = C, h * w, co * k * k + co + C * F + C
+        if slot not in self._slots:
+            self._slots.append(slot)
+
+    def set_cnn2(self, slot, X, y, shape):
+        """Make (X, y) the slot's set for the two-layer CNN model of `shape` =
+        (c_in, h, w, k, pad, c1, c2, n_classes): X nv x (c_in h w) float32,
+        channel-major.  test_error, attack_rate and check_convergence then score
+        LFWCNNModel's flat model."""
+        shape = tuple(int(v) for v in shape)
+        X = np.ascontiguousarray(X, dtype=np.float32).reshape(len(y), -1)
+        self._engine.eval_set_cnn2(slot, X, y, shape)
+        self.n_classes, self.d_in, self.d = shape[7], X.shape[1], cnn2_model_length(shape)
         if slot not in self._slots:
             self._slots.append(slot)
 

@@ -184,6 +184,15 @@ class GroupEngine:
         return sel, sc, mean
 
 
+def cnn2_model_length(shape):
+    """d of the two-layer CNN model of shape (c_in, h, w, k, pad, c1, c2,
+    n_classes), as bk.h's bk_cnn2_shape section counts it."""
+    ci, h, w, k, pad, c1, c2, C = (int(v) for v in shape)
+    ph, pw = (h + 2 * pad - k + 1) // 2, (w + 2 * pad - k + 1) // 2
+    F = c2 * ((ph + 2 * pad - k + 1) // 2) * ((pw + 2 * pad - k + 1) // 2)
+    return c1 * ci * k * k + c1 + c2 * c1 * k * k + c2 + C * F + C
+
+
 class Engine:
     """One libbk context (bk_ctx) bound to one GPU."""
 
@@ -852,6 +861,25 @@ class Engine:
             raise ValueError("X must have h * w = %d columns" % (sh[0] * sh[1]))
         check(lib().bk_eval_set_cnn(self._ctx, int(set_index), X.ctypes.data, X.shape[0],
                                     X.strides[0] // 4, y32.ctypes.data, sh))
+
+    def eval_set_cnn2(self, set_index, X, y, shape):
+        """X nv x (c_in h w) float32 samples (channel-major), y integer labels in
+        [0, n_classes), shape (c_in, h, w, k, pad, c1, c2, n_classes): a set for
+        the two-layer CNN model (bk.h bk_cnn2_shape); the model scored on it is
+        LFWCNNModel's flat layout."""
+        X = np.asarray(X)
+        if X.ndim != 2 or X.dtype != np.float32 or X.shape[0] < 1:
+            raise ValueError("X must be a float32 matrix, nv x (c_in h w)")
+        if X.strides[1] != 4 or X.strides[0] % 4 or X.strides[0] < 4 * X.shape[1]:
+            X = np.ascontiguousarray(X)
+        y32 = np.ascontiguousarray(y, dtype=np.int32)
+        if y32.shape != (X.shape[0],) or not np.array_equal(y32, np.asarray(y)):
+            raise ValueError("y must have one int32 label per row of X")
+        sh = (ctypes.c_int32 * 8)(*[int(v) for v in shape])
+        if X.shape[1] != sh[0] * sh[1] * sh[2]:
+            raise ValueError("X must have c_in * h * w = %d columns" % (sh[0] * sh[1] * sh[2]))
+        check(lib().bk_eval_set_cnn2(self._ctx, int(set_index), X.ctypes.data, X.shape[0],
+                                     X.strides[0] // 4, y32.ctypes.data, sh))
 
     def eval_clear(self, set_index):
         check(lib().bk_eval_clear(self._ctx, int(set_index)))

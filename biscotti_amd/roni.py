@@ -23,9 +23,10 @@ import ctypes
 import numpy as np
 
 from ._lib import BK_HOST, check, lib
-from .krum import Engine, Update, default_engine
+from .krum import Engine, Update, cnn2_model_length, default_engine
 
-__all__ = ["RONI_THRESHOLD", "RONIValidator", "SoftmaxRONIValidator", "CNNRONIValidator", "set_validation", "roni"]
+__all__ = ["RONI_THRESHOLD", "RONIValidator", "SoftmaxRONIValidator", "CNNRONIValidator", "CNN2RONIValidator",
+           "set_validation", "roni"]
 
 RONI_THRESHOLD = 0.02  # main.go:213
 
@@ -280,6 +281,8 @@ class CNNRONIValidator(SoftmaxRONIValidator):
     are always the mini-batch form; round_batches is taken for symmetry with
     SoftmaxRONIValidator."""
 
+    _batches_entry = "bk_roni_cnn_batches"
+
     def __init__(self, Xvalid, yvalid, shape, engine: Optional[Engine] = None,
                  priv_prob: float = 0.0, batch_size: int = 10, seed=None,
                  round_batches: bool = True):
@@ -347,11 +350,41 @@ class CNNRONIValidator(SoftmaxRONIValidator):
             raise ValueError("idx must be (n, 2, nb)")
         out = np.empty(n, dtype=np.float64)
         nt = np.empty((n, 2), dtype=np.int32)
-        check(lib().bk_roni_cnn_batches(self._engine.ctx, ww.ctypes.data, D.ctypes.data, n, self.d,
-                                        idx.ctypes.data, idx.shape[2], out.ctypes.data,
-                                        nt.ctypes.data))
+        check(getattr(lib(), self._batches_entry)(self._engine.ctx, ww.ctypes.data, D.ctypes.data, n,
+                                                  self.d, idx.ctypes.data, idx.shape[2],
+                                                  out.ctypes.data, nt.ctypes.data))
         self.last_idx, self.last_near_ties = idx, nt
         return out
+
+
+class CNN2RONIValidator(CNNRONIValidator):
+    """The torch-path verifier for the two-layer CNN model (LFWCNNModel; bk.h
+    bk_cnn2_shape): CNNRONIValidator's mini-batch semantics, scored by
+    bk_roni_cnn2_batches.  shape = (c_in, h, w, k, pad, c1, c2, n_classes);
+    Xvalid nv x (c_in h w) float32, channel-major.  No rounds: begin_round and
+    verify_update(round=True) raise."""
+
+    _batches_entry = "bk_roni_cnn2_batches"
+
+    def __init__(self, Xvalid, yvalid, shape, engine: Optional[Engine] = None,
+                 priv_prob: float = 0.0, batch_size: int = 10, seed=None):
+        self._engine = engine if engine is not None else default_engine(0)
+        shape = tuple(int(v) for v in shape)
+        y = np.ascontiguousarray(yvalid, dtype=np.int32)
+        X = np.ascontiguousarray(Xvalid, dtype=np.float32).reshape(len(y), -1)
+        if X.shape[1] != shape[0] * shape[1] * shape[2]:
+            raise ValueError("Xvalid must be (nv, c_in * h * w)")
+        self.nv, self.d_in, self.n_classes = X.shape[0], X.shape[1], shape[7]
+        self.d = cnn2_model_length(shape)
+        self.priv_prob = priv_prob
+        self.batch_size = max(1, min(int(batch_size), self.nv))
+        self.round_batches = False
+        self._rng = np.random.default_rng(seed)
+        self.last_near_ties = None
+        self.last_idx = None
+        sh = (ctypes.c_int32 * 8)(*shape)
+        check(lib().bk_roni_cnn2_set_validation(self._engine.ctx, X.ctypes.data, self.nv, X.shape[1],
+                                                y.ctypes.data, sh))
 
 
 _validator: Optional[RONIValidator] = None

@@ -1599,6 +1599,90 @@ int bk_grad_cnn(bk_ctx *ctx, const double *ww, int where, const int64_t *idx, in
                 double max_norm, const double *noise, int precision, double *delta_out,
                 int64_t *q_out, double *loss_out, double *norm_out);
 
+/* The two-layer CNN (the reference's lfw model, ML/Pytorch/lfw_cnn_model.py):
+ * Conv2d(c_in, c1, k, 1, pad), ReLU, MaxPool2d(2, 2, 0) (floor mode: a trailing
+ * odd row or column is dropped), Conv2d(c1, c2, k, 1, pad), ReLU,
+ * MaxPool2d(2, 2, 0), Linear(F, n_classes), F = c2 ph2 pw2.  With
+ * oh1 = h + 2 pad - k + 1: ph1 = oh1 / 2, oh2 = ph1 + 2 pad - k + 1,
+ * ph2 = oh2 / 2, the widths likewise.  A sample is c_in h w fp32,
+ * channel-major.  The flat model of d doubles is laid out as
+ * LFWCNNModel.reshape cuts it: conv1 weight (c1 x c_in x k x k, row-major),
+ * conv1 bias, conv2 weight (c2 x c1 x k x k), conv2 bias, fc weight
+ * (n_classes x F, the feature index running (channel, y, x)), fc bias.  lfw is
+ * {3, 62, 47, 3, 1, 18, 36, 2}: F = 5,940, d = 18,254.
+ * BK_ENOTSUP outside 1 <= c_in <= 3, 2 <= h, w <= 64, k in {1, 2, 3},
+ * 0 <= pad < k, 1 <= c1 <= 32, 1 <= c2 <= 48, 2 <= n_classes <= 16, both
+ * pooled maps at least 1 x 1 -- and, narrower than those, outside the LDS of
+ * one compute unit, which holds a sample's first pooled map, its bound operand
+ * and the conv weights:
+ *     4 (2 c1 ps1 + c2 ws + c1 c_in k k + c1 + c2 + 4 s2) <= 150 KiB,
+ *     ps1 = ((ph1 + 2 pad)(pw1 + 2 pad)) | 1,  s2 = ceil(c1 k k / 4),
+ *     ws = 4 (s2 | 1)
+ * (lfw needs 145,232 bytes).
+ *
+ * THE ARITHMETIC, whatever the grid.  ww (the RONI `after` model: ww + delta,
+ * added in fp64) is rounded to fp32.  A conv pre-activation is one fp64 FMA
+ * chain from +0.0 over (input channel, ky, kx) ascending, of exact products of
+ * fp32 operands, a tap in the padding contributing x = 0; then the bias is
+ * added in fp64 and the sum rounded once to fp32.  The activation is
+ * s < 0 ? 0 : s (a NaN stays NaN).  A pooled value is the maximum of its four
+ * fp32 values, NaN if any of them is.  The logit of class c is the fp64 chain
+ * over the flat feature index ascending of exact fp32 products, plus the bias,
+ * rounded once to fp32.  argmax takes the first maximum and NaN wins; wrong,
+ * err and the RONI score are formed as in the softmax entries.
+ *
+ * NEAR TIES: torch's fp32 forward pass, in any summation order and with or
+ * without FMA, can pick another class only on samples for which
+ *     !( l1 - l2 - u (|l1| + |l2|) > E_a + max_c E_c ),  u = 2^-24,
+ * or any logit is not finite.  With gamma_n = n u / (1 - n u), T1 = c_in k k,
+ * T2 = c1 k k, s = 1 + 2^-20, fp32_up(t) = fp32(t (1 + 2^-22) + 2^-126), every
+ * sum an fp64 chain in the order of its value's chain, every product exact:
+ *     g1 = (gamma_{T1+1} + 1.001 u) s      g2 = (gamma_{T2+1} + 1.001 u) s
+ *     h2 = (1 + gamma_{T2+1}) s            hF = (1 + gamma_{F+1}) s
+ *     gF = gamma_{F+1} (1 + 2^-10)
+ *   layer 1   m1 = sum_taps |w1| |x| + |b1|,  t1 = fp32_up(g1 m1): torch's
+ *             pre-activation differs from the exact sum by at most gamma_{T1+1}
+ *             m1, this library's by at most 1.001 u m1; ReLU does not widen it
+ *   pool 1    A1 = max a1, T1p = max t1 over the window (|max a - max a'| is at
+ *             most the window's largest error);  q1 = fp32_up(g2 A1 + h2 T1p)
+ *   layer 2   B2 = sum_taps |w2| q1,  t2 = fp32_up(B2 + g2 |b2|): the sum's own
+ *             error gamma_{T2+1} and this library's rounding 1.001 u, both on
+ *             sum |w2| A1 + |b2|; the incoming errors through |w2|; and torch's
+ *             sum running over its activations, not these: (1 + gamma_{T2+1})
+ *   pool 2    A2 = max a2, T2p = max t2;  qF = fp32_up(gF A2 + hF T2p)
+ *   fc        E_c = sum_f |W_cf| qF_f + gF |b_c|
+ * so each layer's bound is one more accumulator beside the value's, over one
+ * fp32 operand per activation.  fp32 underflow is not modelled.  A score can
+ * differ from the reference's only if one of its two evaluations has a near
+ * tie, and then by at most (near ties) / nb.
+ *
+ *   bk_eval_set_cnn2  a resident evaluation set of a fourth kind: X nv x
+ *                  (c_in h w) fp32 (row stride ldv), y int32 labels in
+ *                  [0, n_classes).  bk_eval, bk_block_finish_eval and
+ *                  bk_eval_clear take it as they take the others (d is the
+ *                  shape's d; all sets of a call of one kind and shape, else
+ *                  BK_EINVAL).
+ *   bk_roni_cnn2_set_validation  the CNN2 verifier's resident validation set.
+ *   bk_roni_cnn2_batches  bk_roni_cnn_batches' semantics and idx layout:
+ *                  evaluation 2 j is the model ww on idx[(2 j) nb ..] (the delta
+ *                  is not read), evaluation 2 j + 1 fp32(ww + delta_j) on
+ *                  idx[(2 j + 1) nb ..]; near_ties (nullable) 2 n counts.
+ *                  Synchronous.
+ * The checks, their order and their codes are the one-layer entries' (ldv is
+ * compared with c_in h w; nv <= 2^31 - 1).  A launch keeps a scratch of
+ * 128 F bytes per 16 samples of an evaluation on the device (BK_ENOMEM if it
+ * cannot).  Rounds, device-pointer forms and this model's gradient are not
+ * built.  Added without a change of BK_ABI_VERSION (14). */
+typedef struct bk_cnn2_shape {
+    int32_t c_in, h, w, k, pad, c1, c2, n_classes;
+} bk_cnn2_shape;
+int bk_eval_set_cnn2(bk_ctx *ctx, int set, const float *X, int64_t nv, int64_t ldv, const int32_t *y,
+                     const bk_cnn2_shape *shape);
+int bk_roni_cnn2_set_validation(bk_ctx *ctx, const float *Xv, int64_t nv, int64_t ldv,
+                                const int32_t *yv, const bk_cnn2_shape *shape);
+int bk_roni_cnn2_batches(bk_ctx *ctx, const double *ww, const double *deltas, int64_t n, int64_t ld,
+                         const int64_t *idx, int64_t nb, double *scores, int32_t *near_ties);
+
 /* ---- measurement: per-kernel HIP-event timing on the context stream ------- */
 enum bk_kernel_id {
     BK_K_GRAM = 0,     /* K1  fp64-MFMA split-K upper-triangle Gram partials */
