@@ -34,6 +34,7 @@ BK_EVAL_MAX_SETS = 4
 BK_SHARES_MAX_POLY, BK_SHARES_MAX_POINTS = 10, 64
 BK_GRAD_MAX_BATCH, BK_GRAD_MAX_D = 65536, 32768  # bk_grad_*: rows of a step; logistic d, softmax d_in
 BK_GRAD_CNN_MAX_BATCH = 4096  # bk_grad_cnn: rows of a step
+BK_GRAD_CNN2_MAX_BATCH = 1024  # bk_grad_cnn2: rows of a step
 
 # every symbol include/bk.h declares: name -> (restype, argtypes)
 _i = ctypes.c_int
@@ -146,6 +147,8 @@ SIGNATURES = {
     "bk_grad_stats": (_i, [_p, _pi64]),
     "bk_grad_set_cnn": (_i, [_p, _p, _i64, _i64, _p, _p]),
     "bk_grad_cnn": (_i, [_p, _p, _i, _p, _i64, _d, _p, _i, _p, _p, _pd, _pd]),
+    "bk_grad_set_cnn2": (_i, [_p, _p, _i64, _i64, _p, _p]),
+    "bk_grad_cnn2": (_i, [_p, _p, _i, _p, _i64, _d, _p, _i, _p, _p, _pd, _pd]),
     "bk_group_create": (_i, [ctypes.POINTER(_p), _i, _p, _i]),
     "bk_group_destroy": (None, [_p]),
     "bk_group_size": (_i, [_p]),

@@ -11,7 +11,7 @@
 
 namespace bk {
 
-static int cnn2_check_shape(const bk_cnn2_shape *sh, Cnn2Dims *out) {
+int cnn2_check_shape(const bk_cnn2_shape *sh, Cnn2Dims *out) {
     if (!sh) return fail(BK_EINVAL, "null shape");
     if (!cnn2_dims(sh->c_in, sh->h, sh->w, sh->k, sh->pad, sh->c1, sh->c2, sh->n_classes, out))
         return fail(BK_ENOTSUP,

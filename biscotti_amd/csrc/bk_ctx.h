@@ -192,11 +192,31 @@ struct GradCnn {
     DevBuf ssq;               // oh: the workgroups' sums of squares
     DevBuf scal;              // the loss sum, the norm, coef
 };
+// the two-layer CNN's step (bk_grad_cnn2_api.hip, kernels bk_grad_cnn2.hip,
+// DESIGN.md §5ac): the split of a position's backward into items, the LDS of
+// the kernels and the layout of a position's scratch -- functions of the shape
+struct GradCnn2Plan {
+    int nw2, nrt2, npl;       // W2 items (column tiles of 16 conv2 taps); row tiles of c2; A1 planes one stages
+    int nd1, nrt1;            // D1 items (bands of GC2_BH pooled-1 rows); row tiles of c1
+    int bw, dps, nbm;         // a band's zero-padded dP2 rows: width, plane stride; its pooled positions
+    int xw, xrows, xps;       // a band's zero-padded input rows: width, count, plane stride
+    int lds_fwd, lds_bwd;     // dynamic LDS bytes of the two kernels
+    // byte offsets in a position's scratch (g2 at 0): the W2 and D1 parts, r and
+    // the loss part, A1's padded planes, A2, both code maps; the scratch's size
+    int64_t o_pw2, o_pd1, o_r, o_a1, o_a2, o_c1, o_c2, stride;
+};
+struct GradCnn2 {
+    Cnn2Dims m = {};
+    GradCnn2Plan p = {};
+    DevBuf scr;               // count x p.stride: the positions' scratch
+    DevBuf ssq, scal;         // the sum's workgroups' sums of squares; the norm, coef
+};
 struct Grad {
-    int kind = EVAL_EMPTY;    // EVAL_LOGISTIC / EVAL_SOFTMAX / EVAL_CNN
+    int kind = EVAL_EMPTY;    // EVAL_LOGISTIC / EVAL_SOFTMAX / EVAL_CNN / EVAL_CNN2
     int64_t nn = 0, d = 0;    // rows; the model's length
     int64_t din = 0, C = 0;   // softmax: d = C (din + 1); CNN: din = h w
     GradCnn cnn;              // CNN: the shape (d = cnn.m.d) and its buffers
+    GradCnn2 cnn2;            // two-layer CNN: the shape (d = cnn2.m.d; din = c_in h w) and its buffers
     DevBuf X, y;              // compact rows (row stride d / din)
     DevBuf w, noise, idx;     // a call's host inputs on the device
     DevBuf R;                 // softmax: the batch's residuals, positions x 16
@@ -261,6 +281,31 @@ GradCnnTiling grad_cnn_tiling(const CnnDims &m);
 hipError_t launch_grad_cnn_fwd(const GradCnnArgs &a, hipStream_t st);
 hipError_t launch_grad_cnn_bwd(const GradCnnArgs &a, hipStream_t st);
 hipError_t launch_grad_cnn_tail(const GradCnnArgs &a, hipStream_t st);
+// bk_grad_cnn2.hip.  scr: count x p.stride bytes; G: the d gradient entries;
+// ssq: one double per workgroup of the sum; scal: the norm, coef; cnt: one
+// zeroed word, used by the sum, left zero
+constexpr int64_t GRAD_CNN2_MAX_BATCH = 1024;
+struct GradCnn2Args {
+    const float *X;
+    const int32_t *y;
+    const double *ww, *noise;
+    const int64_t *rows;
+    int64_t count, nn;
+    Cnn2Dims m;
+    GradCnn2Plan p;
+    double max_norm, scale;
+    char *scr;
+    double *G, *ssq, *scal, *delta;
+    int64_t *q;
+    GradOut *out;
+    unsigned int *cnt;
+};
+// false: the step does not fit one compute unit's LDS (bk.h's formula)
+bool grad_cnn2_plan(const Cnn2Dims &m, GradCnn2Plan *out);
+hipError_t launch_grad_cnn2_fwd(const GradCnn2Args &a, hipStream_t st);
+hipError_t launch_grad_cnn2_bwd(const GradCnn2Args &a, hipStream_t st);
+hipError_t launch_grad_cnn2_sum(const GradCnn2Args &a, hipStream_t st);
+hipError_t launch_grad_cnn2_tail(const GradCnn2Args &a, hipStream_t st);
 // bk_grad_api.hip: what every gradient call shares.  GradIO: where a call's
 // kernels read and write
 struct GradIO {
@@ -707,6 +752,8 @@ int eval_state(bk_ctx *c);
 int check_set_index(int set);
 // bk_cnn_api.hip: bk.h's limits (BK_EINVAL for a null shape, BK_ENOTSUP outside them)
 int cnn_check_shape(const bk_cnn_shape *shape, CnnDims *out);
+// bk_cnn2_api.hip: the shape's limits (bk.h bk_cnn2_shape)
+int cnn2_check_shape(const bk_cnn2_shape *shape, Cnn2Dims *out);
 // bk_cnn2_api.hip: a launch's tile scratch and hand-off counters for `tiles` tiles
 int cnn2_scratch(bk_ctx *c, const Cnn2Dims &m, int64_t tiles);
 // bk_entries.hip: the mapped pinned block a round's score kernels write (count

@@ -23,7 +23,8 @@ namespace bk {
 void grad_destroy(Grad *g) {
     if (!g) return;
     for (DevBuf *b : {&g->X, &g->y, &g->w, &g->noise, &g->idx, &g->R, &g->part, &g->lossp, &g->out,
-                      &g->cnt, &g->cnn.Rp, &g->cnn.Tp, &g->cnn.ssq, &g->cnn.scal})
+                      &g->cnt, &g->cnn.Rp, &g->cnn.Tp, &g->cnn.ssq, &g->cnn.scal, &g->cnn2.scr,
+                      &g->cnn2.ssq, &g->cnn2.scal})
         if (b->p) (void)hipFree(b->p);
     if (g->hout) (void)hipHostFree(g->hout);
     delete g;
@@ -74,7 +75,7 @@ int grad_check_batch(const bk_ctx *c, int kind, const int64_t *idx, int64_t coun
         return fail(BK_EINVAL, "no resident training set: call bk_grad_set_*");
     if (g->kind != kind)
         return fail(BK_EINVAL, "the resident training set is a %s one",
-                    g->kind == EVAL_CNN ? "CNN" : g->kind == EVAL_SOFTMAX ? "softmax" : "logistic");
+                    g->kind == EVAL_CNN2 ? "two-layer CNN" : g->kind == EVAL_CNN ? "CNN" : g->kind == EVAL_SOFTMAX ? "softmax" : "logistic");
     if (idx && count < 1) return fail(BK_EINVAL, "count=%lld < 1", (long long)count);
     if (idx)
         for (int64_t i = 0; i < count; ++i)

@@ -1334,6 +1334,26 @@ class Engine:
         F = co * (h + 2 * pad - k + 1) * (w + 2 * pad - k + 1)
         self._grad = ("cnn", X.shape[0], co * k * k + co + C * F + C)
 
+    def grad_set_cnn2(self, X, y, shape):
+        """X nn x (c_in h w) float32 samples, channel-major, y integer labels in
+        [0, n_classes), shape (c_in, h, w, k, pad, c1, c2, n_classes): the training
+        set of a peer running the two-layer CNN (bk.h bk_cnn2_shape); the model is
+        LFWCNNModel's flat layout."""
+        X = np.asarray(X)
+        if X.ndim != 2 or X.dtype != np.float32 or X.shape[0] < 1:
+            raise ValueError("X must be a float32 matrix, nn x (c_in h w)")
+        if X.strides[1] != 4 or X.strides[0] % 4 or X.strides[0] < 4 * X.shape[1]:
+            X = np.ascontiguousarray(X)
+        y32 = np.ascontiguousarray(y, dtype=np.int32)
+        if y32.shape != (X.shape[0],) or not np.array_equal(y32, np.asarray(y)):
+            raise ValueError("y must have one int32 label per row of X")
+        sh = (ctypes.c_int32 * 8)(*[int(v) for v in shape])
+        if X.shape[1] != sh[0] * sh[1] * sh[2]:
+            raise ValueError("X must have c_in * h * w = %d columns" % (sh[0] * sh[1] * sh[2]))
+        check(lib().bk_grad_set_cnn2(self._ctx, X.ctypes.data, X.shape[0], X.strides[0] // 4,
+                                     y32.ctypes.data, sh))
+        self._grad = ("cnn2", X.shape[0], cnn2_model_length(list(sh)))
+
     def grad_clear(self):
         check(lib().bk_grad_clear(self._ctx))
         self._grad = None
@@ -1356,7 +1376,7 @@ class Engine:
             if ia.min() < 0 or ia.max() >= nn:
                 raise ValueError("idx outside [0, %d)" % nn)
             ix = np.ascontiguousarray(ia, dtype=np.int64)
-        cap = _lib.BK_GRAD_CNN_MAX_BATCH if kind == "cnn" else _lib.BK_GRAD_MAX_BATCH
+        cap = {"cnn": _lib.BK_GRAD_CNN_MAX_BATCH, "cnn2": _lib.BK_GRAD_CNN2_MAX_BATCH}.get(kind, _lib.BK_GRAD_MAX_BATCH)
         if (nn if ix is None else ix.shape[0]) > cap:
             raise ValueError("a batch of more than %d rows" % cap)
         nz = None
@@ -1430,6 +1450,26 @@ class Engine:
                                 _p(noise_ptr), int(precision), _p(delta_ptr), _p(q_ptr),
                                 ctypes.byref(loss) if loss is not None else None,
                                 ctypes.byref(norm) if norm is not None else None))
+
+    def grad_cnn2(self, ww, idx=None, max_norm=100.0, noise=None, precision=None):
+        """privateFun of the two-layer CNN model: (delta, q or None, loss, norm
+        before clipping)."""
+        mn = float(max_norm)
+        if not (np.isfinite(mn) and mn > 0.0):
+            raise ValueError("max_norm must be a positive finite number")
+        w, ix, nz, p, delta, q = self._grad_args("cnn2", ww, idx, noise, precision)
+        loss, norm = ctypes.c_double(), ctypes.c_double()
+        self.grad_cnn2_ptr(w.ctypes.data, _lib.BK_HOST, ix, mn, _ptr(nz), p, delta.ctypes.data,
+                           _ptr(q), loss, norm)
+        return delta, q, loss.value, norm.value
+
+    def grad_cnn2_ptr(self, ww_ptr, where, idx, max_norm, noise_ptr, precision, delta_ptr, q_ptr,
+                      loss=None, norm=None):
+        check(lib().bk_grad_cnn2(self._ctx, _p(ww_ptr), int(where), _p(_ptr(idx)),
+                                 0 if idx is None else int(idx.shape[0]), float(max_norm),
+                                 _p(noise_ptr), int(precision), _p(delta_ptr), _p(q_ptr),
+                                 ctypes.byref(loss) if loss is not None else None,
+                                 ctypes.byref(norm) if norm is not None else None))
 
     def grad_stats(self):
         """[kernel launches, gradient calls] of bk_grad_* since the engine was made."""

@@ -8,6 +8,7 @@ the peer's Python model every iteration, on the peer's shard held on the device.
                       -Client.getGrad() (client.py:38-65: mean cross-entropy,
                       clip_grad_norm(., 100), W then b flattened)
     CNNStepper        the same privateFun on MNISTCNNModel (the one-layer CNN)
+    CNN2Stepper       the same privateFun on LFWCNNModel (the two-layer CNN)
 
 Drawing the mini-batch (np.random.choice, the shuffled loader's first batch)
 and pre-sampling the noise stay the caller's: both steppers take the batch's row
@@ -108,4 +109,26 @@ class CNNStepper(_Stepper):
 
     def private_fun(self, ww, idx=None, noise=None, precision=None):
         delta, q, self.loss, self.norm = self.engine.grad_cnn(ww, idx, self.max_norm, noise, precision)
+        return self._result(delta, q, precision)
+
+
+class CNN2Stepper(_Stepper):
+    """One peer's two-layer CNN (LFWCNNModel; bk.h bk_cnn2_shape): X nn x
+    (c_in h w) float32 samples, y integer labels in [0, n_classes), shape (c_in,
+    h, w, k, pad, c1, c2, n_classes); the model is the flat layout
+    bk_eval_set_cnn2 scores."""
+
+    def __init__(self, X, y, shape, max_norm=100.0, engine: Engine = None):
+        self.shape = tuple(int(v) for v in shape)
+        if len(self.shape) != 8:
+            raise ValueError("shape must be (c_in, h, w, k, pad, c1, c2, n_classes)")
+        self.max_norm = float(max_norm)
+        if not (np.isfinite(self.max_norm) and self.max_norm > 0.0):
+            raise ValueError("max_norm must be a positive finite number")
+        self.engine = engine or default_engine()
+        self.engine.grad_set_cnn2(X, y, self.shape)
+        _, self.nn, self.d = self.engine._grad
+
+    def private_fun(self, ww, idx=None, noise=None, precision=None):
+        delta, q, self.loss, self.norm = self.engine.grad_cnn2(ww, idx, self.max_norm, noise, precision)
         return self._result(delta, q, precision)

@@ -927,6 +927,7 @@ var (
 	bkGradDim       int
 	bkGradSoftmax   bool
 	bkGradCNN       bool
+	bkGradCNN2      bool
 	bkGradBatch     int
 	bkGradPrecision int
 	bkGradAlpha     float64 = 1e-2
@@ -975,6 +976,7 @@ func initGradGPU(X []float64, y []float64, X32 []float32, y32 []int32, d int, cl
 	}
 	bkGradSoftmax = classes != 0
 	bkGradCNN = false
+	bkGradCNN2 = false
 	bkGradBatch = batchSize
 	bkGradPrecision = precision
 	return true
@@ -1008,6 +1010,43 @@ func initGradCNNGPU(X32 []float32, y32 []int32, shape [6]int, precision int) boo
 	bkGradDim = shape[4]*shape[2]*shape[2] + shape[4] + shape[5]*f + shape[5]
 	bkGradSoftmax = false
 	bkGradCNN = true
+	bkGradCNN2 = false
+	bkGradPrecision = precision
+	return true
+}
+
+// initGradCNN2GPU makes the shard of a peer running the two-layer CNN
+// (LFWCNNModel) resident: X32 nn x (c_in h w) float32 samples, channel-major,
+// with labels y32, shape = {c_in, h, w, k, pad, c1, c2, n_classes} (bk.h
+// bk_cnn2_shape; lfw: {3, 62, 47, 3, 1, 18, 36, 2}).  oneGradientStepGPU then
+// steps that model.
+func initGradCNN2GPU(X32 []float32, y32 []int32, shape [8]int32, precision int) bool {
+	bkGradDim = 0
+	nn := len(y32)
+	dIn := int(shape[0] * shape[1] * shape[2])
+	if bkCtx == nil || nn == 0 || dIn == 0 || len(X32) != nn*dIn {
+		return false
+	}
+	var xfp *C.float
+	var yip *C.int32_t
+	var sh C.bk_cnn2_shape
+	xfp = (*C.float)(unsafe.Pointer(&X32[0]))
+	yip = (*C.int32_t)(unsafe.Pointer(&y32[0]))
+	sh = C.bk_cnn2_shape{c_in: C.int32_t(shape[0]), h: C.int32_t(shape[1]), w: C.int32_t(shape[2]),
+		k: C.int32_t(shape[3]), pad: C.int32_t(shape[4]), c1: C.int32_t(shape[5]), c2: C.int32_t(shape[6]),
+		n_classes: C.int32_t(shape[7])}
+	if st := C.bk_grad_set_cnn2(bkCtx, xfp, C.int64_t(nn), C.int64_t(dIn), yip, &sh); st != C.BK_OK {
+		outLog.Printf("bk_grad_set_cnn2 failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	k, pad, c1, c2 := int(shape[3]), int(shape[4]), int(shape[5]), int(shape[6])
+	ph1 := (int(shape[1]) + 2*pad - k + 1) / 2
+	pw1 := (int(shape[2]) + 2*pad - k + 1) / 2
+	f := c2 * ((ph1 + 2*pad - k + 1) / 2) * ((pw1 + 2*pad - k + 1) / 2)
+	bkGradDim = c1*int(shape[0])*k*k + c1 + c2*c1*k*k + c2 + int(shape[7])*f + int(shape[7])
+	bkGradSoftmax = false
+	bkGradCNN = false
+	bkGradCNN2 = true
 	bkGradPrecision = precision
 	return true
 }
@@ -1037,6 +1076,8 @@ func oneGradientStepGPU(globalW []float64, idx []int64) ([]float64, []int64) {
 	}
 	var st C.int
 	switch {
+	case bkGradCNN2:
+		st = C.bk_grad_cnn2(bkCtx, wp, C.BK_HOST, ip, C.int64_t(count), C.double(bkGradMaxNorm), np, C.int(bkGradPrecision), dp, qp, nil, nil)
 	case bkGradCNN:
 		st = C.bk_grad_cnn(bkCtx, wp, C.BK_HOST, ip, C.int64_t(count), C.double(bkGradMaxNorm), np, C.int(bkGradPrecision), dp, qp, nil, nil)
 	case bkGradSoftmax:

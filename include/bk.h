@@ -1671,8 +1671,9 @@ int bk_grad_cnn(bk_ctx *ctx, const double *ww, int where, const int64_t *idx, in
  * The checks, their order and their codes are the one-layer entries' (ldv is
  * compared with c_in h w; nv <= 2^31 - 1).  A launch keeps a scratch of
  * 128 F bytes per 16 samples of an evaluation on the device (BK_ENOMEM if it
- * cannot).  Rounds, device-pointer forms and this model's gradient are not
- * built.  Added without a change of BK_ABI_VERSION (14). */
+ * cannot).  Rounds and device-pointer forms are not built; this model's
+ * gradient step is bk_grad_cnn2 below.  Added without a change of
+ * BK_ABI_VERSION (14). */
 typedef struct bk_cnn2_shape {
     int32_t c_in, h, w, k, pad, c1, c2, n_classes;
 } bk_cnn2_shape;
@@ -1682,6 +1683,82 @@ int bk_roni_cnn2_set_validation(bk_ctx *ctx, const float *Xv, int64_t nv, int64_
                                 const int32_t *yv, const bk_cnn2_shape *shape);
 int bk_roni_cnn2_batches(bk_ctx *ctx, const double *ww, const double *deltas, int64_t n, int64_t ld,
                          const int64_t *idx, int64_t nb, double *scores, int32_t *near_ties);
+
+/* The two-layer CNN's gradient step -- privateFun of a peer running
+ * LFWCNNModel (ML/Pytorch/client_obj.py:73-77 -> client.py:38-65: autograd,
+ * clip_grad_norm(., 100), the flatten), followed by updateFloatToInt.
+ *   bk_grad_set_cnn2  makes the context's ONE resident training set a set of a
+ *                  fourth kind: X nn x (c_in h w) fp32, channel-major (row
+ *                  stride ldx), y int32 labels in [0, n_classes).  The flat
+ *                  model layout is bk_cnn2_shape's; bk_grad_clear empties it.
+ *   bk_grad_cnn2   bk_grad_cnn's semantics for every argument (`where` for ww,
+ *                  noise, delta_out and q_out; host idx, repeats allowed, NULL:
+ *                  every row; precision; nullable outputs; synchronous).
+ * Narrower than bk_cnn2_shape's limits, BK_ENOTSUP unless each of
+ *     4 (c1 ps1 + c2 ws + c1 c_in k k + c1 + c2 + 4 s2 + F)
+ *     9 F + 4 min(c1, 15 / (k k) + 2) ps1
+ *     8 (c2 dps + 32 rt1 pw1) + 4 (c2 c1 k k + c_in (k + 3)(2 pw1 + k - 1)) + 32 rt1 pw1
+ * is at most 131,072 (the second and third rounded up to 16), with
+ * dps = ((k + 1)(pw1 + k - 1)) | 1 and rt1 = ceil(c1 / 16): the LDS of the
+ * forward, of a conv2-weight item and of a conv1 item (lfw: 109,592, 63,360
+ * and 61,232 bytes).
+ *
+ * THE ARITHMETIC, whatever the grid or timing.  N = count.
+ *  1. Forward: the activations and pooled values A1 (c1 x ph1 x pw1) and A2
+ *     (F) of a position are exactly bk_cnn2_shape's above (ww rounded to fp32,
+ *     the fp64 tap chain from +0.0 over (ci, ky, kx) ascending, + bias, one
+ *     rounding to fp32, s < 0 ? 0 : s, the maximum of four).  A pool's selected
+ *     element is the first maximum of its window in (dy, dx) ascending order
+ *     (a NaN, the first one, wins).
+ *  2. The logits stay fp64: lane t in [0, 256) holds the FMA chain from +0.0
+ *     over f = t, t + 256, .. ascending of W[c][f] A2[f]; l[c] = the 256 lane
+ *     values by bk_grad_softmax's tree, + b_c.  NOT bk_eval's single chain.
+ *  3. bk_grad_softmax's rule: the maximum, e^{l - max} summed over c ascending,
+ *     r[s][c] = p - [y_s = c]; the loss part log sum + max - l_y, added over
+ *     groups of 64 positions by a fixed tree, the groups in order; loss = the
+ *     mean cross-entropy.
+ *  4. g2[s][f] = A2 > 0 ? (the FMA chain over c ascending from +0.0 of
+ *     W[c][f] r[s][c]) : 0 (a NaN A2 gives NaN); dP2[s][co][oy][ox] = g2 at
+ *     the pooled position's selected element, 0 elsewhere and outside the kept
+ *     2 ph2 x 2 pw2 positions.
+ *  5. GW[c][f] = (the FMA chain over s ascending from +0.0 of r[s][c]
+ *     A2[s][f]) / N; gb_c the same with A2 = 1.
+ *  6. Per position, Gw2[co][(ci, ky, kx)]: four chains w = 0..3, chain w over
+ *     the pooled positions pp = w, w + 4, .. ascending, one 4-term FMA step per
+ *     pp over its window's (dy, dx) ascending, of dP2[co] A1pad[ci][oy + ky]
+ *     [ox + kx]; the position's value is ((w0 + w1) + w2) + w3.  Gb2[co] the
+ *     same with A1pad = 1.  The entry = the chain of adds from +0.0 over s
+ *     ascending, / N.
+ *  7. dA1[s][ci][y1][x1] = one FMA chain from +0.0 over (co, ky, kx) ascending
+ *     of w2[co][ci][ky][kx] dP2[co][y1 + pad - ky][x1 + pad - kx], masked:
+ *     A1 > 0 ? dA1 : 0 (NaN for a NaN A1); dP1 = dA1 at pool 1's selected
+ *     element, 0 elsewhere.
+ *  8. Per position and band b of two pooled-1 rows, Gw1[c][(ci, ky, kx)] is one
+ *     chain from +0.0 over the band's pooled positions (y1, x1) ascending, one
+ *     4-term step per position over (dy, dx), of dP1[c] xpad; Gb1[c] with
+ *     xpad = 1.  The entry = one chain of adds from +0.0 over (s, b) ascending,
+ *     / N.
+ *  9. norm = sqrt of: workgroup j of the sum covers entries 256 j .., its 256
+ *     squares by the tree; workgroup sums j in lane (j mod 256)'s sum,
+ *     ascending; those 256 by the tree.  coef = max_norm / (norm + 1e-6) scales
+ *     every entry where it is below 1 -- or NaN, so that a NaN anywhere makes
+ *     every entry NaN; delta = -g [+ noise], quantised by
+ *     bk_quantized_sum_device's rule.  norm_out: the norm before clipping.
+ * A NaN in ww gives an all-NaN delta_out and BK_OK.
+ *   bk_grad_stats  counts a CNN2 call's four launches in out[0].
+ * Checked in this order, before any copy or launch.  bk_grad_set_cnn2:
+ * bk_grad_set_cnn's checks and codes (ldx is compared with c_in h w), the LDS
+ * formula right behind the shape's limits.  bk_grad_cnn2: bk_grad_cnn's checks;
+ * the other three gradient entries on a CNN2 set, and bk_grad_cnn2 on a set of
+ * another kind, are BK_EINVAL; BK_ENOTSUP for a batch of more than 1,024 rows
+ * (the scratch is sized by the batch: 258 KiB a position at lfw; the deployed
+ * batch is 10); BK_ENOMEM if the scratch cannot be allocated.
+ * Added without a change of BK_ABI_VERSION (14). */
+int bk_grad_set_cnn2(bk_ctx *ctx, const float *X, int64_t nn, int64_t ldx, const int32_t *y,
+                     const bk_cnn2_shape *shape);
+int bk_grad_cnn2(bk_ctx *ctx, const double *ww, int where, const int64_t *idx, int64_t count,
+                 double max_norm, const double *noise, int precision, double *delta_out,
+                 int64_t *q_out, double *loss_out, double *norm_out);
 
 /* ---- measurement: per-kernel HIP-event timing on the context stream ------- */
 enum bk_kernel_id {
