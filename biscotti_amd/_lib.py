@@ -119,6 +119,9 @@ SIGNATURES = {
     "bk_roni_cnn2_batches": (_i, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _p]),
     "bk_roni_cnn_round_begin": (_i, [_p, _p, _i]),
     "bk_roni_cnn_round_score_batches": (_i, [_p, _p, _i64, _i, _p, _i64, _p, _p]),
+    "bk_roni_cnn2_round_begin": (_i, [_p, _p, _i]),
+    "bk_roni_cnn2_round_score_batches": (_i, [_p, _p, _i64, _i, _p, _i64, _p, _p]),
+    "bk_roni_cnn2_round_set_band": (_i, [_p, _i]),
     "bk_shares_chunks": (_i64, [_i64, _i]),
     "bk_shares_generate": (_i, [_p, _p, _i, _i64, _i, _i, _i, _p]),
     "bk_shares_begin": (_i, [_p, _i64, _i, _i, _i64]),

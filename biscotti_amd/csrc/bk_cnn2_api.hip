@@ -93,6 +93,7 @@ int bk_roni_cnn2_set_validation(bk_ctx *c, const float *Xv, int64_t nv, int64_t 
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard dg(c->device);
     c->c2_nv = 0;  // invalid until the new set has landed
+    c->c2r_live = 0;  // a round's held verdicts were the old set's
     HostDrain drain{c};
     CHK(upload_samples(c, m, c->c2_X, c->c2_y, Xv, nv, ldv, yv));
     drain.armed = false;

@@ -502,6 +502,12 @@ struct bk_ctx {
     // through the other rounds' round_rows, round_idx and round_out
     DevBuf cr_w, cr_flags, cr_scratch, cr_cnt;
     int cr_live = 0;
+    // the CNN2 verifier's round (bk_roni_cnn2_round_*, bk_cnn2_round_api.hip):
+    // the same four for k_cnn2_round (the scratch of at most CNN2_ROUND_TILES
+    // tiles); live until the next begin or bk_roni_cnn2_set_validation.
+    // c2r_band: bk_roni_cnn2_round_set_band (0: cnn2_round_band chooses)
+    DevBuf c2r_w, c2r_flags, c2r_scratch, c2r_cnt;
+    int c2r_live = 0, c2r_band = 0;
     // RONI rounds (bk_roni*_round_*): the iteration's model, its evaluation's
     // counts (logistic: mismatches; softmax: correct, near ties) and the begin's
     // prepared columns (softmax: the widened fp32 weights and their norms), kept
@@ -757,7 +763,8 @@ int cnn2_check_shape(const bk_cnn2_shape *shape, Cnn2Dims *out);
 // bk_cnn2_api.hip: a launch's tile scratch and hand-off counters for `tiles` tiles
 int cnn2_scratch(bk_ctx *c, const Cnn2Dims &m, int64_t tiles);
 // bk_entries.hip: the mapped pinned block a round's score kernels write (count
-// scores, then nnt near-tie counts), shared with bk_cnn_round_api.hip
+// scores, then nnt near-tie counts), shared with bk_cnn_round_api.hip and
+// bk_cnn2_round_api.hip
 int ensure_round_out(bk_ctx *c, int64_t count, int64_t nnt);
 // bk_host.hip
 int stage_host_pipelined(bk_ctx *c, const void *X, int64_t ld, int dtype, const double *noise,

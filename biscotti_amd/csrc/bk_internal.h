@@ -460,6 +460,45 @@ inline size_t cnn_round_tile_floats(const CnnDims &m) {
     return (size_t)2 * cnn_round_chunks(m) * CNN_ROUND_KC * 16;
 }
 hipError_t launch_cnn_round(const CnnRoundLaunch &a, hipStream_t st);
+// bk_cnn2_round.hip: the CNN2 verifier's rounds (bk_roni_cnn2_round_*, DESIGN.md
+// §5ad).  launch_cnn_round's tile space, tiles of CNN2_TS samples, at most
+// CNN2_ROUND_TILES of them a launch -- but a workgroup is (one sample, one band
+// of bh consecutive rows of the second pooled map): the grid is the launch's
+// samples x ceil(ph2 / bh), samp_lo the samples of the space before tile_lo.
+// scratch: tiles x cnn2_tile_floats floats.  cnt: CNN2_ROUND_CNT_WORDS words
+// ([0, 2 G) the updates' counts, then the tiles' hand-off counters, then the
+// exit counter), zero before a group's first launch and left zero by its last
+// (finish != 0).  idx / flags / scores / near as for launch_cnn_round
+constexpr int CNN2_ROUND_TILES = 64;
+constexpr int CNN2_ROUND_CNT_WORDS = 2 * RONI_ROUND_G + CNN2_ROUND_TILES + 1;
+struct Cnn2RoundLaunch {
+    Cnn2Dims m;
+    const float *X;
+    const int32_t *y;
+    int64_t nv;
+    const double *ww;
+    RoundRows rows;
+    int g;
+    const int64_t *idx_dev;
+    RoundIdx idx_arg;
+    int64_t nb, samp_lo;
+    int tile_lo, tiles, bh, finish;
+    uint8_t *flags;
+    float *scratch;
+    unsigned int *cnt;
+    double *scores;
+    int32_t *near;
+};
+// a band of bh rows: its slice of the padded first pooled map (rows and the odd
+// plane stride) and the dynamic LDS of its workgroup; bh = ph2 is k_cnn2's
+__host__ __device__ inline int cnn2_band_rows(const Cnn2Dims &m, int bh) { return 2 * bh + m.k - 1; }
+__host__ __device__ inline int cnn2_band_stride(const Cnn2Dims &m, int bh) {
+    return (cnn2_band_rows(m, bh) * m.P1w) | 1;
+}
+inline int cnn2_band_lds(const Cnn2Dims &m, int bh) {
+    return 4 * (2 * m.c1 * cnn2_band_stride(m, bh) + m.c2 * m.ws + m.c1 * m.T1 + m.c1 + m.c2 + 4 * m.st2);
+}
+hipError_t launch_cnn2_round(const Cnn2RoundLaunch &a, hipStream_t st);
 // bk_i8.hip: K1i8, the Gram of fp32 rows from exact int8 digit slices
 // (BK_F32_I8): column ranges (one per XCD), digit planes [3][npad][dp] int8
 struct I8Layout {

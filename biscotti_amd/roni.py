@@ -282,6 +282,8 @@ class CNNRONIValidator(SoftmaxRONIValidator):
     SoftmaxRONIValidator."""
 
     _batches_entry = "bk_roni_cnn_batches"
+    _round_begin_entry = "bk_roni_cnn_round_begin"
+    _round_score_entry = "bk_roni_cnn_round_score_batches"
 
     def __init__(self, Xvalid, yvalid, shape, engine: Optional[Engine] = None,
                  priv_prob: float = 0.0, batch_size: int = 10, seed=None,
@@ -305,7 +307,7 @@ class CNNRONIValidator(SoftmaxRONIValidator):
                                                y.ctypes.data, sh))
 
     def _begin(self, ww):
-        check(lib().bk_roni_cnn_round_begin(self._engine.ctx, ww.ctypes.data, BK_HOST))
+        check(getattr(lib(), self._round_begin_entry)(self._engine.ctx, ww.ctypes.data, BK_HOST))
 
     def begin_round(self, ww):
         if not self.round_batches:
@@ -315,7 +317,7 @@ class CNNRONIValidator(SoftmaxRONIValidator):
     def score_round(self, deltas, idx=None) -> np.ndarray:
         """Each update against the held model on its two drawn batches (or idx,
         (n, 2, nb)): bitwise scores(ww, deltas, idx)
-        (bk_roni_cnn_round_score_batches)."""
+        (bk_roni_cnn_round_score_batches; the CNN2 validator's entry likewise)."""
         if self._round_ww is None:
             raise ValueError("no round: call begin_round(ww) first")
         rows = [np.ascontiguousarray(r, dtype=np.float64) for r in deltas]
@@ -328,9 +330,9 @@ class CNNRONIValidator(SoftmaxRONIValidator):
         out = np.empty(n, dtype=np.float64)
         nt = np.empty((n, 2), dtype=np.int32)
         table = (ctypes.c_void_p * n)(*[r.ctypes.data for r in rows])
-        check(lib().bk_roni_cnn_round_score_batches(self._engine.ctx, table, n, BK_HOST,
-                                                    idx.ctypes.data, idx.shape[2],
-                                                    out.ctypes.data, nt.ctypes.data))
+        check(getattr(lib(), self._round_score_entry)(self._engine.ctx, table, n, BK_HOST,
+                                                      idx.ctypes.data, idx.shape[2],
+                                                      out.ctypes.data, nt.ctypes.data))
         self.last_idx, self.last_near_ties = idx, nt
         return out
 
@@ -361,13 +363,22 @@ class CNN2RONIValidator(CNNRONIValidator):
     """The torch-path verifier for the two-layer CNN model (LFWCNNModel; bk.h
     bk_cnn2_shape): CNNRONIValidator's mini-batch semantics, scored by
     bk_roni_cnn2_batches.  shape = (c_in, h, w, k, pad, c1, c2, n_classes);
-    Xvalid nv x (c_in h w) float32, channel-major.  No rounds: begin_round and
-    verify_update(round=True) raise."""
+    Xvalid nv x (c_in h w) float32, channel-major.
+
+    Rounds (bk_roni_cnn2_round_*) are opt-in: with round_batches=True,
+    begin_round, score_round(deltas, idx=None) and verify_update(..., round=True)
+    work as CNNRONIValidator's do, bitwise scores(ww, deltas, idx) of a same-seed
+    validator; a default-built validator's begin_round and
+    verify_update(round=True) raise.  set_band(rows) pins the kernel's split of a
+    sample (0: the library's choice); the scores are the same bytes either way."""
 
     _batches_entry = "bk_roni_cnn2_batches"
+    _round_begin_entry = "bk_roni_cnn2_round_begin"
+    _round_score_entry = "bk_roni_cnn2_round_score_batches"
 
     def __init__(self, Xvalid, yvalid, shape, engine: Optional[Engine] = None,
-                 priv_prob: float = 0.0, batch_size: int = 10, seed=None):
+                 priv_prob: float = 0.0, batch_size: int = 10, seed=None,
+                 round_batches: bool = False):
         self._engine = engine if engine is not None else default_engine(0)
         shape = tuple(int(v) for v in shape)
         y = np.ascontiguousarray(yvalid, dtype=np.int32)
@@ -378,13 +389,18 @@ class CNN2RONIValidator(CNNRONIValidator):
         self.d = cnn2_model_length(shape)
         self.priv_prob = priv_prob
         self.batch_size = max(1, min(int(batch_size), self.nv))
-        self.round_batches = False
+        self.round_batches = bool(round_batches)
         self._rng = np.random.default_rng(seed)
         self.last_near_ties = None
         self.last_idx = None
         sh = (ctypes.c_int32 * 8)(*shape)
         check(lib().bk_roni_cnn2_set_validation(self._engine.ctx, X.ctypes.data, self.nv, X.shape[1],
                                                 y.ctypes.data, sh))
+
+    def set_band(self, rows):
+        """Rows of the second pooled map per workgroup of the round's kernel
+        (bk_roni_cnn2_round_set_band); 0: the library's choice per launch."""
+        check(lib().bk_roni_cnn2_round_set_band(self._engine.ctx, int(rows)))
 
 
 _validator: Optional[RONIValidator] = None

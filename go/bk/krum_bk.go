@@ -515,6 +515,51 @@ func verifyUpdateCNN2GPU(globalW []float64, delta []float64, idx []int64) (float
 	return float64(score), true
 }
 
+// beginRoundCNN2GPU is beginRoundCNNGPU for LFWCNNModel
+// (bk_roni_cnn2_round_begin): bc.getLatestGradient() held on the GPU with its
+// verdict on every validation sample for the iteration's verifyUpdate calls.
+// globalW is consumed on return and the evaluation runs on behind it.
+func beginRoundCNN2GPU(globalW []float64) bool {
+	d := len(globalW)
+	if bkCtx == nil || d == 0 {
+		return false
+	}
+	var wp *C.double
+	wp = (*C.double)(unsafe.Pointer(&globalW[0]))
+	if st := C.bk_roni_cnn2_round_begin(bkCtx, wp, C.BK_HOST); st != C.BK_OK {
+		outLog.Printf("bk_roni_cnn2_round_begin failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	return true
+}
+
+// verifyUpdateCNN2RoundGPU is verifyUpdateCNN2GPU against the model held by
+// beginRoundCNN2GPU: the same score, bit for bit, with only the delta uploaded
+// and `original` taken from the held verdicts.  delta's backing array is pinned
+// for the call and consumed on return.
+func verifyUpdateCNN2RoundGPU(delta []float64, idx []int64) (float64, bool) {
+	d := len(delta)
+	nb := len(idx) / 2
+	if bkCtx == nil || d == 0 || nb == 0 {
+		return 0, false
+	}
+	var pinner runtime.Pinner
+	defer pinner.Unpin()
+	var rowsC unsafe.Pointer
+	rowsC = C.malloc(C.size_t(unsafe.Sizeof(uintptr(0))))
+	defer C.free(rowsC)
+	pinner.Pin(&delta[0])
+	unsafe.Slice((*unsafe.Pointer)(rowsC), 1)[0] = unsafe.Pointer(&delta[0])
+	var ip *C.int64_t
+	var score C.double
+	ip = (*C.int64_t)(unsafe.Pointer(&idx[0]))
+	if st := C.bk_roni_cnn2_round_score_batches(bkCtx, (C.bk_row_table)(rowsC), 1, C.BK_HOST, ip, C.int64_t(nb), &score, nil); st != C.BK_OK {
+		outLog.Printf("bk_roni_cnn2_round_score_batches failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return 0, false
+	}
+	return float64(score), true
+}
+
 func evalSetGPU(weights []float64, set int) float64 {
 	d := len(weights)
 	if bkCtx == nil || d == 0 {

@@ -1671,9 +1671,9 @@ int bk_grad_cnn(bk_ctx *ctx, const double *ww, int where, const int64_t *idx, in
  * The checks, their order and their codes are the one-layer entries' (ldv is
  * compared with c_in h w; nv <= 2^31 - 1).  A launch keeps a scratch of
  * 128 F bytes per 16 samples of an evaluation on the device (BK_ENOMEM if it
- * cannot).  Rounds and device-pointer forms are not built; this model's
- * gradient step is bk_grad_cnn2 below.  Added without a change of
- * BK_ABI_VERSION (14). */
+ * cannot).  The verifier's rounds are bk_roni_cnn2_round_* below; device-pointer
+ * forms of bk_roni_cnn2_batches are not built; this model's gradient step is
+ * bk_grad_cnn2 below.  Added without a change of BK_ABI_VERSION (14). */
 typedef struct bk_cnn2_shape {
     int32_t c_in, h, w, k, pad, c1, c2, n_classes;
 } bk_cnn2_shape;
@@ -1683,6 +1683,41 @@ int bk_roni_cnn2_set_validation(bk_ctx *ctx, const float *Xv, int64_t nv, int64_
                                 const int32_t *yv, const bk_cnn2_shape *shape);
 int bk_roni_cnn2_batches(bk_ctx *ctx, const double *ww, const double *deltas, int64_t n, int64_t ld,
                          const int64_t *idx, int64_t nb, double *scores, int32_t *near_ties);
+/* The CNN2 verifier's round: "The CNN verifier's round" above, word for word,
+ * for the two-layer model.
+ *   bk_roni_cnn2_round_begin  needs bk_roni_cnn2_set_validation; ww (the shape's
+ *                  d doubles) at `where`, consumed on return.  The model is kept
+ *                  on the device as fp64 and its verdict on every validation
+ *                  sample as one byte (bit 0 wrong, bit 1 near tie); that
+ *                  evaluation runs on asynchronously on the context stream.  The
+ *                  round lives until the next begin or the next
+ *                  bk_roni_cnn2_set_validation.
+ *   bk_roni_cnn2_round_score_batches  bk_roni_cnn_round_score_batches' rows, idx
+ *                  (a HOST array, count x 2 x nb, repeats counted), outputs and
+ *                  BK_RONI_ROUND_G grouping.  Update j's `original` is the sum
+ *                  of the held bytes over idx[(2 j) nb ..], its `after` one
+ *                  forward pass of idx[(2 j + 1) nb ..] under fp32(ww + delta_j).
+ *                  Only the rows go up.  Synchronous.  Every score and near-tie
+ *                  count is bitwise what one bk_roni_cnn2_batches call on the
+ *                  same ww, rows and idx returns: THE ARITHMETIC and NEAR TIES
+ *                  above, unchanged.
+ *   bk_roni_cnn2_round_set_band  the kernel cuts a sample into bands of `rows`
+ *                  consecutive rows of the second pooled map, one workgroup
+ *                  each; this fixes the band height of the context's later round
+ *                  launches.  0 (the default) leaves the choice to the library
+ *                  per launch, a value above ph2 means one band.  The outputs
+ *                  are the same bytes for every value.  BK_EINVAL for a null ctx
+ *                  or rows < 0.
+ * The checks, their order, their codes and their messages are the one-layer
+ * round's (a refused call leaves the round as it was).  Every shape
+ * bk_roni_cnn2_set_validation accepts is served.  A launch keeps a scratch of
+ * 128 F bytes per 16 samples on the device, at most 64 such tiles a launch.
+ * Added without a change of BK_ABI_VERSION (14); the launches carry no timing
+ * id. */
+int bk_roni_cnn2_round_begin(bk_ctx *ctx, const double *ww, int where);
+int bk_roni_cnn2_round_score_batches(bk_ctx *ctx, bk_row_table deltas, int64_t count, int where,
+                                     const int64_t *idx, int64_t nb, double *scores, int32_t *near_ties);
+int bk_roni_cnn2_round_set_band(bk_ctx *ctx, int rows);   /* 0: the library's choice */
 
 /* The two-layer CNN's gradient step -- privateFun of a peer running
  * LFWCNNModel (ML/Pytorch/client_obj.py:73-77 -> client.py:38-65: autograd,
