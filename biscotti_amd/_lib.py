@@ -117,6 +117,9 @@ SIGNATURES = {
     "bk_eval_set_cnn2": (_i, [_p, _i, _p, _i64, _i64, _p, _p]),
     "bk_roni_cnn2_set_validation": (_i, [_p, _p, _i64, _i64, _p, _p]),
     "bk_roni_cnn2_batches": (_i, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _p]),
+    "bk_eval_set_cnnc": (_i, [_p, _i, _p, _i64, _i64, _p, _p]),
+    "bk_roni_cnnc_set_validation": (_i, [_p, _p, _i64, _i64, _p, _p]),
+    "bk_roni_cnnc_batches": (_i, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _p]),
     "bk_roni_cnn_round_begin": (_i, [_p, _p, _i]),
     "bk_roni_cnn_round_score_batches": (_i, [_p, _p, _i64, _i, _p, _i64, _p, _p]),
     "bk_roni_cnn2_round_begin": (_i, [_p, _p, _i]),

@@ -24,7 +24,8 @@ SOURCES = ["bk_gram.hip", "bk_small.hip", "bk_scores.hip", "bk_mean.hip", "bk_sm
            "bk_commit.hip", "bk_commit_api.hip", "bk_commit_points.hip", "bk_commit_points_api.hip",
            "bk_cnn.hip", "bk_cnn_api.hip", "bk_grad_cnn.hip", "bk_grad_cnn_api.hip",
            "bk_cnn_round.hip", "bk_cnn_round_api.hip", "bk_cnn2.hip", "bk_cnn2_api.hip",
-           "bk_grad_cnn2.hip", "bk_grad_cnn2_api.hip", "bk_cnn2_round.hip", "bk_cnn2_round_api.hip"]
+           "bk_grad_cnn2.hip", "bk_grad_cnn2_api.hip", "bk_cnn2_round.hip", "bk_cnn2_round_api.hip",
+           "bk_cnnc.hip", "bk_cnnc_api.hip"]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -49,7 +50,8 @@ SOURCE_FLAGS = {"bk_commit_points.hip": NO_PACKED_FP32, "bk_commit_points_api.hi
                 "bk_cnn_round.hip": NO_PACKED_FP32, "bk_cnn_round_api.hip": NO_PACKED_FP32,
                 "bk_cnn2.hip": NO_PACKED_FP32, "bk_cnn2_api.hip": NO_PACKED_FP32,
                 "bk_grad_cnn2.hip": NO_PACKED_FP32, "bk_grad_cnn2_api.hip": NO_PACKED_FP32,
-                "bk_cnn2_round.hip": NO_PACKED_FP32, "bk_cnn2_round_api.hip": NO_PACKED_FP32}
+                "bk_cnn2_round.hip": NO_PACKED_FP32, "bk_cnn2_round_api.hip": NO_PACKED_FP32,
+                "bk_cnnc.hip": NO_PACKED_FP32, "bk_cnnc_api.hip": NO_PACKED_FP32}
 LIBS = ["-L" + os.path.join(ROCM, "lib"), "-lrccl", "-Wl,-rpath," + os.path.join(ROCM, "lib")]
 
 

@@ -238,7 +238,7 @@ void bk_destroy(bk_ctx *c) {
                           &c->batch_rec, &c->batch_X, &c->batch_sel, &c->batch_hsc, &c->batch_mean,
                           &c->batch_desc, &c->cnn_X, &c->cnn_y, &c->cnn_cnt,
                           &c->cr_w, &c->cr_flags, &c->cr_scratch, &c->cr_cnt,
-                          &c->c2_X, &c->c2_y, &c->c2_scratch, &c->c2_tcnt,
+                          &c->c2_X, &c->c2_y, &c->c2_scratch, &c->c2_tcnt, &c->cc_X, &c->cc_y,
                           &c->c2r_w, &c->c2r_flags, &c->c2r_scratch, &c->c2r_cnt};
         if (c->hmargin) (void)hipHostFree(c->hmargin);
         if (c->hout) (void)hipHostFree(c->hout);

@@ -151,13 +151,14 @@ struct Shares {
 
 // bk_eval*: the evaluation sets of a context (bk_eval.hip),
 // buffers of their own: RONI's validation sets and rounds never see them
-enum { EVAL_EMPTY = 0, EVAL_LOGISTIC = 1, EVAL_SOFTMAX = 2, EVAL_CNN = 3, EVAL_CNN2 = 4 };
+enum { EVAL_EMPTY = 0, EVAL_LOGISTIC = 1, EVAL_SOFTMAX = 2, EVAL_CNN = 3, EVAL_CNN2 = 4, EVAL_CNNC = 5 };
 struct EvalSlot {
     int kind = EVAL_EMPTY;
     int64_t nv = 0, d = 0;    // samples; the model's length
     int64_t din = 0, C = 0;   // softmax: d = C (din + 1); CNN: din = h w
     CnnDims cnn = {};         // CNN: the shape (d = cnn.d)
     Cnn2Dims cnn2 = {};       // two-layer CNN: the shape (d = cnn2.d; din = c_in h w)
+    CnncDims cnnc = {};       // cifar CNN: the shape (d = cnnc.d; din = c_in h w)
     DevBuf X, y, xn;          // compact rows (row stride d / din); xn: softmax only
 };
 struct Eval {
@@ -493,6 +494,12 @@ struct bk_ctx {
     DevBuf c2_X, c2_y, c2_scratch, c2_tcnt;
     int64_t c2_nv = 0;
     Cnn2Dims c2_dims = {};
+    // the cifar CNN RONI (bk_roni_cnnc_*, bk_cnnc_api.hip): its validation set
+    // (compact c_in h w fp32 rows, int32 labels); the counters are cnn_cnt, a
+    // call's other scratch the softmax form's
+    DevBuf cc_X, cc_y;
+    int64_t cc_nv = 0;
+    CnncDims cc_dims = {};
     // the CNN verifier's round (bk_roni_cnn_round_*, bk_cnn_round_api.hip): the
     // held model (fp64), its verdict on every validation sample (one byte: bit 0
     // wrong, bit 1 near tie), the conv items' scratch of one launch (at most
@@ -760,6 +767,8 @@ int check_set_index(int set);
 int cnn_check_shape(const bk_cnn_shape *shape, CnnDims *out);
 // bk_cnn2_api.hip: the shape's limits (bk.h bk_cnn2_shape)
 int cnn2_check_shape(const bk_cnn2_shape *shape, Cnn2Dims *out);
+// bk_cnnc_api.hip: the shape's limits (bk.h bk_cnnc_shape)
+int cnnc_check_shape(const bk_cnnc_shape *shape, CnncDims *out);
 // bk_cnn2_api.hip: a launch's tile scratch and hand-off counters for `tiles` tiles
 int cnn2_scratch(bk_ctx *c, const Cnn2Dims &m, int64_t tiles);
 // bk_entries.hip: the mapped pinned block a round's score kernels write (count

@@ -352,6 +352,9 @@ int eval_check_sets(bk_ctx *c, int64_t d, const int *sets, int nsets) {
         if (kind == EVAL_CNN2 && memcmp(&s->cnn2, &c->eval->set[sets[0]].cnn2, sizeof(Cnn2Dims)) != 0)
             return fail(BK_EINVAL, "evaluation set %d is of another CNN shape than set %d", sets[i],
                         sets[0]);
+        if (kind == EVAL_CNNC && memcmp(&s->cnnc, &c->eval->set[sets[0]].cnnc, sizeof(CnncDims)) != 0)
+            return fail(BK_EINVAL, "evaluation set %d is of another CNN shape than set %d", sets[i],
+                        sets[0]);
         for (int j = 0; j < i; ++j)
             if (sets[j] == sets[i]) return fail(BK_EINVAL, "evaluation set %d is named twice", sets[i]);
     }
@@ -384,6 +387,7 @@ int eval_queue(bk_ctx *c, const double *dw, const int *sets, int nsets) {
     CHK(ensure_eval_out(c, e));
     const EvalSlot &first = e->set[sets[0]];
     const bool softmax = first.kind == EVAL_SOFTMAX, cnn = first.kind == EVAL_CNN;
+    const bool cnnc = first.kind == EVAL_CNNC;
     if (first.kind == EVAL_CNN2) {  // k_cnn2 (bk_cnn2.hip): a workgroup per sample, fc tiles of 16
         EvalDesc desc = {};
         desc.nsets = nsets;
@@ -410,13 +414,13 @@ int eval_queue(bk_ctx *c, const double *dw, const int *sets, int nsets) {
         ++e->launches;
         return BK_OK;
     }
-    const int ts = cnn ? first.cnn.ts : softmax ? EVAL_LOGITS_TS : EVAL_SIGN_TS;
+    const int ts = cnn ? first.cnn.ts : cnnc ? CNNC_TS : softmax ? EVAL_LOGITS_TS : EVAL_SIGN_TS;
     EvalDesc desc = {};
     desc.nsets = nsets;
     int64_t tiles = 0;
     for (int i = 0; i < nsets; ++i) {
         const EvalSlot &s = e->set[sets[i]];
-        desc.s[i] = {s.X.p, s.y.p, (const double *)s.xn.p, s.nv, softmax || cnn ? s.din : s.d,
+        desc.s[i] = {s.X.p, s.y.p, (const double *)s.xn.p, s.nv, softmax || cnn || cnnc ? s.din : s.d,
                      (int)tiles};
         tiles += (s.nv + ts - 1) / ts;
         if (tiles > 0x7fffffff) return fail(BK_ENOTSUP, "the sets' %lld tiles exceed the grid",
@@ -431,6 +435,18 @@ int eval_queue(bk_ctx *c, const double *dw, const int *sets, int nsets) {
         a.out = e->out_dev;
         const hipError_t he = launch_cnn(a, tiles, c->stream);
         if (he != hipSuccess) return fail(BK_EHIP, "k_cnn launch: %s", hipGetErrorString(he));
+        ++e->launches;
+        return BK_OK;
+    }
+    if (cnnc) {  // k_cnnc (bk_cnnc.hip): likewise
+        CnncLaunch a = {};
+        a.desc = desc;
+        a.m = first.cnnc;
+        a.ww = dw;
+        a.cnt = (unsigned int *)e->cnt.p;
+        a.out = e->out_dev;
+        const hipError_t he = launch_cnnc(a, tiles, c->stream);
+        if (he != hipSuccess) return fail(BK_EHIP, "k_cnnc launch: %s", hipGetErrorString(he));
         ++e->launches;
         return BK_OK;
     }

@@ -418,6 +418,36 @@ constexpr int CNN2_TS = 16;  // samples per fc tile: the MFMA's columns
 inline int64_t cnn2_tiles(int64_t samples) { return (samples + CNN2_TS - 1) / CNN2_TS; }
 __host__ __device__ inline size_t cnn2_tile_floats(const Cnn2Dims &m) { return (size_t)2 * m.F4 * CNN2_TS; }
 hipError_t launch_cnn2(const Cnn2Launch &a, int64_t samples, hipStream_t st);
+// bk_cnnc.hip: the one-layer cifar CNN's forward pass (bk.h bk_cnnc_shape,
+// DESIGN.md §5ae): launch_cnn's two addressings, counters and outputs, with
+// tiles of CNNC_TS samples whatever the shape
+struct CnncDims {
+    int c_in, h, w, k, pad, co, C;
+    int oh, ow, ph, pw;  // the output plane; the padded input plane
+    int T, Fc, nchc;     // taps c_in k k; features and 64-feature chunks of one channel
+    int W, D;            // the band ring: a row's stride in x, its depth in rows
+    int lds;             // dynamic LDS bytes
+    int64_t F, d;        // features co oh ow; the flat model's length
+};
+// false: outside bk.h's limits; *lds_ok: the band ring fits a compute unit's LDS
+bool cnnc_dims(int c_in, int h, int w, int k, int pad, int co, int C, CnncDims *out, bool *lds_ok);
+// the near-tie bound's two factors (bk.h): g_F on the activation, g_e on the tap magnitudes
+void cnnc_gammas(const CnncDims &m, double *gF, double *ge);
+struct CnncLaunch {
+    EvalDesc desc;
+    CnncDims m;
+    const double *ww, *deltas;
+    int64_t ld;
+    const int64_t *idx;
+    int64_t nb, n;
+    unsigned int *cnt;
+    EvalOut *out;
+    double *scores;
+    int32_t *near;
+};
+constexpr int CNNC_TS = 16;  // samples per tile: the MFMA's columns
+__host__ __device__ inline int cnnc_tiles(int64_t samples) { return (int)((samples + CNNC_TS - 1) / CNNC_TS); }
+hipError_t launch_cnnc(const CnncLaunch &a, int64_t tiles, hipStream_t st);
 // bk_cnn_round.hip: the CNN verifier's rounds (bk_roni_cnn_round_*, DESIGN.md
 // §5aa).  One launch runs `tiles` sample tiles (dims.ts samples each) of a
 // linear tile space, from tile_lo on: the begin's (g = 0) is the validation set

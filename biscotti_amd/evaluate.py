@@ -15,7 +15,7 @@ from typing import Optional
 
 import numpy as np
 
-from .krum import Engine, cnn2_model_length, default_engine
+from .krum import Engine, cnn2_model_length, cnnc_model_length, default_engine
 
 __all__ = ["ModelEvaluator", "TRAIN", "TEST", "ATTACK"]
 
@@ -29,18 +29,21 @@ class ModelEvaluator:
     n_classes * (d_in + 1) entries: W row-major, then b).  cnn_shape = (h, w, k,
     pad, c_out, n_classes): the one-layer CNN model instead (set_cnn);
     cnn2_shape = (c_in, h, w, k, pad, c1, c2, n_classes): the two-layer one
-    (set_cnn2).
+    (set_cnn2); cnnc_shape = (c_in, h, w, k, pad, c_out, n_classes): the
+    one-layer cifar one (set_cnnc).
 
     One evaluator per engine at a time: the sets live in the engine's context
     (slots TRAIN, TEST, ATTACK)."""
 
     def __init__(self, train=None, test=None, attack=None, n_classes: Optional[int] = None,
-                 engine: Optional[Engine] = None, cnn_shape=None, cnn2_shape=None):
-        if cnn_shape is not None or cnn2_shape is not None:  # the CNN models (bk.h bk_cnn*_shape)
+                 engine: Optional[Engine] = None, cnn_shape=None, cnn2_shape=None, cnnc_shape=None):
+        if cnn_shape is not None or cnn2_shape is not None or cnnc_shape is not None:  # the CNN models (bk.h bk_cnn*_shape)
             self._engine = engine if engine is not None else default_engine(0)
             self._slots, self.near_ties = [], {}
             for slot, s in ((TRAIN, train), (TEST, test), (ATTACK, attack)):
-                if s is not None and cnn2_shape is not None:
+                if s is not None and cnnc_shape is not None:
+                    self.set_cnnc(slot, s[0], s[1], cnnc_shape)
+                elif s is not None and cnn2_shape is not None:
                     self.set_cnn2(slot, s[0], s[1], cnn2_shape)
                 elif s is not None:
                     self.set_cnn(slot, s[0], s[1], cnn_shape)
@@ -104,6 +107,18 @@ class ModelEvaluator:
         X = np.ascontiguousarray(X, dtype=np.float32).reshape(len(y), -1)
         self._engine.eval_set_cnn2(slot, X, y, shape)
         self.n_classes, self.d_in, self.d = shape[7], X.shape[1], cnn2_model_length(shape)
+        if slot not in self._slots:
+            self._slots.append(slot)
+
+    def set_cnnc(self, slot, X, y, shape):
+        """Make (X, y) the slot's set for the one-layer cifar CNN model of `shape`
+        = (c_in, h, w, k, pad, c_out, n_classes): X nv x (c_in h w) float32,
+        channel-major.  test_error, attack_rate and check_convergence then score
+        CIFARCNNModel's flat model."""
+        shape = tuple(int(v) for v in shape)
+        X = np.ascontiguousarray(X, dtype=np.float32).reshape(len(y), -1)
+        self._engine.eval_set_cnnc(slot, X, y, shape)
+        self.n_classes, self.d_in, self.d = shape[6], X.shape[1], cnnc_model_length(shape)
         if slot not in self._slots:
             self._slots.append(slot)
 

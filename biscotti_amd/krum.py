@@ -193,6 +193,14 @@ def cnn2_model_length(shape):
     return c1 * ci * k * k + c1 + c2 * c1 * k * k + c2 + C * F + C
 
 
+def cnnc_model_length(shape):
+    """d of the one-layer cifar CNN model of shape (c_in, h, w, k, pad, c_out,
+    n_classes), as bk.h's bk_cnnc_shape section counts it."""
+    ci, h, w, k, pad, co, C = (int(v) for v in shape)
+    F = co * (h + 2 * pad - k + 1) * (w + 2 * pad - k + 1)
+    return co * ci * k * k + co + C * F + C
+
+
 class Engine:
     """One libbk context (bk_ctx) bound to one GPU."""
 
@@ -880,6 +888,52 @@ class Engine:
             raise ValueError("X must have c_in * h * w = %d columns" % (sh[0] * sh[1] * sh[2]))
         check(lib().bk_eval_set_cnn2(self._ctx, int(set_index), X.ctypes.data, X.shape[0],
                                      X.strides[0] // 4, y32.ctypes.data, sh))
+
+    @staticmethod
+    def _cnnc_args(X, y, shape):
+        X = np.asarray(X)
+        if X.ndim != 2 or X.dtype != np.float32 or X.shape[0] < 1:
+            raise ValueError("X must be a float32 matrix, nv x (c_in h w)")
+        if X.strides[1] != 4 or X.strides[0] % 4 or X.strides[0] < 4 * X.shape[1]:
+            X = np.ascontiguousarray(X)
+        y32 = np.ascontiguousarray(y, dtype=np.int32)
+        if y32.shape != (X.shape[0],) or not np.array_equal(y32, np.asarray(y)):
+            raise ValueError("y must have one int32 label per row of X")
+        sh = (ctypes.c_int32 * 7)(*[int(v) for v in shape])
+        if X.shape[1] != sh[0] * sh[1] * sh[2]:
+            raise ValueError("X must have c_in * h * w = %d columns" % (sh[0] * sh[1] * sh[2]))
+        return X, y32, sh
+
+    def eval_set_cnnc(self, set_index, X, y, shape):
+        """X nv x (c_in h w) float32 samples (channel-major), y integer labels in
+        [0, n_classes), shape (c_in, h, w, k, pad, c_out, n_classes): a set for
+        the one-layer cifar CNN model (bk.h bk_cnnc_shape); the model scored on
+        it is CIFARCNNModel's flat layout."""
+        X, y32, sh = self._cnnc_args(X, y, shape)
+        check(lib().bk_eval_set_cnnc(self._ctx, int(set_index), X.ctypes.data, X.shape[0],
+                                     X.strides[0] // 4, y32.ctypes.data, sh))
+
+    def roni_cnnc_set_validation(self, X, y, shape):
+        """The CNNC verifier's resident validation set (bk_roni_cnnc_set_validation);
+        X, y and shape as for eval_set_cnnc."""
+        X, y32, sh = self._cnnc_args(X, y, shape)
+        check(lib().bk_roni_cnnc_set_validation(self._ctx, X.ctypes.data, X.shape[0],
+                                                X.strides[0] // 4, y32.ctypes.data, sh))
+
+    def roni_cnnc_batches(self, ww, deltas, idx):
+        """bk_roni_cnnc_batches: update j scored as after - original on its two
+        batches idx[j, 0] (model ww) and idx[j, 1] (model ww + deltas[j]); idx is
+        (n, 2, nb) int64.  Returns (scores n, near ties n x 2)."""
+        ww = np.ascontiguousarray(ww, dtype=np.float64)
+        D = np.ascontiguousarray(np.atleast_2d(deltas), dtype=np.float64)
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        n = D.shape[0]
+        if ww.ndim != 1 or D.shape[1] != ww.shape[0] or idx.ndim != 3 or idx.shape[:2] != (n, 2):
+            raise ValueError("ww must be (d,), deltas (n, d) and idx (n, 2, nb)")
+        out, nt = np.empty(n, dtype=np.float64), np.empty((n, 2), dtype=np.int32)
+        check(lib().bk_roni_cnnc_batches(self._ctx, ww.ctypes.data, D.ctypes.data, n, D.shape[1],
+                                         idx.ctypes.data, idx.shape[2], out.ctypes.data, nt.ctypes.data))
+        return out, nt
 
     def eval_clear(self, set_index):
         check(lib().bk_eval_clear(self._ctx, int(set_index)))

@@ -23,9 +23,9 @@ import ctypes
 import numpy as np
 
 from ._lib import BK_HOST, check, lib
-from .krum import Engine, Update, cnn2_model_length, default_engine
+from .krum import Engine, Update, cnn2_model_length, cnnc_model_length, default_engine
 
-__all__ = ["RONI_THRESHOLD", "RONIValidator", "SoftmaxRONIValidator", "CNNRONIValidator", "CNN2RONIValidator",
+__all__ = ["RONI_THRESHOLD", "RONIValidator", "SoftmaxRONIValidator", "CNNRONIValidator", "CNN2RONIValidator", "CNNCRONIValidator",
            "set_validation", "roni"]
 
 RONI_THRESHOLD = 0.02  # main.go:213
@@ -401,6 +401,40 @@ class CNN2RONIValidator(CNNRONIValidator):
         """Rows of the second pooled map per workgroup of the round's kernel
         (bk_roni_cnn2_round_set_band); 0: the library's choice per launch."""
         check(lib().bk_roni_cnn2_round_set_band(self._engine.ctx, int(rows)))
+
+
+class CNNCRONIValidator(CNNRONIValidator):
+    """The torch-path verifier for the one-layer cifar CNN model (CIFARCNNModel;
+    bk.h bk_cnnc_shape): CNNRONIValidator's mini-batch semantics, scored by
+    bk_roni_cnnc_batches.  shape = (c_in, h, w, k, pad, c_out, n_classes);
+    Xvalid nv x (c_in h w) float32, channel-major.  Rounds are not built for
+    this model: begin_round, score_round and verify_update(round=True) raise."""
+
+    _batches_entry = "bk_roni_cnnc_batches"
+
+    def __init__(self, Xvalid, yvalid, shape, engine: Optional[Engine] = None,
+                 priv_prob: float = 0.0, batch_size: int = 10, seed=None):
+        self._engine = engine if engine is not None else default_engine(0)
+        shape = tuple(int(v) for v in shape)
+        y = np.ascontiguousarray(yvalid, dtype=np.int32)
+        X = np.ascontiguousarray(Xvalid, dtype=np.float32).reshape(len(y), -1)
+        if X.shape[1] != shape[0] * shape[1] * shape[2]:
+            raise ValueError("Xvalid must be (nv, c_in * h * w)")
+        self.nv, self.d_in, self.n_classes = X.shape[0], X.shape[1], shape[6]
+        self.d = cnnc_model_length(shape)
+        self.priv_prob = priv_prob
+        self.batch_size = max(1, min(int(batch_size), self.nv))
+        self.round_batches = False
+        self._rng = np.random.default_rng(seed)
+        self.last_near_ties = None
+        self.last_idx = None
+        self._engine.roni_cnnc_set_validation(X, y, shape)
+
+    def begin_round(self, ww):
+        raise ValueError("rounds are not built for the cifar CNN model")
+
+    def score_round(self, deltas, idx=None):
+        raise ValueError("rounds are not built for the cifar CNN model")
 
 
 _validator: Optional[RONIValidator] = None

@@ -515,6 +515,54 @@ func verifyUpdateCNN2GPU(globalW []float64, delta []float64, idx []int64) (float
 	return float64(score), true
 }
 
+// setEvalCNNCGPU is the form for CIFARCNNModel (the one-layer cifar CNN, bk.h
+// bk_cnnc_shape {c_in, h, w, k, pad, c_out, n_classes}): X nv x (c_in h w)
+// float32, channel-major, y the labels.  testModelGPU and testAttackRateGPU
+// then score the CNN's flat model on the slot.
+func setEvalCNNCGPU(set int, X []float32, y []int32, shape [7]int32) bool {
+	nv := len(y)
+	dIn := int(shape[0] * shape[1] * shape[2])
+	if bkCtx == nil || nv == 0 || dIn == 0 || len(X) != nv*dIn {
+		return false
+	}
+	var xp *C.float
+	var yp *C.int32_t
+	var sh C.bk_cnnc_shape
+	xp = (*C.float)(unsafe.Pointer(&X[0]))
+	yp = (*C.int32_t)(unsafe.Pointer(&y[0]))
+	sh = C.bk_cnnc_shape{c_in: C.int32_t(shape[0]), h: C.int32_t(shape[1]), w: C.int32_t(shape[2]),
+		k: C.int32_t(shape[3]), pad: C.int32_t(shape[4]), c_out: C.int32_t(shape[5]),
+		n_classes: C.int32_t(shape[6])}
+	if st := C.bk_eval_set_cnnc(bkCtx, C.int(set), xp, C.int64_t(nv), C.int64_t(dIn), yp, &sh); st != C.BK_OK {
+		outLog.Printf("bk_eval_set_cnnc failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return false
+	}
+	return true
+}
+
+// verifyUpdateCNNCGPU is verifyUpdateCNN2GPU for CIFARCNNModel: the update's
+// score, after - original on the two drawn mini-batches idx[0:nb] and
+// idx[nb:2 nb] of the validation set given once to bk_roni_cnnc_set_validation.
+// ok is false on an engine error (the caller then falls back to the Python call).
+func verifyUpdateCNNCGPU(globalW []float64, delta []float64, idx []int64) (float64, bool) {
+	d := len(globalW)
+	nb := len(idx) / 2
+	if bkCtx == nil || d == 0 || len(delta) != d || nb == 0 {
+		return 0, false
+	}
+	var wp, dp *C.double
+	var ip *C.int64_t
+	var score C.double
+	wp = (*C.double)(unsafe.Pointer(&globalW[0]))
+	dp = (*C.double)(unsafe.Pointer(&delta[0]))
+	ip = (*C.int64_t)(unsafe.Pointer(&idx[0]))
+	if st := C.bk_roni_cnnc_batches(bkCtx, wp, dp, 1, C.int64_t(d), ip, C.int64_t(nb), &score, nil); st != C.BK_OK {
+		outLog.Printf("bk_roni_cnnc_batches failed (%d): %s", int(st), C.GoString(C.bk_last_error()))
+		return 0, false
+	}
+	return float64(score), true
+}
+
 // beginRoundCNN2GPU is beginRoundCNNGPU for LFWCNNModel
 // (bk_roni_cnn2_round_begin): bc.getLatestGradient() held on the GPU with its
 // verdict on every validation sample for the iteration's verifyUpdate calls.

@@ -1795,6 +1795,86 @@ int bk_grad_cnn2(bk_ctx *ctx, const double *ww, int where, const int64_t *idx, i
                  double max_norm, const double *noise, int precision, double *delta_out,
                  int64_t *q_out, double *loss_out, double *norm_out);
 
+/* The one-layer cifar CNN (the reference's cifar model,
+ * ML/Pytorch/cifar_cnn_model.py): Conv2d(c_in, c_out, k, stride 1, padding pad)
+ * on a c_in x h x w fp32 image (channel-major, as torch's NCHW), ReLU,
+ * MaxPool2d(1) (the identity), then Linear(F, n_classes) with F = c_out oh ow,
+ * oh = h + 2 pad - k + 1, ow likewise.  With T = c_in k k the flat model of
+ * d = c_out T + c_out + n_classes F + n_classes doubles is laid out as
+ * CIFARCNNModel.reshape cuts it: the conv weight (c_out x c_in x k x k,
+ * row-major), the conv bias, the fc weight (n_classes x F, the feature index
+ * running (channel, y, x)), the fc bias.  cifar is {3, 32, 32, 3, 3, 20, 10}:
+ * oh = ow = 36, F = 25,920, d = 259,770.
+ * BK_ENOTSUP outside 1 <= c_in <= 4, 1 <= h, w <= 64, 1 <= k <= 5,
+ * 0 <= pad <= k (pad = k is allowed), k <= h + 2 pad, k <= w + 2 pad,
+ * 1 <= c_out <= 32, 2 <= n_classes <= 16 -- and, narrower than those and
+ * checked right behind them, for a shape whose band of input rows does not fit
+ * the LDS of one compute unit:
+ *     8 ceil2(c_out T) + 64 c_in D W <= 136 KiB,   W = w + 2 pad + (-(k - 1) mod 4),
+ * ceil2 rounding up to even, D the largest number of consecutive padded input
+ * rows that two consecutive 64-feature chunks of one output channel's (y, x)
+ * walk touch, the k - 1 rows below the last included and the walk continued
+ * into the next channel (cifar: D = 7, 58,080 bytes).  A tile is 16 samples at
+ * every shape.
+ *
+ * THE ARITHMETIC, whatever the grid.  ww (the RONI `after` model: ww + delta,
+ * added in fp64) is rounded to fp32.  The pre-activation of (ch, y, x) is one
+ * fp64 FMA chain from +0.0 over the taps (ci, ky, kx) row-major ascending --
+ * the conv weight's own order -- of exact products of fp32 operands, a tap in
+ * the padding contributing x = 0; then the bias is added in fp64 and the sum
+ * rounded once to fp32.  The activation is s < 0 ? 0 : s (a NaN stays NaN).
+ * The logit of class c is the fp64 chain over the flat feature index ascending
+ * of exact fp32 products, plus the bias, rounded once to fp32.  argmax takes
+ * the first maximum and NaN wins; wrong, err and the RONI score are formed as
+ * in the softmax entries.
+ *
+ * NEAR TIES: torch's fp32 convolution and sgemm, in any summation order and
+ * with or without FMA, can pick another class only on samples for which
+ *     !( l1 - l2 - u (|l1| + |l2|) > E_a + max_c E_c ),  u = 2^-24,
+ *     E_c = sum_k |W_ck| t_k + g_F |b_c|,
+ *     t_k = fp32_up( g_F a_k + g_e m_k ),   m_k = sum_taps |w| |x| + |b_ch|,
+ * or any logit is not finite (l1: the winning logit, class a; l2: the best
+ * other).  a_k is this library's activation of feature k, m_k its taps'
+ * magnitudes (an fp64 chain in the taps' order like the pre-activation's, then
+ * + |b_ch|), T = c_in k k,
+ *     g_F = gamma_{F+1}(u) (1 + 2^-10),
+ *     g_e = (gamma_{T+1}(u) + 1.001 u) (1 + gamma_{F+1}(u)) (1 + 2^-20),
+ * gamma_n(u) = n u / (1 - n u), fp32_up(t) = fp32(t (1 + 2^-22) + 2^-126) (not
+ * below t), and the sum over k is an fp64 chain over k ascending of exact
+ * products: bk_cnn_shape's rule with its T.  fp32 underflow is not modelled.
+ * A score can differ from the reference's only if one of its two evaluations
+ * has a near tie, and then by at most (near ties) / nb.
+ * With c_in = 1 and a shape bk_cnn_shape also accepts, both statements
+ * coincide: every output is bitwise bk_eval_set_cnn's / bk_roni_cnn_batches'.
+ *
+ *   bk_eval_set_cnnc  a resident evaluation set of a fifth kind: X nv x
+ *                  (c_in h w) fp32 (row stride ldv), y int32 labels in
+ *                  [0, n_classes).  bk_eval, bk_block_finish_eval and
+ *                  bk_eval_clear take it as they take the others (d is the
+ *                  shape's d; all sets of a call of one kind and shape, else
+ *                  BK_EINVAL).
+ *   bk_roni_cnnc_set_validation  the CNNC verifier's resident validation set.
+ *   bk_roni_cnnc_batches  bk_roni_cnn_batches' semantics and idx layout:
+ *                  evaluation 2 j is the model ww on idx[(2 j) nb ..] (the delta
+ *                  is not read), evaluation 2 j + 1 fp32(ww + delta_j) on
+ *                  idx[(2 j + 1) nb ..]; near_ties (nullable) 2 n counts;
+ *                  n <= 262139.  Synchronous.
+ * The checks, their order and their codes are bk_eval_set_cnn's and
+ * bk_roni_cnn_batches', before any copy (ldv is compared with c_in h w); a
+ * refused call leaves the state as it was.  The verifier's rounds, device-pointer
+ * forms of bk_roni_cnnc_batches and this model's gradient step are not built.
+ * Added without a change of BK_ABI_VERSION (14); the launches carry no timing
+ * id. */
+typedef struct bk_cnnc_shape {
+    int32_t c_in, h, w, k, pad, c_out, n_classes;
+} bk_cnnc_shape;
+int bk_eval_set_cnnc(bk_ctx *ctx, int set, const float *X, int64_t nv, int64_t ldv, const int32_t *y,
+                     const bk_cnnc_shape *shape);
+int bk_roni_cnnc_set_validation(bk_ctx *ctx, const float *Xv, int64_t nv, int64_t ldv,
+                                const int32_t *yv, const bk_cnnc_shape *shape);
+int bk_roni_cnnc_batches(bk_ctx *ctx, const double *ww, const double *deltas, int64_t n, int64_t ld,
+                         const int64_t *idx, int64_t nb, double *scores, int32_t *near_ties);
+
 /* ---- measurement: per-kernel HIP-event timing on the context stream ------- */
 enum bk_kernel_id {
     BK_K_GRAM = 0,     /* K1  fp64-MFMA split-K upper-triangle Gram partials */
